@@ -9,7 +9,8 @@ over ranks with no data-path collective; after every clip the ranks all_gather t
 random tensors of the exact SVD-XT / DepthCrafter architecture (no checkpoints on the box) -
 throughput is weight-value independent.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps clips, writes --dump-outputs and prints the line;
+--full also measures everything else on the same line (side rates, calibration probes, `roofline`, `cpu_baseline`, ...).
 """
 import argparse
 import json
@@ -231,6 +232,28 @@ def cpu_baseline_stablenormal(threads):
             "sample_wall_s": round(wall, 2), "weight_init_s": round(t_init, 1)}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` = (name, array) pairs in priority order, written as float32 out_dir/<name>.npy while they fit DUMP_BUDGET_BYTES whole;
+    a later one that does not is written as out_dir/<name>_sample.npy: as many of its elements as the rest of the budget holds, at flat indices drawn
+    without replacement by numpy default_rng(0) and sorted - the same indices in every run of the same configuration."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, arr in arrays:
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        left -= 128                                              # .npy header
+        if arr.nbytes <= left:
+            np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+            left -= arr.nbytes
+            continue
+        k = max(0, left // 4)
+        idx = np.sort(np.random.default_rng(0).choice(arr.size, k, replace=False))
+        np.save(os.path.join(out_dir, f"{name}_sample.npy"), arr.reshape(-1)[idx])
+        left -= 4 * k
+
+
 def sn_images_in_flight(preds, img, reps):
     """images/s of len(preds) StableNormal predictor contexts on one GPU, each on its own host thread, one image per call (tools/sn_images_in_flight.py)."""
     import threading
@@ -269,9 +292,11 @@ def bench_stablenormal(a):
             pred.predict_batch(x)
         t0 = time.perf_counter()
         for _ in range(n):
-            pred.predict_batch(x)
-        return n * B / (time.perf_counter() - t0), (time.perf_counter() - t0) / n * 1e3
-    v1, ms1 = rate(1, a.steps, a.warmup)
+            y = pred.predict_batch(x)
+        return n * B / (time.perf_counter() - t0), (time.perf_counter() - t0) / n * 1e3, y
+    v1, ms1, normals1 = rate(1, a.steps, a.warmup)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, [("normals", normals1)])
     # round 5: independent images in flight (the reference calls the predictor once per frame, model/stablenormal.py:39; frames are independent): a batch-1 image's
     # launches have 81 - 5184 rows and leave most of the chip idle - further predictor contexts on their own streams / host threads run there
     v_fl = None
@@ -281,7 +306,7 @@ def bench_stablenormal(a):
             print("[debug] hip runtimes mapped:", sorted({l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l}), "torch" in sys.modules, file=sys.stderr)
         for p_ in extra:
             p_.engine.close()
-    v8, _ = rate(8, max(1, a.steps // 2), 1)
+    v8, _, _ = rate(8, max(1, a.steps // 2), 1)
     # the reference's own use (configs/stablenormal_scannetpp.yaml): 25-frame clips at 384x512 - here one batch per clip
     x25 = np.clip(rng.uniform(0, 255, (25, 384, 512, 3)), 0, 255).astype(np.uint8).astype(np.float32) / 255.0
     pred.predict_batch(x25)
@@ -349,9 +374,9 @@ def main():
                     help="independent clips in flight per GPU INSIDE THE TIMED REGION.  Default 1: `value` / `ms_per_step` are SURVEY 8(d)'s quantity - one clip per "
                          "ug_dc_run call, one call at a time, as the reference harness drives the plugin (eval.py:33-39).  N > 1 = that many engine contexts (own weights "
                          "replica, workspace, HIP stream, host thread; clip i on context i %% N) - the throughput mode for BASELINE configs[2]; the line then says so in "
-                         "config.workload and carries value_one_clip_at_a_time beside it")
+                         "config.workload and, with --full, carries value_one_clip_at_a_time beside it")
     ap.add_argument("--side-in-flight", type=int, default=3,
-                    help="clips in flight for the SIDE rate value_clips_in_flight, measured after the timed region on one GPU (0 / 1 = skip).  Clips are independent samples "
+                    help="--full: clips in flight for the SIDE rate value_clips_in_flight, measured after the timed region on one GPU (0 / 1 = skip).  Clips are independent samples "
                          "(reference eval.py:33-56): a second clip fills the CUs that one clip's tile tails and under-filled launches leave idle "
                          "(tools/two_clips_in_flight.py)")
     ap.add_argument("--sn-in-flight", type=int, default=4, help="--workload stablenormal: images in flight for value_images_in_flight (1 = skip)")
@@ -363,7 +388,17 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: run the UNet transformers' linear layers on MX-fp8 matrix instructions "
                     "(reduced precision; the headline metric is the fp16 path)")
     ap.add_argument("--tiny", action="store_true", help="tiny full-topology weights instead of the 1.5 B-parameter architecture (plumbing checks only)")
+    ap.add_argument("--full", action="store_true",
+                    help="depthcrafter workload: besides the headline also measure everything else - the clips-in-flight and one-clip-at-a-time side rates, SMI "
+                         "clock / power sampling, calibration probes, the per-kernel roofline pass, the extras (--no-extras) and the CPU baseline "
+                         "(--no-cpu-baseline).  Off: set up, warm up, time the --steps clips, write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed clips, write what the last one computed - the outputs ug_dc_get_outputs returns, depth and decoded frames - as "
+                         "float32 DIR/<name>.npy (--workload stablenormal: the normals of the last timed image), at most 64 MB in all: an output that does not fit whole is written as DIR/<name>_sample.npy, a fixed "
+                         "seeded sample of its elements (flat indices from numpy default_rng(0), ascending)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.workload == "stablenormal":
         return bench_stablenormal(a)
 
@@ -372,6 +407,17 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {a.gpus}")
+
+    from concurrent.futures import ThreadPoolExecutor
+    from unigeo_amd import weights as Wt
+    cfgs = Wt.tiny_cfgs() if a.tiny else (Wt.UNetCfg(), Wt.VAECfg(), Wt.CLIPCfg())
+    # the seeded random weights of from_random(seed=42), generated once on the host and uploaded into every context (a full replica each, as on separate GPUs).
+    # The three models draw from independent generators: they are synthesised side by side (numpy fills and converts arrays outside the GIL) while torch
+    # imports - the same arrays as one after the other, in about the time of the UNet's alone
+    pool = ThreadPoolExecutor(3)
+    pending = [pool.submit(Wt.random_state, manifest(cfg), seed)
+               for manifest, cfg, seed in zip((Wt.unet_manifest, Wt.vae_manifest, Wt.clip_manifest), cfgs, (42, 43, 44))]
+    pool.shutdown(wait=False)
 
     import torch
     from unigeo_amd.shard import pin_rank_to_cores
@@ -391,12 +437,10 @@ def main():
 
     T, H, W = a.frames, a.height, a.width
     nctx = max(1, min(a.in_flight, a.steps)) if not a.fp8 else 1                      # contexts inside the timed region
-    n_side = a.side_in_flight if (world == 1 and not a.force_dist and not a.no_extras and not a.fp8 and a.side_in_flight > 1 and nctx == 1) else 0
+    n_side = a.side_in_flight if (a.full and world == 1 and not a.force_dist and not a.no_extras and not a.fp8 and a.side_in_flight > 1 and nctx == 1) else 0
     nall = max(nctx, n_side)           # every context exists (and has run) BEFORE the timed region: streams created behind a busy context share its hardware queues
-    from unigeo_amd import weights as Wt
-    cfgs = Wt.tiny_cfgs() if a.tiny else (Wt.UNetCfg(), Wt.VAECfg(), Wt.CLIPCfg())
-    # the seeded random weights of from_random(seed=42), generated once on the host and uploaded into every context (a full replica each, as on separate GPUs)
-    states = (Wt.random_state(Wt.unet_manifest(cfgs[0]), 42), Wt.random_state(Wt.vae_manifest(cfgs[1]), 43), Wt.random_state(Wt.clip_manifest(cfgs[2]), 44))
+    states = tuple(f.result() for f in pending)
+    del pending
     pipes = []
     for j in range(nall):
         ws = (3 << 30) if a.tiny else ((40 << 30) if j == 0 else (12 << 30))
@@ -450,7 +494,7 @@ def main():
     if multi:
         dist.barrier()
     torch.cuda.synchronize() if torch.cuda.is_available() else None
-    smi = SmiSampler(local) if rank == 0 else None
+    smi = SmiSampler(local) if rank == 0 and a.full else None
     if smi:
         smi.__enter__()
     t0 = time.perf_counter()
@@ -470,8 +514,11 @@ def main():
         allr = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [[round(float(v), 2) for v in r.tolist()] for r in allr]
+    if a.dump_outputs and rank == 0:                       # before anything else runs a clip: the last timed clip ran on context (steps - 1) % nctx
+        fo, do, _ = engs[(a.steps - 1) % nctx].get_outputs(frames=True, depth=True)
+        dump_outputs(a.dump_outputs, [("depth", do), ("frames", fo)])
     value_one = None
-    if nctx > 1 and rank == 0 and not multi:               # the same binary, one clip at a time (3 clips on context 0), right after the timed region
+    if a.full and nctx > 1 and rank == 0 and not multi:    # the same binary, one clip at a time (3 clips on context 0), right after the timed region
         eng.set_coscheduled(False)
         eng.run(a.denoise_steps, 8, with_normals=False)
         t1 = time.perf_counter()
@@ -524,10 +571,11 @@ def main():
         res["per_rank_ms"] = {"columns": ["clip_mean", "clip_max", "gather_mean", "gather_max"],
                               "ranks": per_rank if per_rank is not None else [[round(float(np.mean(t_clip_timed)), 2), round(float(np.max(t_clip_timed)), 2), 0.0, 0.0]],
                               "host_affinity": affinity}
-        res["calibration"] = {**calibration_probe(eng, local), **smi.summary(),
-                              "note": "probes run in this process right after the timed clips; sclk / power sampled at 20 Hz during them (None = SMI not readable in this container)"}
-        full = (T, H, W, a.denoise_steps) == (25, 384, 512, 25)
-        if not a.no_profile:
+        if a.full:
+            res["calibration"] = {**calibration_probe(eng, local), **smi.summary(),
+                                  "note": "probes run in this process right after the timed clips; sclk / power sampled at 20 Hz during them (None = SMI not readable in this container)"}
+        full_size = (T, H, W, a.denoise_steps) == (25, 384, 512, 25)
+        if a.full and not a.no_profile:
             # separate, un-timed pass with HIP events around every kernel family on the engine's stream
             eng.profile_begin()
             eng.run(a.denoise_steps, 8, with_normals=False)
@@ -568,12 +616,12 @@ def main():
             # one extra clip with a HIP-event pair around EVERY op (~10 us of stream idle per op, chunks run one after the other): its sum is
             # larger than ms_per_step by construction - a per-family breakdown, not a second measurement of the clip
             res["kernel_ms_event_bracketed"] = {k: round(v["ms"], 2) for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])}
-            if full:
+            if full_size:
                 clip_tflop = a.denoise_steps * TFLOP_UNET + TFLOP_VAE_ENC + TFLOP_VAE_DEC + TFLOP_CLIP
                 res["pipeline_tflops"] = round(clip_tflop / (ms * 1e-3), 1)
         res["runtime_switches"] = {k: v[1] for k, v in unigeo_amd.runtime_switches().items()}     # HIP runtime configuration this process ran with (unigeo_amd/__init__.py)
         res["workspace_peak_gb"] = round(eng.workspace_peak() / 2 ** 30, 2)      # the headline workload's arena high-water mark (before the side runs below)
-        if not a.no_extras:
+        if a.full and not a.no_extras:
             # The reference's own boundary is host to host (model/depthcrafter.py:80-90 takes numpy frames and returns numpy): upload of frames + noise,
             # ug_dc_run, download of frames + depth - measured, not asserted.  `value` stays the HBM-resident rate.
             try:
@@ -609,7 +657,7 @@ def main():
                 eng.set_inputs(frames, nl, na, K)
             except Exception as e:
                 res["plugin_forward_note"] = f"plugin forward side rate failed: {e!r}"
-        if full and not a.no_profile and not a.no_extras:
+        if a.full and full_size and not a.no_profile and not a.no_extras:
             # also report the rate with prepare_output's normals inside the call, the reference-as-shipped N = 5 rate
             # (model/depthcrafter.py:86) and the cost of the reference-faithful float32 VAE encoder vs the fp16-storage one
             def rate(n, steps, **kw):
@@ -692,7 +740,7 @@ def main():
                         pred.engine.close()
                 except Exception:
                     pass
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             try:
                 ncpu = min(os.cpu_count() or 1, 32)
                 mode = a.cpu_baseline if a.cpu_baseline != "auto" else ("config0" if ncpu >= 16 else "sample")

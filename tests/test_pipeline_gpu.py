@@ -346,12 +346,16 @@ def test_multi_gpu_entry_points_run_under_a_single_rank_rccl_group(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     env["MASTER_PORT"] = "29561"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--tiny", "--steps", "2", "--warmup", "1",
-                        "--frames", "5", "--height", "64", "--width", "128", "--denoise-steps", "2", "--no-cpu-baseline", "--in-flight", "2"],
+                        "--frames", "5", "--height", "64", "--width", "128", "--denoise-steps", "2", "--no-cpu-baseline", "--in-flight", "2",
+                        "--full", "--dump-outputs", str(tmp_path / "out")],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])          # the JSON line must be the LAST line of stdout (driver contract)
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["scaling"] == "weak" and "all_gather" in line["config"]["parallelism"]
     assert line["config"]["clips_in_flight_per_gpu"] == 2      # min(--in-flight, --steps) engine contexts per rank (the throughput mode; the default is 1), the gathers issued in clip order from the main thread
+    assert "calibration" in line and "roofline" in line        # --full: the probes and the per-kernel pass ran after the timed clips
+    depth, frames = np.load(tmp_path / "out" / "depth.npy"), np.load(tmp_path / "out" / "frames.npy")   # the last timed clip ran on context 1
+    assert depth.shape == (5, 64, 128) and frames.shape == (5, 64, 128, 3) and np.isfinite(depth).all() and np.isfinite(frames).all()
     cfg = tmp_path / "cfg.yaml"
     cfg.write_text(textwrap.dedent("""
         dataset: "SyntheticGeometryDataset"
@@ -371,3 +375,25 @@ def test_multi_gpu_entry_points_run_under_a_single_rank_rccl_group(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     csv = (tmp_path / "debug_output" / "metrics.csv").read_text().strip().splitlines()
     assert csv[-1].startswith("Average") and len(csv) >= 3
+
+
+def test_plain_bench_run_is_the_headline_alone_and_its_outputs_repeat(tmp_path):
+    """bench.py without --full: set-up, warm-up, the --steps timed clips, --dump-outputs, the line - no side measurement.  Two runs with the
+    same arguments see the same inputs, so their dumped outputs are bit-identical (deterministic kernels)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--tiny", "--steps", "3", "--warmup", "1",
+                            "--frames", "5", "--height", "64", "--width", "128", "--denoise-steps", "2", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["config"]["clips_per_gpu_timed"] == 3
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "fp16"
+    assert line["value"] == pytest.approx(5 * 1000.0 / line["ms_per_step"], rel=5e-3)       # value = frames per timed clip / ms_per_step (both rounded)
+    assert not {"calibration", "roofline", "cpu_baseline", "value_clips_in_flight", "value_host_to_host"} & set(line)
+    for name in ("depth.npy", "frames.npy"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.array_equal(a, b), name

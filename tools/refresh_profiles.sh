@@ -1,8 +1,9 @@
 #!/bin/bash
-# usage (through gpurun): bash tools/refresh_profiles.sh  -> gpurun_out/r06_*; copy what is to be judged into profiles/
+# usage, from the repository root on an MI355X: bash tools/refresh_profiles.sh  -> out/r06_bench_line_final.json (the --full bench line) and the r06_* summaries
+# of the profiler scripts below, in their own output folder; copy what is to be judged into profiles/
 # round-6 measurement refresh: default bench line, rocprofv3 kernel stats of the same workload (one clip per run call = the headline), PMC traffic / MFMA
 # utilisation, per-shape table
-python bench.py > gpurun_out/r06_bench_line_final.json 2> gpurun_out/r06_bench_final.err; tail -c 600 gpurun_out/r06_bench_line_final.json
+mkdir -p out && python bench.py --full > out/r06_bench_line_final.json 2> out/r06_bench_final.err; tail -c 600 out/r06_bench_line_final.json
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/prof_r06
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r06 -o bench -- python bench.py --steps 10 --warmup 1 --no-extras --no-cpu-baseline > gpurun_out/r06_bench_line_under_rocprof.json 2> gpurun_out/r06_bench_under_rocprof.err

@@ -261,9 +261,11 @@ def random_state(manifest, seed: int, dtype=np.float16) -> Dict[str, np.ndarray]
             fan_in = int(np.prod(shape[1:]))
             n = int(np.prod(shape))
             if n > (1 << 22):   # big tensors: tile a 4M-sample block (keeps full-size weight synthesis to seconds)
-                a = np.resize(rng.standard_normal(1 << 22, dtype=np.float32), n).reshape(shape)
-            else:
-                a = rng.standard_normal(shape, dtype=np.float32)
+                # scale and cast the block before tiling it: both are elementwise, so the tiles are the same bits, at 1/n of the conversion work
+                block = (rng.standard_normal(1 << 22, dtype=np.float32) * np.float32(1.0 / np.sqrt(fan_in))).astype(dtype)
+                out[name] = np.resize(block, n).reshape(shape)
+                continue
+            a = rng.standard_normal(shape, dtype=np.float32)
             a = a * np.float32(1.0 / np.sqrt(fan_in))
         out[name] = np.ascontiguousarray(a.astype(dtype))
     return out
