@@ -92,6 +92,12 @@ int ug_dc_run(ug_ctx* ctx, int steps, int decode_chunk, int with_normals);
  * frames of the noise passed to ug_dc_set_inputs are the window noise (rotated by `overlap` frames per window, as upstream). */
 int ug_dc_run_windows(ug_ctx* ctx, int steps, int decode_chunk, int with_normals, int window, int overlap);
 int ug_dc_get_outputs(ug_ctx* ctx, float* frames_out, float* depth_out, float* normals_out);
+/* Classifier-free guidance: `guidance_scale` of the pipeline call (model/depthcrafter.py:80-90, where the reference passes 1.0).  Per-context
+ * state for ug_dc_run and ug_dc_run_windows, default 1.0.  <= 1: no guidance (the reference path).  > 1: every Euler step evaluates the UNet on
+ * the conditional input and on an unconditional one (zero image embeddings, zero conditioning latents) and steps on v_u + g (v_c - v_u),
+ * restated from upstream DepthCrafter's published pipeline (UNPINNED); both evaluations run as one UNet pass over the two stacked videos.
+ * A value that is not finite is rejected. */
+int ug_dc_set_guidance(ug_ctx* ctx, float guidance_scale);
 /* Arithmetic of the VAE *encoder*.  The reference pipeline up-casts the VAE to float32 around encode (diffusers force_upcast;
  * pipeline built at model/depthcrafter.py:24-29) and runs everything else in fp16.  on = 1 (default): float32-grade encoder -
  * fp32 residual stream / GroupNorm / softmax, GEMMs on fp16 hi/lo activation pairs against the (fp16-valued) weights, which is

@@ -42,6 +42,11 @@ int ug_vae_encode(ug_ctx* ctx, const float* video_m11_thwc, int T, int H, int W,
 int ug_vae_decode(ug_ctx* ctx, const float* z_tchw, int T, int h, int w, float* frames_out /*[T,8h,8w,3] in [0,1]*/);
 int ug_unet_forward(ug_ctx* ctx, const float* sample_tchw /*[T,Cin,h,w]*/, int T, int h, int w, float timestep,
                     const float* clip_emb /*[T,cross]*/, float* out_tchw /*[T,Cout,h,w]*/);
+/* ONE batched UNet pass over two arbitrary videos stacked [2][T] (what ug_dc_run runs per step under classifier-free guidance, without the
+ * combine): samples [T,Cin,h,w], embeddings [T,cross], outputs [T,Cout,h,w].  The guided pass is b = the same latents with zero conditioning
+ * channels and emb_b = 0.  Frame-mixing operators stay inside each video (tests/test_cfg_gpu.py). */
+int ug_unet_forward_pair(ug_ctx* ctx, const float* sample_a, const float* emb_a, const float* sample_b, const float* emb_b, int T, int h, int w,
+                         float timestep, float* out_a, float* out_b);
 /* Op-level entry points for kernel parity tests (row-major host matrices, fp32 in/out, computed in fp16). */
 int ug_op_linear(ug_ctx* ctx, const float* A, int M, int K, const float* W, int N, const float* bias,
                  const float* R1, float c0, float c1, int act, int geglu, float* out);

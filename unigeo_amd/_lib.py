@@ -18,7 +18,7 @@ EXPORTS = [
     "ug_unet_config_default", "ug_vae_config_default", "ug_clip_config_default",
     "ug_create", "ug_destroy", "ug_last_error", "ug_workspace_peak",
     "ug_load_tensor", "ug_bind_unet", "ug_bind_vae", "ug_bind_clip",
-    "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
+    "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
     "ug_eval_depth", "ug_eval_normal", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
@@ -103,6 +103,12 @@ def load_library():
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_unet_forward.argtypes = [vp, vp, ip, ip, ip, C.c_float, vp, vp]
+    try:
+        lib.ug_dc_set_guidance.argtypes = [vp, C.c_float]
+        lib.ug_unet_forward_pair.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp, vp]
+    except AttributeError:
+        if not os.environ.get("UG_LIB_PATH"):      # an explicitly selected OLDER build (tools/ab A/B runs) may lack these
+            raise
     lib.ug_normals_from_depth.argtypes = [vp, vp, vp, ip, ip, ip, vp]
     lib.ug_op_linear.argtypes = [vp, vp, ip, ip, vp, ip, vp, vp, C.c_float, C.c_float, ip, ip, vp]
     lib.ug_op_conv.argtypes = [vp, vp, ip, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp]
@@ -295,6 +301,11 @@ class Engine:
         else:
             self._ck(self.lib.ug_dc_run(self.ctx, int(steps), int(decode_chunk), int(bool(with_normals))))
 
+    def set_guidance(self, guidance_scale=1.0):
+        """Classifier-free guidance scale of the following runs (``guidance_scale`` of the pipeline call): <= 1 is the unguided path; a
+        value that is not finite raises."""
+        self._ck(self.lib.ug_dc_set_guidance(self.ctx, float(guidance_scale)))
+
     def set_coscheduled(self, on=True):
         """This context shares the GPU with another clip in flight (a second context): drop the heuristics that fill the last round of one kernel at the
         price of extra launches / work (fused feed-forward tail split, last-round fill factor of the tile planner)."""
@@ -410,6 +421,18 @@ class Engine:
         out = np.empty((T, self.unet_cfg.out_channels, h, w), np.float32)
         self._ck(self.lib.ug_unet_forward(self.ctx, _ptr(s), T, h, w, float(timestep), _ptr(e), _ptr(out)))
         return out
+
+    def unet_forward_pair(self, sample_a, emb_a, sample_b, emb_b, timestep):
+        """ONE batched UNet pass over two videos (samples [T,Cin,h,w], embeddings [T,cross]) -> (out_a, out_b), each [T,Cout,h,w]."""
+        a, b = _f32(sample_a), _f32(sample_b)
+        ea, eb = _f32(emb_a), _f32(emb_b)
+        T, _, h, w = a.shape
+        if b.shape != a.shape or ea.shape != eb.shape or ea.shape[0] != T:
+            raise ValueError("unet_forward_pair: both videos need the same shapes")
+        oa = np.empty((T, self.unet_cfg.out_channels, h, w), np.float32)
+        ob = np.empty_like(oa)
+        self._ck(self.lib.ug_unet_forward_pair(self.ctx, _ptr(a), _ptr(ea), _ptr(b), _ptr(eb), T, h, w, float(timestep), _ptr(oa), _ptr(ob)))
+        return oa, ob
 
     def normals_from_depth(self, depth, intrinsics):
         d = _f32(depth); T, H, W = d.shape

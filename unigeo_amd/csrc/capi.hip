@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/unigeo_hip.h"
@@ -152,6 +153,12 @@ int ug_set_vae_encode_fp32(ug_ctx* x, int on) {
   x->c.vae_encode_fp32 = on ? 1 : 0; x->c.lane_need.clear();
   return 0;
 }
+int ug_dc_set_guidance(ug_ctx* x, float guidance_scale) {
+  UG_TRY(x, {
+    UG_REQUIRE(std::isfinite(guidance_scale), "guidance_scale must be finite");
+    x->c.guidance = guidance_scale;
+  });
+}
 int ug_dc_set_trace(ug_ctx* x, float* host_latents, int steps) {
   if (!x) return -1;
   x->c.trace_host = host_latents; x->c.trace_steps = host_latents ? steps : 0;
@@ -185,11 +192,14 @@ struct Scope {
   explicit Scope(Ctx& c_) : c(c_), mk(c_.ws.mark()) {}
   ~Scope() { (void)hipStreamSynchronize(c.stream); c.ws.release(mk); }
 };
-f16* up16(Ctx& c, const float* h, long n) {
+void upload16(const float* h, long n, f16* d) {   // float host -> f16 device, into d
   std::vector<f16> v((size_t)n);
   for (long i = 0; i < n; ++i) v[i] = (f16)h[i];
-  f16* d = c.ws.get<f16>(n);
   UG_CHECK(hipMemcpy(d, v.data(), (size_t)n * 2, hipMemcpyHostToDevice));
+}
+f16* up16(Ctx& c, const float* h, long n) {
+  f16* d = c.ws.get<f16>(n);
+  upload16(h, n, d);
   return d;
 }
 f16* up16_opt(Ctx& c, const float* h, long n) { return h ? up16(c, h, n) : nullptr; }
@@ -199,14 +209,17 @@ void down16(Ctx& c, const f16* d, float* h, long n) {
   UG_CHECK(hipMemcpy(v.data(), d, (size_t)n * 2, hipMemcpyDeviceToHost));
   for (long i = 0; i < n; ++i) h[i] = (float)v[i];
 }
-// NCHW float host -> NHWC(+channel pad) f16 device
-f16* up_nchw(Ctx& c, const float* h, int T, int C, int H, int W, int Cpad) {
+// NCHW float host -> NHWC(+channel pad) f16 device, into d (T*H*W*Cpad elements)
+void upload_nchw(const float* h, int T, int C, int H, int W, int Cpad, f16* d) {
   std::vector<f16> v((size_t)T * H * W * Cpad, (f16)0.f);
   for (int t = 0; t < T; ++t)
     for (int ch = 0; ch < C; ++ch)
       for (long p = 0; p < (long)H * W; ++p) v[((size_t)t * H * W + p) * Cpad + ch] = (f16)h[((size_t)t * C + ch) * H * W + p];
-  f16* d = c.ws.get<f16>((long)v.size());
   UG_CHECK(hipMemcpy(d, v.data(), v.size() * 2, hipMemcpyHostToDevice));
+}
+f16* up_nchw(Ctx& c, const float* h, int T, int C, int H, int W, int Cpad) {
+  f16* d = c.ws.get<f16>((long)T * H * W * Cpad);
+  upload_nchw(h, T, C, H, W, Cpad, d);
   return d;
 }
 void down_nchw(Ctx& c, const f16* d, float* h, int T, int C, int H, int W) {
@@ -274,6 +287,30 @@ int ug_unet_forward(ug_ctx* x, const float* sample, int T, int h, int w, float t
     unet_prepare(c, T, de, &timestep, 1);
     f16* y = unet_forward(c, dx, T, h, w, 0);
     down_nchw(c, y, out, T, g.out_ch, h, w);
+  });
+}
+
+// one batched UNet pass over two videos stacked [2][T] (the classifier-free-guidance pass of ug_dc_run, without the combine)
+int ug_unet_forward_pair(ug_ctx* x, const float* sample_a, const float* emb_a, const float* sample_b, const float* emb_b, int T, int h, int w,
+                         float timestep, float* out_a, float* out_b) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const UNetCfg& g = c.unet.cfg;
+    UG_REQUIRE(sample_a && emb_a && sample_b && emb_b && out_a && out_b && T >= 1, "ug_unet_forward_pair: null buffer / no frames");
+    const long ns = (long)T * h * w * g.in_ch, ne = (long)T * g.cross_dim;
+    f16* dx = c.ws.get<f16>(2 * ns);
+    f16* de = c.ws.get<f16>(2 * ne);
+    const float* smp[2] = {sample_a, sample_b};
+    const float* emb[2] = {emb_a, emb_b};
+    for (int v = 0; v < 2; ++v) {     // straight into the stacked [2][T] buffers
+      upload_nchw(smp[v], T, g.in_ch, h, w, g.in_ch, dx + v * ns);
+      upload16(emb[v], ne, de + v * ne);
+    }
+    unet_prepare(c, T, de, &timestep, 1, 2);
+    f16* y = unet_forward(c, dx, T, h, w, 0, 2);
+    const long no = (long)T * h * w * g.out_ch;
+    down_nchw(c, y, out_a, T, g.out_ch, h, w);
+    down_nchw(c, y + no, out_b, T, g.out_ch, h, w);
   });
 }
 

@@ -176,6 +176,7 @@ struct TemporalAttnP {
   const f16* Q; const f16* K; const f16* V; long ld;
   f16* O; long ldo;
   int T, HW, H; float scale;
+  int nv = 1;         // videos stacked [nv][T][HW] (the batched guided UNet pass): grid dimension z, the sequence never crosses a video
 };
 void launch_temporal_attn64(const TemporalAttnP& p, hipStream_t s);
 
@@ -221,6 +222,10 @@ void launch_clip_assemble(const f16* patches, const f16* cls, const f16* pos, f1
 void launch_make_unet_input(const f16* lat, const f16* cond, f16* x, long pixels, float inv_scale,
                             hipStream_t s);   // x[p, 0:4] = lat/sqrt(s^2+1), x[p,4:8] = cond
 void launch_euler_step(const f16* v, f16* lat, long n, float sigma, float sigma_next, hipStream_t s);
+// classifier-free guidance: the stacked [2][pixels][8] UNet input of the batched pass (video 0 = lat/den | cond, video 1 = lat/den | 0), and the
+// guided Euler step v = v_u + g (v_c - v_u) (fp32, rounded to fp16 like the reference's fp16 noise_pred) followed by k_euler_step's arithmetic
+void launch_make_unet_input_cfg(const f16* lat, const f16* cond, f16* x, long pixels, float inv_scale, hipStream_t s);
+void launch_euler_step_cfg(const f16* vc, const f16* vu, float g, f16* lat, long n, float sigma, float sigma_next, hipStream_t s);
 void launch_scale_f16(const f16* in, f16* out, float sc, long n, hipStream_t s);
 void launch_axpby_f16(const f16* x, float a, const f16* y, float b, f16* out, long n, hipStream_t s);
 void launch_crossfade_f16(const f16* cur, f16* all, long frame_elems, int overlap, hipStream_t s);

@@ -54,6 +54,7 @@ struct Transformer {
   Lin tpe1, tpe2;
   float alpha = 0.5f;
   // per-clip caches (device, persistent)
+  // (unet_prepare with nv = 2 videos, the batched guided pass: [nv][T][C] / [nv][C]; frame_emb is the same for both videos and repeated)
   f16* frame_emb = nullptr; int frame_emb_T = 0;   // [T][C]
   f16* cross_sp = nullptr;                          // [T][C]
   f16* cross_tm = nullptr;                          // [1][C]
@@ -78,6 +79,7 @@ struct UNet {
   std::vector<Res2D*> temb_s; std::vector<ResT*> temb_t;   // res-blocks with time_emb_proj, in order
   // per-run caches
   f16* tproj = nullptr; long tproj_stride = 0; int tproj_steps = 0; std::vector<long> tproj_off_s, tproj_off_t;
+  int prep_nv = 1;   // videos the per-transformer caches were prepared for (unet_prepare)
 };
 
 struct VAttn { Norm gn; Lin qkv, out; int C = 0; };
@@ -161,6 +163,7 @@ struct Ctx {
                              // bit 1: its LayerNorm (+ broadcast row added to the residual stream) applied inside that kernel (A/B runs)
   int fp8_linears = 0;       // 1 = run the UNet's eligible linear layers on MX-fp8 MFMAs (BASELINE configs[4]; reduced precision, off by default)
   int vae_encode_fp32 = 1;   // 1 = reference behaviour (float32-grade encoder), 0 = fp16 storage like the decoder
+  float guidance = 1.f;      // classifier-free guidance scale of dc_run (ug_dc_set_guidance); <= 1 = no guidance, the unguided path
   // lanes (run_lanes): streams are created on first use; lane_need remembers the arena bytes a task kind needed when it first ran serially
   std::vector<Lane> lanes; hipEvent_t fork_ev = nullptr;
   int concurrency = 1;       // independent sub-graphs in flight (1 = everything on the one stream, in order; ug_set_concurrency); outputs are
@@ -185,8 +188,11 @@ void finish_binding(Ctx& c, const std::string& prefix);   // fail on unused tens
 
 // ---- graphs (device pointers, stream-ordered, transient memory from c.ws) ----
 // x [T,h,w,in_ch] f16; clip_emb [T,cross_dim] f16; tsteps host array of continuous timesteps
-void unet_prepare(Ctx& c, int T, const f16* clip_emb, const float* timesteps, int nsteps);
-f16* unet_forward(Ctx& c, const f16* x, int T, int h, int w, int step);   // -> [T,h,w,out_ch] (ws)
+// nv = 2 (the batched classifier-free-guidance pass): clip_emb is [2][T][cross_dim], x [2][T][h][w][in_ch], the output [2][T][h][w][out_ch];
+// row-wise work runs once over all 2T frames, the operators that mix frames stay inside each video.  vid0: first video of the prepared
+// caches this pass uses (an nv = 1 pass over video 1 of an nv = 2 preparation: the sequential measurement variant of dc_run).
+void unet_prepare(Ctx& c, int T, const f16* clip_emb, const float* timesteps, int nsteps, int nv = 1);
+f16* unet_forward(Ctx& c, const f16* x, int T, int h, int w, int step, int nv = 1, int vid0 = 0);   // -> [nv*T,h,w,out_ch] (ws)
 f16* vae_encode(Ctx& c, const f16* x8, int T, int H, int W);              // x8 [T,H,W,8] -> [T,H/8,W/8,4]; precision per c.vae_encode_fp32
 void vae_decode(Ctx& c, const f16* z, int T, int h, int w, float* frames_out);  // z [T,h,w,4] (already /scaling) -> f32 [T,8h,8w,3]
 f16* clip_embed(Ctx& c, const f16* video_m11, int T, int H, int W);       // [T,H,W,3] -> [T,proj]

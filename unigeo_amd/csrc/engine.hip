@@ -349,7 +349,8 @@ static void groupnorm(Ctx& c, const f16* x0, int C0, const f16* x1, int C1, int 
     if (c.prof_on && c.prof_shapes) snprintf(nm, sizeof(nm), "groupnorm:T%dxHW%dxC%d%s", T, HW, n.c, temporal ? "t" : "");
     else snprintf(nm, sizeof(nm), "groupnorm");
     ProfScope ps(c, nm, 0, (double)T * HW * n.c * 2.0 * 3.0);
-    launch_groupnorm(p, c.stream);
+    const bool from_part = launch_groupnorm(p, c.stream);
+    if (from_part && ps.idx >= 0 && c.prof_shapes) c.prof[ps.idx].name += ":ep";   // shape-keyed profiles: the statistics came from the producer's epilogue
   }
   c.ws.release(mk);   // stream-ordered: later kernels that reuse this memory run after the GN kernels
 }
@@ -896,24 +897,50 @@ static void res2d_forward(Ctx& c, const Res2D& r, const f16* x0, int C0, const f
 }
 
 // in_stats: epilogue statistics of x0 (single source) from whatever produced it; out_stats: filled with those of the block's output (the caller hands
-// them to the next block's / the transformer's first GroupNorm) - allocated next to `out`, same lifetime
+// them to the next block's / the transformer's first GroupNorm) - allocated next to `out`, same lifetime.
+// nv videos stacked [nv][T] (the batched guided pass): the spatial res-block runs once over all nv*T frames; the temporal res-block's convolutions
+// (taps at frames t-1 / t+1) and its pooled GroupNorms run once per video, on the video's rows and the video's slice of the epilogue statistics
+// (blocks of rb rows never straddle a frame, so video v's partial sums start at block v*T*HW/rb).
 static f16* stres_forward(Ctx& c, const STRes& rb, const f16* x0, int C0, const f16* x1, int C1, int T, int h, int w,
-                          int G, const f16* tproj_s, const f16* tproj_t, StatPart* out_stats = nullptr, const StatPart* in_stats = nullptr) {
-  const long M = (long)T * h * w;
+                          int G, const f16* tproj_s, const f16* tproj_t, StatPart* out_stats = nullptr, const StatPart* in_stats = nullptr,
+                          int nv = 1) {
+  const long Mv = (long)T * h * w, M = nv * Mv;
   const int cout = rb.cout;
   f16* out = c.ws.get<f16>(M * cout);
-  if (out_stats) *out_stats = stat_alloc(c, M, cout, T, h * w, G, 0);
+  if (out_stats) *out_stats = stat_alloc(c, M, cout, nv * T, h * w, G, 0);
   const size_t mk = c.ws.mark();
   f16* xs = c.ws.get<f16>(M * cout);
   StatPart sx = stat_alloc(c, M, cout, T, h * w, G, 1), sh = stat_alloc(c, M, cout, T, h * w, G, 1);
-  res2d_forward(c, rb.s, x0, C0, x1, C1, T, h, w, G, tproj_s, xs, &sx, in_stats);
+  res2d_forward(c, rb.s, x0, C0, x1, C1, nv * T, h, w, G, tproj_s, xs, &sx, in_stats);
+  // video v's view of statistics written over all nv videos (consumers: the per-video temporal GroupNorms)
+  auto view = [&](const StatPart& sp, int v) {
+    StatPart r = sp;
+    if (v > 0) { if (sp.part && sp.rb > 0 && Mv % sp.rb == 0) r.part = sp.part + v * (Mv / sp.rb) * cout; else r.rb = 0; }
+    return r;
+  };
+  // temporal convolution, one launch per video; so (optional) collects the epilogue statistics of all videos in one block array
+  auto tconv = [&](const Conv& cv, const f16* in, f16* o, Epi e, StatPart* so) {
+    if (nv == 1) { e.so = so; conv(c, in, cout, nullptr, 0, T, h, w, cv, 1, 0, 0, 1, o, e); return; }
+    const f16* r1 = e.R1;
+    int rb0 = 0;
+    for (int v = 0; v < nv; ++v) {
+      const long off = v * Mv * cout;
+      StatPart sv;
+      if (so && so->part) { sv.part = so->part; if (v > 0 && rb0 > 0 && Mv % rb0 == 0) sv.part += v * (Mv / rb0) * cout; }
+      Epi ev = e; ev.so = (so && so->part) ? &sv : nullptr;
+      if (r1) ev.R1 = r1 + off;
+      conv(c, in + off, cout, nullptr, 0, T, h, w, cv, 1, 0, 0, 1, o + off, ev);
+      if (v == 0) rb0 = sv.rb; else if (sv.rb != rb0) rb0 = 0;
+    }
+    if (so && so->part) so->rb = (rb0 > 0 && Mv % rb0 == 0) ? rb0 : 0;
+  };
   f16* a = c.ws.get<f16>(M * cout);
-  groupnorm(c, xs, cout, nullptr, 0, T, h * w, G, rb.t.n1, 1, 1, a, &sx);
+  for (int v = 0; v < nv; ++v) { const StatPart sv = view(sx, v); groupnorm(c, xs + v * Mv * cout, cout, nullptr, 0, T, h * w, G, rb.t.n1, 1, 1, a + v * Mv * cout, &sv); }
   f16* hb = c.ws.get<f16>(M * cout);
-  { Epi e; e.bias2 = tproj_t; e.so = &sh; conv(c, a, cout, nullptr, 0, T, h, w, rb.t.c1, 1, 0, 0, 1, hb, e); }
-  groupnorm(c, hb, cout, nullptr, 0, T, h * w, G, rb.t.n2, 1, 1, a, &sh);
+  { Epi e; e.bias2 = tproj_t; tconv(rb.t.c1, a, hb, e, &sh); }
+  for (int v = 0; v < nv; ++v) { const StatPart sv = view(sh, v); groupnorm(c, hb + v * Mv * cout, cout, nullptr, 0, T, h * w, G, rb.t.n2, 1, 1, a + v * Mv * cout, &sv); }
   // blend: alpha*xs + (1-alpha)*(xs + conv) = xs + (1-alpha)*conv
-  { Epi e; e.c0 = 1.f - rb.alpha; e.R1 = xs; e.ldr1 = cout; e.c1 = 1.f; e.so = out_stats; conv(c, a, cout, nullptr, 0, T, h, w, rb.t.c2, 1, 0, 0, 1, out, e); }
+  { Epi e; e.c0 = 1.f - rb.alpha; e.R1 = xs; e.ldr1 = cout; e.c1 = 1.f; tconv(rb.t.c2, a, out, e, out_stats); }
   c.ws.release(mk);
   return out;
 }
@@ -1016,13 +1043,17 @@ static void ln_ff(Ctx& c, const f16* x, long M, const Norm& ln, const f16* addve
   ff_pair(c, t1, M, f1, f2, mid, out, e2, q);
 }
 
-static f16* transformer_forward(Ctx& c, const Transformer& tr, const f16* x, int T, int h, int w, int G, const StatPart* in_stats = nullptr) {
+// nv videos stacked [nv][T] (the batched guided pass): everything but the temporal attention is row- or frame-wise and runs over all nv*T
+// frames; the temporal attention runs per video (grid dimension z), the first-frame cross-attention row is video v's for its T*HW rows.
+// vid0: first video of the prepared caches (cross_sp / cross_tm) this pass uses.
+static f16* transformer_forward(Ctx& c, const Transformer& tr, const f16* x, int T, int h, int w, int G, const StatPart* in_stats = nullptr,
+                                int nv = 1, int vid0 = 0) {
   const int C = tr.C, HW = h * w;
-  const long M = (long)T * HW;
+  const long M = (long)nv * T * HW;
   f16* out = c.ws.get<f16>(M * C);
   const size_t mk = c.ws.mark();
   f16* t1 = c.ws.get<f16>(M * C);
-  groupnorm(c, x, C, nullptr, 0, T, HW, G, tr.gn, 0, 0, t1, in_stats);
+  groupnorm(c, x, C, nullptr, 0, nv * T, HW, G, tr.gn, 0, 0, t1, in_stats);
   f16* h0 = c.ws.get<f16>(M * C);
   // fp8 linear path: the LayerNorms feeding a linear layer write MX-fp8 directly (no fp16 copy, no separate quantiser pass)
   const bool q8 = c.fp8_linears && !getenv("UG_NO_LNQ") && C % 128 == 0 && M >= 256 && tr.qkv1.w8 && tr.ff1.w8 && tr.ffin1.w8 && tr.tqkv.w8 && tr.tff1.w8;
@@ -1036,11 +1067,11 @@ static f16* transformer_forward(Ctx& c, const Transformer& tr, const f16* x, int
   f16* ao = c.ws.get<f16>(M * C);
   {
     FlashP p; p.Q = qkv; p.K = qkv + C; p.V = qkv + 2 * C; p.ldq = p.ldk = p.ldv = 3 * C; p.O = ao; p.ldo = C;
-    p.B = T; p.H = tr.heads; p.S = HW; p.scale = 0.125f; p.variant = c.flash_variant;
+    p.B = nv * T; p.H = tr.heads; p.S = HW; p.scale = 0.125f; p.variant = c.flash_variant;
     char nm[96];
-    if (c.prof_on && c.prof_shapes) snprintf(nm, sizeof(nm), "flash_attn:B%dxH%dxS%d", T, tr.heads, HW);
+    if (c.prof_on && c.prof_shapes) snprintf(nm, sizeof(nm), "flash_attn:B%dxH%dxS%d", nv * T, tr.heads, HW);
     else snprintf(nm, sizeof(nm), "flash_attn");
-    ProfScope ps(c, nm, 4.0 * T * tr.heads * (double)HW * HW * 64, 0);
+    ProfScope ps(c, nm, 4.0 * nv * T * tr.heads * (double)HW * HW * 64, 0);
     launch_flash_attn64(p, c.stream);
   }
   f16* h1 = c.ws.get<f16>(M * C);
@@ -1048,7 +1079,7 @@ static f16* transformer_forward(Ctx& c, const Transformer& tr, const f16* x, int
   f16* ffm = c.ws.get<f16>(M * 4 * C);
   f16* hs = c.ws.get<f16>(M * C);
   { Epi e; e.R1 = h0; linear(c, ao, M, tr.o1, h1, e); }
-  { Epi e; e.R1 = h2; ln_ff(c, h1, M, tr.ln3, tr.cross_sp, HW, h2, t1, tr.ff1, tr.ff2, ffm, hs, e, qp); }
+  { Epi e; e.R1 = h2; ln_ff(c, h1, M, tr.ln3, tr.cross_sp + (long)vid0 * T * C, HW, h2, t1, tr.ff1, tr.ff2, ffm, hs, e, qp); }
   // ---- temporal block (token order kept; only the attention gathers over frames)
   f16* xm = h0;   // h0 is dead
   f16* g1 = h1;   // h1 is dead
@@ -1056,8 +1087,8 @@ static f16* transformer_forward(Ctx& c, const Transformer& tr, const f16* x, int
   ln_linear(c, g1, M, tr.tln1, t1, tr.tqkv, qkv, qp);
   {
     TemporalAttnP p; p.Q = qkv; p.K = qkv + C; p.V = qkv + 2 * C; p.ld = 3 * C; p.O = ao; p.ldo = C;
-    p.T = T; p.HW = HW; p.H = tr.heads; p.scale = 0.125f;
-    ProfScope ps(c, "temporal_attn", 4.0 * HW * tr.heads * (double)T * T * 64, (double)M * C * 2.0 * 4.0);
+    p.T = T; p.HW = HW; p.H = tr.heads; p.scale = 0.125f; p.nv = nv;
+    ProfScope ps(c, "temporal_attn", 4.0 * nv * HW * tr.heads * (double)T * T * 64, (double)M * C * 2.0 * 4.0);
     launch_temporal_attn64(p, c.stream);
   }
   f16* g2 = h2;   // h2 is dead
@@ -1066,7 +1097,7 @@ static f16* transformer_forward(Ctx& c, const Transformer& tr, const f16* x, int
   {
     Epi e; e.c0 = 1.f - tr.alpha; e.R1 = g3; e.c1 = 1.f - tr.alpha; e.R2 = hs; e.c2 = tr.alpha;
     { Epi e1; e1.R1 = g1; linear(c, ao, M, tr.to1, g2, e1); }
-    ln_ff(c, g2, M, tr.tln3, tr.cross_tm, M, g3, t1, tr.tff1, tr.tff2, ffm, mix, e, qp);
+    ln_ff(c, g2, M, tr.tln3, tr.cross_tm + (long)vid0 * C, (long)T * HW, g3, t1, tr.tff1, tr.tff2, ffm, mix, e, qp);
   }
   { Epi e; e.R1 = x; linear(c, mix, M, tr.proj_out, out, e); }
   c.ws.release(mk);
@@ -1095,9 +1126,10 @@ static f16* upload_f16(Ctx& c, const std::vector<f16>& v) {
 // latents is computed ONCE here: per-step time-embedding projections of all res-blocks, per-transformer
 // frame-position embeddings and the single-token cross-attention outputs.  The denoise loop then runs with
 // zero host synchronisation.  Allocations come from c.ws and stay live until the caller releases its mark.
-void unet_prepare(Ctx& c, int T, const f16* clip_emb, const float* timesteps, int nsteps) {
+void unet_prepare(Ctx& c, int T, const f16* clip_emb, const float* timesteps, int nsteps, int nv) {
   UNet& u = c.unet;
   UG_REQUIRE(u.bound, "UNet weights are not bound");
+  UG_REQUIRE(nv == 1 || nv == 2, "unet_prepare: 1 or 2 videos");
   const UNetCfg& cfg = u.cfg;
   const int temb = cfg.boc[0] * 4;
   std::vector<f16> hs;
@@ -1131,79 +1163,87 @@ void unet_prepare(Ctx& c, int T, const f16* clip_emb, const float* timesteps, in
     host_sinusoid(fidx.data(), T, tr.C, hs);
     f16* s = upload_f16(c, hs);
     f16* m1 = c.ws.get<f16>((long)T * 4 * tr.C);
-    tr.frame_emb = c.ws.get<f16>((long)T * tr.C); tr.frame_emb_T = T;
+    tr.frame_emb = c.ws.get<f16>((long)nv * T * tr.C); tr.frame_emb_T = T;
     { Epi e; e.act = UG_ACT_SILU; linear(c, s, T, tr.tpe1, m1, e); }
     linear(c, m1, T, tr.tpe2, tr.frame_emb);
-    f16* v = c.ws.get<f16>((long)T * tr.C);
-    tr.cross_sp = c.ws.get<f16>((long)T * tr.C);
-    linear(c, clip_emb, T, tr.v2, v);
-    linear(c, v, T, tr.o2, tr.cross_sp);
-    f16* v1 = c.ws.get<f16>(tr.C);
-    tr.cross_tm = c.ws.get<f16>(tr.C);
-    linear(c, clip_emb, 1, tr.tv2, v1);        // first frame's token
-    linear(c, v1, 1, tr.to2, tr.cross_tm);
+    for (int vv = 1; vv < nv; ++vv)            // the same frame positions for every video
+      UG_CHECK(hipMemcpyAsync(tr.frame_emb + (long)vv * T * tr.C, tr.frame_emb, (size_t)T * tr.C * 2, hipMemcpyDeviceToDevice, c.stream));
+    // the projections of every video's embeddings (the unconditional video of the guided pass: the same projections of a zero embedding)
+    f16* v = c.ws.get<f16>((long)nv * T * tr.C);
+    tr.cross_sp = c.ws.get<f16>((long)nv * T * tr.C);
+    linear(c, clip_emb, (long)nv * T, tr.v2, v);
+    linear(c, v, (long)nv * T, tr.o2, tr.cross_sp);
+    f16* v1 = c.ws.get<f16>((long)nv * tr.C);
+    tr.cross_tm = c.ws.get<f16>((long)nv * tr.C);
+    for (int vv = 0; vv < nv; ++vv) {          // first frame's token of each video
+      linear(c, clip_emb + (long)vv * T * cfg.cross_dim, 1, tr.tv2, v1 + (long)vv * tr.C);
+      linear(c, v1 + (long)vv * tr.C, 1, tr.to2, tr.cross_tm + (long)vv * tr.C);
+    }
   };
   for (auto& d : u.down) for (auto& t : d.attn) prep(t);
   prep(u.mid_attn);
   for (auto& d : u.up) for (auto& t : d.attn) prep(t);
+  u.prep_nv = nv;
 }
 
-f16* unet_forward(Ctx& c, const f16* x, int T, int h, int w, int step) {
+f16* unet_forward(Ctx& c, const f16* x, int T, int h, int w, int step, int nv, int vid0) {
   UNet& u = c.unet;
   const UNetCfg& cfg = u.cfg;
   UG_REQUIRE(u.bound && u.tproj && step < u.tproj_steps, "unet_prepare must run first");
   UG_REQUIRE(h % 8 == 0 && w % 8 == 0, "latent height/width must be multiples of 8 (image multiples of 64)");
+  UG_REQUIRE(nv >= 1 && vid0 >= 0 && vid0 + nv <= u.prep_nv, "unet_forward: videos beyond what unet_prepare prepared");
+  const int Tn = nv * T;   // frames of all videos: the extent of every frame-wise operator
   const int G = cfg.groups, n = cfg.nlev;
   auto tp_s = [&](const STRes& r) { return r.s.has_temb ? u.tproj + u.tproj_off_s[r.s.tidx] + (long)step * r.s.temb.out : nullptr; };
   auto tp_t = [&](const STRes& r) { return r.t.has_temb ? u.tproj + u.tproj_off_t[r.t.tidx] + (long)step * r.t.temb.out : nullptr; };
-  f16* out = c.ws.get<f16>((long)T * h * w * cfg.out_ch);
+  f16* out = c.ws.get<f16>((long)Tn * h * w * cfg.out_ch);
   const size_t mk = c.ws.mark();
   struct Skip { f16* p; int C; };
   std::vector<Skip> skips;
   int ch = cfg.boc[0], ch_h = h, ch_w = w;
-  f16* cur = c.ws.get<f16>((long)T * h * w * ch);
-  conv(c, x, cfg.in_ch, nullptr, 0, T, h, w, u.conv_in, 1, 1, 1, 1, cur);
+  f16* cur = c.ws.get<f16>((long)Tn * h * w * ch);
+  conv(c, x, cfg.in_ch, nullptr, 0, Tn, h, w, u.conv_in, 1, 1, 1, 1, cur);
   StatPart cs;      // epilogue statistics of `cur` (valid while its producer was a convolution that could write them)
   skips.push_back({cur, ch});
   for (int i = 0; i < n; ++i) {
     for (int j = 0; j < cfg.layers; ++j) {
       const STRes& r = u.down[i].res[j];
       StatPart so;
-      cur = stres_forward(c, r, cur, ch, nullptr, 0, T, ch_h, ch_w, G, tp_s(r), tp_t(r), &so, cs.part ? &cs : nullptr);
+      cur = stres_forward(c, r, cur, ch, nullptr, 0, T, ch_h, ch_w, G, tp_s(r), tp_t(r), &so, cs.part ? &cs : nullptr, nv);
       ch = r.cout; cs = so;
-      if (cfg.has_attn[i]) { cur = transformer_forward(c, u.down[i].attn[j], cur, T, ch_h, ch_w, G, &cs); cs = StatPart(); }
+      if (cfg.has_attn[i]) { cur = transformer_forward(c, u.down[i].attn[j], cur, T, ch_h, ch_w, G, &cs, nv, vid0); cs = StatPart(); }
       skips.push_back({cur, ch});
     }
     if (u.down[i].has_down) {
-      f16* d = c.ws.get<f16>((long)T * (ch_h / 2) * (ch_w / 2) * ch);
-      conv(c, cur, ch, nullptr, 0, T, ch_h, ch_w, u.down[i].down, 2, 1, 1, 1, d);
+      f16* d = c.ws.get<f16>((long)Tn * (ch_h / 2) * (ch_w / 2) * ch);
+      conv(c, cur, ch, nullptr, 0, Tn, ch_h, ch_w, u.down[i].down, 2, 1, 1, 1, d);
       ch_h /= 2; ch_w /= 2; cur = d; cs = StatPart();
       skips.push_back({cur, ch});
     }
   }
   { StatPart so;
-    cur = stres_forward(c, u.mid0, cur, ch, nullptr, 0, T, ch_h, ch_w, G, tp_s(u.mid0), tp_t(u.mid0), &so, cs.part ? &cs : nullptr);
-    cur = transformer_forward(c, u.mid_attn, cur, T, ch_h, ch_w, G, &so); }
-  cur = stres_forward(c, u.mid1, cur, ch, nullptr, 0, T, ch_h, ch_w, G, tp_s(u.mid1), tp_t(u.mid1));
+    cur = stres_forward(c, u.mid0, cur, ch, nullptr, 0, T, ch_h, ch_w, G, tp_s(u.mid0), tp_t(u.mid0), &so, cs.part ? &cs : nullptr, nv);
+    cur = transformer_forward(c, u.mid_attn, cur, T, ch_h, ch_w, G, &so, nv, vid0); }
+  cur = stres_forward(c, u.mid1, cur, ch, nullptr, 0, T, ch_h, ch_w, G, tp_s(u.mid1), tp_t(u.mid1), nullptr, nullptr, nv);
   for (int i = 0; i < n; ++i) {
     const int lev = n - 1 - i;
     for (size_t j = 0; j < u.up[i].res.size(); ++j) {
       const STRes& r = u.up[i].res[j];
       const Skip sk = skips.back(); skips.pop_back();
       StatPart so;
-      cur = stres_forward(c, r, cur, ch, sk.p, sk.C, T, ch_h, ch_w, G, tp_s(r), tp_t(r), &so);
+      cur = stres_forward(c, r, cur, ch, sk.p, sk.C, T, ch_h, ch_w, G, tp_s(r), tp_t(r), &so, nullptr, nv);
       ch = r.cout;
-      if (cfg.has_attn[lev]) cur = transformer_forward(c, u.up[i].attn[j], cur, T, ch_h, ch_w, G, &so);
+      if (cfg.has_attn[lev]) cur = transformer_forward(c, u.up[i].attn[j], cur, T, ch_h, ch_w, G, &so, nv, vid0);
     }
     if (u.up[i].has_up) {
-      f16* d = c.ws.get<f16>((long)T * (ch_h * 2) * (ch_w * 2) * ch);
-      conv(c, cur, ch, nullptr, 0, T, ch_h, ch_w, u.up[i].up, 1, 1, 1, 2, d);
+      f16* d = c.ws.get<f16>((long)Tn * (ch_h * 2) * (ch_w * 2) * ch);
+      conv(c, cur, ch, nullptr, 0, Tn, ch_h, ch_w, u.up[i].up, 1, 1, 1, 2, d);
       ch_h *= 2; ch_w *= 2; cur = d;
     }
   }
-  f16* a = c.ws.get<f16>((long)T * h * w * ch);
-  groupnorm(c, cur, ch, nullptr, 0, T, h * w, G, u.norm_out, 0, 1, a);
-  conv(c, a, ch, nullptr, 0, T, h, w, u.conv_out, 1, 1, 1, 1, out);
+  f16* a = c.ws.get<f16>((long)Tn * h * w * ch);
+  groupnorm(c, cur, ch, nullptr, 0, Tn, h * w, G, u.norm_out, 0, 1, a);
+  conv(c, a, ch, nullptr, 0, Tn, h, w, u.conv_out, 1, 1, 1, 1, out);
   c.ws.release(mk);
   return out;
 }
@@ -1565,19 +1605,51 @@ void dc_run(Ctx& c, int steps, int chunk, int with_normals, int window, int over
   karras_sigmas(steps, sig, ts);
   const float sigma0 = sqrtf(sig[0] * sig[0] + 1.f);    // init_noise_sigma, "leading" spacing
   f16* lat = c.ws.get<f16>(lp * 4);      // running result (all frames)
+  // classifier-free guidance (guidance_scale > 1, diffusers' do_classifier_free_guidance): every step evaluates the UNet on the conditional
+  // input and on an unconditional one (zero image embeddings, zero conditioning latents) and steps on v_u + g (v_c - v_u).  Both run as ONE
+  // UNet pass over the two videos stacked [2][T] (unet_forward nv = 2).  UG_CFG_SEQUENTIAL (measurement aid, tools/time_cfg.py): two
+  // unbatched passes instead, same fused input builder and guided step.
+  const bool guided = c.guidance > 1.f;
+  const char* seq_env = getenv("UG_CFG_SEQUENTIAL");          // read per call: the A/B tool flips it between runs of one process
+  const bool cfg_seq = guided && seq_env && atoi(seq_env) != 0;
+  const int nv = guided ? 2 : 1;
+  auto prepare = [&](const f16* e, int Tw) {      // guided: the embeddings of both videos, [e | 0]
+    const f16* ep = e;
+    if (guided) {
+      const long ne = (long)Tw * c.clip.cfg.proj;
+      f16* p2 = c.ws.get<f16>(2 * ne);
+      UG_CHECK(hipMemcpyAsync(p2, e, (size_t)ne * 2, hipMemcpyDeviceToDevice, c.stream));
+      UG_CHECK(hipMemsetAsync(p2 + ne, 0, (size_t)ne * 2, c.stream));
+      ep = p2;
+    }
+    unet_prepare(c, Tw, ep, ts.data(), steps, nv);
+  };
+  auto denoise_step = [&](f16* cur, const f16* cnd, f16* xin, int Tw, int i) {   // cur [Tw,h,w,4] advanced by Euler step i
+    const long pix = (long)Tw * h * w;
+    const float den = sqrtf(sig[i] * sig[i] + 1.f);
+    if (!guided) {
+      launch_make_unet_input(cur, cnd, xin, pix, den, c.stream);
+      f16* v = unet_forward(c, xin, Tw, h, w, i);
+      launch_euler_step(v, cur, pix * 4, sig[i], sig[i + 1], c.stream);
+      return;
+    }
+    launch_make_unet_input_cfg(cur, cnd, xin, pix, den, c.stream);
+    const f16* vc; const f16* vu;
+    if (cfg_seq) { vc = unet_forward(c, xin, Tw, h, w, i, 1, 0); vu = unet_forward(c, xin + pix * 8, Tw, h, w, i, 1, 1); }
+    else { vc = unet_forward(c, xin, Tw, h, w, i, 2); vu = vc + pix * 4; }
+    launch_euler_step_cfg(vc, vu, c.guidance, cur, pix * 4, sig[i], sig[i + 1], c.stream);
+  };
   if (!windows) {
     launch_init_latents2(c.d_noise_lat, lat, sigma0, T, (long)h * w, c.stream);
-    unet_prepare(c, T, emb, ts.data(), steps);
-    f16* xin = c.ws.get<f16>(lp * 8);
+    prepare(emb, T);
+    f16* xin = c.ws.get<f16>(lp * 8 * nv);
     // 5. denoise loop: no host sync inside
     const bool host_timing = getenv("UG_HOST_TIMING") != nullptr;   // measurement aid: is the host ahead of the stream?
     if (host_timing) UG_CHECK(hipStreamSynchronize(c.stream));
     const auto ht0 = std::chrono::steady_clock::now();
     for (int i = 0; i < steps; ++i) {
       const size_t m2 = c.ws.mark();
-      launch_make_unet_input(lat, cond, xin, lp, sqrtf(sig[i] * sig[i] + 1.f), c.stream);
-      f16* v = unet_forward(c, xin, T, h, w, i);
-      launch_euler_step(v, lat, lp * 4, sig[i], sig[i + 1], c.stream);
+      denoise_step(lat, cond, xin, T, i);
       if (c.trace_host && i < c.trace_steps) {   // parity instrumentation only (tests/): latents [T,h,w,4] after step i
         float* tf = c.ws.get<float>(lp * 4);
         launch_cast_f16_f32(lat, tf, lp * 4, c.stream);
@@ -1599,7 +1671,7 @@ void dc_run(Ctx& c, int steps, int chunk, int with_normals, int window, int over
     f16* init = c.ws.get<f16>(fe * window);              // latents_init: unit noise * sigma0 for one window
     f16* rot = c.ws.get<f16>(fe * window);
     f16* cur = c.ws.get<f16>(fe * window);
-    f16* xin = c.ws.get<f16>(fe * window * 2);
+    f16* xin = c.ws.get<f16>(fe * window * 2 * nv);
     launch_init_latents2(c.d_noise_lat, init, sigma0, window, (long)h * w, c.stream);
     int n_all = 0;
     for (int s0 = 0; s0 < T - overlap; s0 += stride) {
@@ -1613,12 +1685,10 @@ void dc_run(Ctx& c, int steps, int chunk, int with_normals, int window, int over
       if (n_all > 0 && overlap)   // first `overlap` frames: previous result + noise at sigma_0 (cur holds noise * sigma0)
         launch_axpby_f16(lat + fe * (n_all - overlap), 1.f, cur, sig[0] / sigma0, cur, fe * overlap, c.stream);
       const size_t mw = c.ws.mark();
-      unet_prepare(c, Tw, emb + (long)s0 * c.clip.cfg.proj, ts.data(), steps);
+      prepare(emb + (long)s0 * c.clip.cfg.proj, Tw);
       for (int i = 0; i < steps; ++i) {
         const size_t m2 = c.ws.mark();
-        launch_make_unet_input(cur, cond + fe * s0, xin, (long)Tw * h * w, sqrtf(sig[i] * sig[i] + 1.f), c.stream);
-        f16* v = unet_forward(c, xin, Tw, h, w, i);
-        launch_euler_step(v, cur, lw, sig[i], sig[i + 1], c.stream);
+        denoise_step(cur, cond + fe * s0, xin, Tw, i);
         c.ws.release(m2);
       }
       c.ws.release(mw);

@@ -783,6 +783,9 @@ __global__ __launch_bounds__(256) void temporal_attn64_kernel(const TemporalAttn
   const long pix = (long)blockIdx.x * 4 + wave;
   const int h = blockIdx.y;
   if (pix >= p.HW) return;   // wave-uniform; no block-level barrier is used below
+  const long vrow = (long)blockIdx.z * p.T * p.HW;   // first row of this video (nv > 1: stacked videos)
+  const f16* Qv = p.Q + vrow * p.ld; const f16* Kv = p.K + vrow * p.ld; const f16* Vv = p.V + vrow * p.ld;
+  f16* Ov = p.O + vrow * p.ldo;
   const int qi = lane & 31, hh = lane >> 5;
   const float sc = p.scale * 1.4426950408889634f;
   f16* vt = lds + wave * (NB * 32 * 64);
@@ -792,7 +795,7 @@ __global__ __launch_bounds__(256) void temporal_attn64_kernel(const TemporalAttn
     for (int j = 0; j < 4 * NB; ++j) {   // wave-instructions of 8 rows x 128 B
       const int r = j * 8 + (lane >> 3);
       const int rr = r < p.T ? r : 0;   // padded keys get P == 0
-      const f16* vs = p.V + ((long)rr * p.HW + pix) * p.ld + h * 64 + ((pc ^ vswz(r)) * 8);
+      const f16* vs = Vv + ((long)rr * p.HW + pix) * p.ld + h * 64 + ((pc ^ vswz(r)) * 8);
       __builtin_amdgcn_global_load_lds((gptr_t)vs, (lptr_t)(vt + j * 8 * 64), 16, 0, 0);
     }
   }
@@ -802,7 +805,7 @@ __global__ __launch_bounds__(256) void temporal_attn64_kernel(const TemporalAttn
     const int t = kb * 32 + qi;
     const long row = (long)(t < p.T ? t : 0) * p.HW + pix;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) kf[kb][c] = *(const f16x8*)(p.K + row * p.ld + h * 64 + c * 16 + hh * 8);
+    for (int c = 0; c < 4; ++c) kf[kb][c] = *(const f16x8*)(Kv + row * p.ld + h * 64 + c * 16 + hh * 8);
   }
   bool waited = false;
 #pragma unroll
@@ -813,7 +816,7 @@ __global__ __launch_bounds__(256) void temporal_attn64_kernel(const TemporalAttn
     const long rowq = (long)(ok ? tq : 0) * p.HW + pix;
     f16x8 qf[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) qf[c] = *(const f16x8*)(p.Q + rowq * p.ld + h * 64 + c * 16 + hh * 8);
+    for (int c = 0; c < 4; ++c) qf[c] = *(const f16x8*)(Qv + rowq * p.ld + h * 64 + c * 16 + hh * 8);
     float pr[NB][16];
     float mx = -1e30f;
 #pragma unroll
@@ -853,7 +856,7 @@ __global__ __launch_bounds__(256) void temporal_attn64_kernel(const TemporalAttn
     for (int kb = 0; kb < NB; ++kb) pv_block(vt, kb * 32, lane, pr[kb], o);
     if (ok) {
       const float inv = 1.0f / ps;
-      f16* dst = p.O + rowq * p.ldo + h * 64;
+      f16* dst = Ov + rowq * p.ldo + h * 64;
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
@@ -870,7 +873,8 @@ __global__ __launch_bounds__(256) void temporal_attn64_kernel(const TemporalAttn
 void launch_temporal_attn64(const TemporalAttnP& p, hipStream_t s) {
   UG_REQUIRE(p.T >= 1 && p.T <= 128, "temporal attention supports up to 128 frames per denoising window");
   UG_REQUIRE(p.ld % 8 == 0 && p.ldo % 4 == 0, "temporal attention strides");
-  dim3 grid(cdiv(p.HW, 4), p.H);
+  UG_REQUIRE(p.nv >= 1 && p.nv <= 65535, "temporal attention video count");
+  dim3 grid(cdiv(p.HW, 4), p.H, p.nv);
   if (p.T <= 32) hipLaunchKernelGGL(temporal_attn64_kernel<1>, grid, dim3(256), 0, s, p);
   else if (p.T <= 64) hipLaunchKernelGGL(temporal_attn64_kernel<2>, grid, dim3(256), 0, s, p);
   else if (p.T <= 96) hipLaunchKernelGGL(temporal_attn64_kernel<3>, grid, dim3(256), 0, s, p);

@@ -369,6 +369,43 @@ void launch_euler_step(const f16* v, f16* lat, long n, float sigma, float sigma_
   hipLaunchKernelGGL(k_euler_step, gs_grid(n), dim3(256), 0, s, v, lat, n, sigma, sigma_next);
 }
 
+// Classifier-free guidance, batched pass: x [2][pixels][8] = (lat / den | cond) for the conditional video, (lat / den | 0) for the
+// unconditional one - one launch, the scaled latents computed once per pixel and stored twice.
+__global__ void k_make_unet_input_cfg(const f16* lat, const f16* cond, f16* x, long pixels, float inv_scale_den) {
+  GS_LOOP(p, pixels) {
+    const f16x4 l = *(const f16x4*)(lat + p * 4);
+    const f16x4 c = *(const f16x4*)(cond + p * 4);
+    f16x8 o, u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { o[e] = (f16)((float)l[e] / inv_scale_den); o[4 + e] = c[e]; u[e] = o[e]; u[4 + e] = (f16)0.f; }
+    *(f16x8*)(x + p * 8) = o;
+    *(f16x8*)(x + (pixels + p) * 8) = u;
+  }
+}
+void launch_make_unet_input_cfg(const f16* lat, const f16* cond, f16* x, long pixels, float den, hipStream_t s) {
+  hipLaunchKernelGGL(k_make_unet_input_cfg, gs_grid(pixels), dim3(256), 0, s, lat, cond, x, pixels, den);
+}
+
+// Guided Euler step: v = v_u + g (v_c - v_u) in fp32 registers, rounded to fp16 (the reference's noise_pred is an fp16 tensor), then
+// exactly k_euler_step.  One pass over v_c, v_u and the latents instead of three elementwise launches.
+__global__ void k_euler_step_cfg(const f16* vc, const f16* vu, float g, f16* lat, long n, float sigma, float sigma_next) {
+  const float c = -sigma / sqrtf(sigma * sigma + 1.f);
+  const float d2 = sigma * sigma + 1.f;
+  const float dt = sigma_next - sigma;
+  GS_LOOP(i, n) {
+    const float u = (float)vu[i];
+    const float v = (float)(f16)(u + g * ((float)vc[i] - u));
+    const float x = (float)lat[i];
+    const float vcs = (float)(f16)(v * c);
+    const float x0 = vcs + x / d2;
+    const float der = (x - x0) / sigma;
+    lat[i] = (f16)(x + der * dt);
+  }
+}
+void launch_euler_step_cfg(const f16* vc, const f16* vu, float g, f16* lat, long n, float sigma, float sigma_next, hipStream_t s) {
+  hipLaunchKernelGGL(k_euler_step_cfg, gs_grid(n), dim3(256), 0, s, vc, vu, g, lat, n, sigma, sigma_next);
+}
+
 __global__ void k_silu(const f16* in, f16* out, long n) {
   GS_LOOP(i, n) { const float x = (float)in[i]; out[i] = (f16)(x * __builtin_amdgcn_rcpf(1.0f + __expf(-x))); }
 }

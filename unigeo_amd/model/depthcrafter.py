@@ -11,6 +11,7 @@ Differences that are deliberate and visible:
   * noise comes from a seeded CPU generator (``seed`` kwarg + the sample's dataset index, so clips get independent noise
     like the reference's fresh draws) instead of the un-seeded global CUDA RNG;
   * ``num_inference_steps`` defaults to the reference's shipped value 5 (:86) and is a kwarg;
+  * ``guidance_scale`` (kwarg / YAML model_params) defaults to the reference's 1.0 (:85); > 1 switches on classifier-free guidance;
   * without checkpoints on disk the constructor raises unless ``synthetic_weights=True`` is passed.
 """
 import os
@@ -24,6 +25,7 @@ class DepthCrafter:
     def __init__(self, model_dir=None, unet_path=None, pre_train_path=None, **kwargs):
         self.num_inference_steps = int(kwargs.get("num_inference_steps", 5))
         self.seed = int(kwargs.get("seed", 0))
+        self.guidance_scale = float(kwargs.get("guidance_scale", 1.0))   # the reference passes 1.0 (:85); > 1 = classifier-free guidance
         self._calls = 0
         device_id = int(kwargs.get("device_id", 0))
         self.device = f"hip:{device_id}"
@@ -107,7 +109,7 @@ class DepthCrafter:
         self._last_seed = clip_seed
         self._noise_prefetch(shape, clip_seed + stride)
         res = self.pipeline(frames, height=frames.shape[1], width=frames.shape[2], output_type="np",
-                            guidance_scale=1.0, num_inference_steps=self.num_inference_steps,
+                            guidance_scale=getattr(self, "guidance_scale", 1.0), num_inference_steps=self.num_inference_steps,
                             window_size=len(frames), overlap=25, track_time=False, seed=clip_seed,
                             noise_latents=noise_latents, noise_aug=noise_aug,
                             intrinsics=K, with_normals=True, return_frames=False)

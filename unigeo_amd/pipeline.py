@@ -6,6 +6,7 @@ Reference interface (``/root/reference/model/depthcrafter.py``):
   * :31-34  ``.to(device)``, ``.enable_xformers_memory_efficient_attention()``, ``.enable_attention_slicing()``
   * :80-90  ``pipeline(frames, height=, width=, output_type="np", guidance_scale=1.0,
             num_inference_steps=, window_size=len(frames), overlap=, track_time=False).frames[0]``
+            (guidance_scale > 1: classifier-free guidance as upstream DepthCrafter's pipeline does it - restated, unpinned)
 
 Everything heavy happens inside libunigeo_hip.so; this file is argument checking, noise generation
 (explicit CPU generator - the reference uses the un-seeded global CUDA RNG) and weight upload.
@@ -90,8 +91,9 @@ class DepthCrafterPipelineHIP:
             raise ValueError("height/width must equal the frame size (the reference passes frames.shape)")
         if H % 64 or Wd % 64:
             raise ValueError("height and width must be multiples of 64")
-        if guidance_scale > 1.0:
-            raise NotImplementedError("classifier-free guidance is not on the reference path (guidance_scale=1.0)")
+        guidance_scale = float(guidance_scale)
+        if not np.isfinite(guidance_scale):
+            raise ValueError("guidance_scale must be finite")
         if T > window_size and window_size > 128:
             raise ValueError("a denoising window holds at most 128 frames (temporal attention tile); pass window_size <= 128")
         if T > window_size and not 0 <= overlap < window_size:
@@ -105,6 +107,9 @@ class DepthCrafterPipelineHIP:
         chunk = decode_chunk_size or self.decode_chunk_size
         eng = self.engine
         eng.set_inputs(video, noise_latents, noise_aug, intrinsics)
+        # classifier-free guidance (> 1; upstream DepthCrafter's scalar guidance, restated - unpinned): engine state, set on every call so that a
+        # call with 1.0 after a guided one is the unguided path again
+        eng.set_guidance(guidance_scale)
         # T > window_size: upstream DepthCrafter's latent sliding windows (off on the reference path, which passes window_size = T)
         eng.run(num_inference_steps, chunk, with_normals=with_normals, window=window_size if T > window_size else 0, overlap=overlap)
         # return_frames=False (the plugin's forward, which consumes depth / normals only): the decoded frames stay in HBM - 59 MB less to download per clip
