@@ -15,7 +15,8 @@
  *     DepthCrafter.prepare_input produces them (model/depthcrafter.py:39-45).
  *   - noise is an INPUT (the reference draws it from the global CUDA RNG without a generator,
  *     model/depthcrafter.py:80-90): noise_latents [T,4,H/8,W/8], noise_aug [T,3,H,W], float32,
- *     laid out as torch.randn would produce them inside the pipeline (NCHW).
+ *     laid out as torch.randn would produce them inside the pipeline (NCHW).  ug_dc_set_inputs_ex can instead generate both on the
+ *     device from one 64-bit seed (the reference draws on the GPU too, unseeded).
  */
 #ifndef UNIGEO_HIP_H
 #define UNIGEO_HIP_H
@@ -86,6 +87,21 @@ int ug_bind_clip(ug_ctx* ctx, const ug_clip_config* cfg);
 int ug_dc_set_inputs(ug_ctx* ctx, const float* frames_thwc, int T, int H, int W, const float* noise_latents,
                      const float* noise_aug, const float* intrinsics_t33);
 int ug_dc_run(ug_ctx* ctx, int steps, int decode_chunk, int with_normals);
+/* Opt-in input modes of the same call (ug_dc_set_inputs is unchanged): replaces DepthCrafter.prepare_input (model/depthcrafter.py:39-45) and the
+ * noise the pipeline draws from the global CUDA RNG (model/depthcrafter.py:80-90).
+ *   frames_format UG_FRAMES_F32_THWC: frames = float32 [T,H,W,3] in [0,1], as ug_dc_set_inputs.
+ *                 UG_FRAMES_U8_TCHW : frames = uint8 planar [T,3,H,W], the dataset's images stacked; converted on the device to x / 255, bit-identical
+ *                                     to prepare_input (a quarter of the upload).
+ *   noise_latents and noise_aug both given: host noise, as ug_dc_set_inputs.  Both NULL: the two resident noise tensors (same buffers, same layout)
+ *   are generated on the context's stream from noise_seed by a counter-based generator (Philox4x32-10 + Box-Muller): element
+ *   e of a tensor depends on (noise_seed, tensor, e) only - not on the context, the rank, the launch geometry or what ran before; |z| <= 5.768.
+ *   One of the two NULL is an error.  Same checks as ug_dc_set_inputs; ug_dc_run / ug_dc_run_windows / guidance read the same buffers.
+ * ug_dc_get_noise: HBM -> host, the resident noise of the current inputs however it got there (noise_latents_out [T,4,H/8,W/8], noise_aug_out
+ *   [T,3,H,W], float32; either may be NULL) - what to pass to ug_dc_set_inputs to repeat a seeded clip bit for bit. */
+enum { UG_FRAMES_F32_THWC = 0, UG_FRAMES_U8_TCHW = 1 };
+int ug_dc_set_inputs_ex(ug_ctx* ctx, const void* frames, int frames_format, int T, int H, int W, const float* noise_latents,
+                        const float* noise_aug, uint64_t noise_seed, const float* intrinsics_t33);
+int ug_dc_get_noise(ug_ctx* ctx, float* noise_latents_out, float* noise_aug_out);
 /* Long-video mode of the pipeline call (`window_size` / `overlap` of model/depthcrafter.py:87-88, which the reference pins to
  * len(frames) / 25, i.e. OFF): latent sliding windows of `window` (<= 128) frames with `overlap` re-noised + cross-faded frames,
  * restated from upstream DepthCrafter's published pipeline (UNPINNED).  window == 0 or >= T is ug_dc_run.  The first `window`

@@ -70,6 +70,15 @@ int ug_op_temporal_attn(ug_ctx* ctx, const float* qkv /*[T*HW,3*H*64]*/, int T, 
 int ug_op_attention_generic(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);
 int ug_op_flash_attn_dh(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);   /* fused self-attention, head dim d in {32,48,80,96,112,128}: the CLIP tower's 16 x 80 heads */
 int ug_op_euler_step(ug_ctx* ctx, const float* v, float* latents_inout, long n, float sigma, float sigma_next);
+/* Clip inputs made on the device (kernels/noise.hip; behind ug_dc_set_inputs_ex of the product header).
+ *   ug_op_philox_u32  : Philox4x32-10 words of blocks block_offset .. block_offset + nblocks - 1 for key = seed (lo, hi) and counter
+ *                       (q lo, q hi, stream, 0) -> out [nblocks][4] uint32 (the generator against the published known-answer vectors)
+ *   ug_op_randn       : standard normal numbers element_offset .. element_offset + n - 1 of (seed, stream).  inout holds n + guard floats: all of
+ *                       it is uploaded, the kernel writes the first n, all of it is downloaded - the guard words come back as they went in
+ *   ug_op_u8_to_frames: uint8 planar [T,3,H,W] -> float32 [T,H,W,3] = x / 255, bit-identical to DepthCrafter.prepare_input (H * W % 4 == 0) */
+int ug_op_philox_u32(ug_ctx* ctx, uint64_t seed, uint32_t stream, uint64_t block_offset, long nblocks, uint32_t* out);
+int ug_op_randn(ug_ctx* ctx, uint64_t seed, uint32_t stream, uint64_t element_offset, long n, long guard, float* inout);
+int ug_op_u8_to_frames(ug_ctx* ctx, const unsigned char* frames_tchw, int T, int H, int W, float* out_thwc);
 /* Tuning aids (not on the product path): GEMM / implicit-conv microbenchmark on device-resident random data,
  * and an override of the tile/split-K heuristic (-1 = heuristic). ms_out: [ms per launch, cfg, split, M, K]. */
 /* GroupNorm launch-scheme A/B (mode: launch_groupnorm in kernels/norm.hip); tuning aid, no reference counterpart. */

@@ -18,7 +18,7 @@ EXPORTS = [
     "ug_unet_config_default", "ug_vae_config_default", "ug_clip_config_default",
     "ug_create", "ug_destroy", "ug_last_error", "ug_workspace_peak",
     "ug_load_tensor", "ug_bind_unet", "ug_bind_vae", "ug_bind_clip",
-    "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
+    "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_dc_set_inputs_ex", "ug_dc_get_noise", "ug_op_philox_u32", "ug_op_randn", "ug_op_u8_to_frames", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
     "ug_eval_depth", "ug_eval_normal", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
@@ -106,6 +106,15 @@ def load_library():
     try:
         lib.ug_dc_set_guidance.argtypes = [vp, C.c_float]
         lib.ug_unet_forward_pair.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp, vp]
+    except AttributeError:
+        if not os.environ.get("UG_LIB_PATH"):      # an explicitly selected OLDER build (tools/ab A/B runs) may lack these
+            raise
+    try:
+        lib.ug_dc_set_inputs_ex.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, C.c_uint64, vp]
+        lib.ug_dc_get_noise.argtypes = [vp, vp, vp]
+        lib.ug_op_philox_u32.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_long, vp]
+        lib.ug_op_randn.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_long, C.c_long, vp]
+        lib.ug_op_u8_to_frames.argtypes = [vp, vp, ip, ip, ip, vp]
     except AttributeError:
         if not os.environ.get("UG_LIB_PATH"):      # an explicitly selected OLDER build (tools/ab A/B runs) may lack these
             raise
@@ -294,6 +303,62 @@ class Engine:
         k = None if intrinsics is None else _f32(intrinsics).reshape(T, 3, 3)
         self._ck(self.lib.ug_dc_set_inputs(self.ctx, _ptr(f), T, H, W, _ptr(nl), _ptr(na), _ptr(k)))
         self._shape = (T, H, W)
+
+    FRAMES_F32_THWC, FRAMES_U8_TCHW = 0, 1
+
+    def set_inputs_ex(self, frames, noise_latents=None, noise_aug=None, seed=None, intrinsics=None):
+        """The opt-in input modes (``ug_dc_set_inputs_ex``).  ``frames``: a uint8 array is planar ``[T,3,H,W]`` (converted to ``x / 255`` on the
+        device), anything else float32 channels-last ``[T,H,W,3]``.  Noise: both host arrays, or neither and a ``seed`` (0 <= seed < 2**64) from
+        which the device generates both tensors."""
+        f = np.asarray(frames)
+        if f.dtype == np.uint8:
+            f = np.ascontiguousarray(f); fmt = self.FRAMES_U8_TCHW
+            if f.ndim != 4 or f.shape[1] != 3:
+                raise ValueError("uint8 frames must be planar [T,3,H,W]")
+            T, _, H, W = f.shape
+        else:
+            f = _f32(f); fmt = self.FRAMES_F32_THWC
+            if f.ndim != 4 or f.shape[3] != 3:
+                raise ValueError("float frames must be channels-last [T,H,W,3]")
+            T, H, W, _ = f.shape
+        if (noise_latents is None) != (noise_aug is None):
+            raise ValueError("pass both noise arrays, or neither (noise from the seed)")
+        if (noise_latents is None) == (seed is None):
+            raise ValueError("pass either the two noise arrays or a seed")
+        nl = na = None
+        if noise_latents is not None:
+            nl, na = _f32(noise_latents).reshape(T, 4, H // 8, W // 8), _f32(noise_aug).reshape(T, 3, H, W)
+        elif not 0 <= int(seed) < 1 << 64:
+            raise ValueError("the noise seed must be in [0, 2**64)")
+        k = None if intrinsics is None else _f32(intrinsics).reshape(T, 3, 3)
+        self._ck(self.lib.ug_dc_set_inputs_ex(self.ctx, _ptr(f), fmt, T, H, W, _ptr(nl), _ptr(na), int(seed or 0), _ptr(k)))
+        self._shape = (T, H, W)
+
+    def get_noise(self):
+        """(noise_latents [T,4,H/8,W/8], noise_aug [T,3,H,W]) resident for the current inputs, host arrays or generated from a seed."""
+        T, H, W = self._shape
+        nl, na = np.empty((T, 4, H // 8, W // 8), np.float32), np.empty((T, 3, H, W), np.float32)
+        self._ck(self.lib.ug_dc_get_noise(self.ctx, _ptr(nl), _ptr(na)))
+        return nl, na
+
+    def op_philox_u32(self, seed, stream, block_offset, nblocks):
+        out = np.empty((int(nblocks), 4), np.uint32)
+        self._ck(self.lib.ug_op_philox_u32(self.ctx, int(seed), int(stream), int(block_offset), int(nblocks), _ptr(out)))
+        return out
+
+    def op_randn(self, seed, stream, element_offset, n, guard=0, fill=np.nan):
+        """n normals of (seed, stream) from ``element_offset`` on, followed by ``guard`` words that went to the device holding ``fill`` and
+        came back from it (untouched by the kernel when it writes exactly n values)."""
+        buf = np.full(int(n) + int(guard), fill, np.float32)
+        self._ck(self.lib.ug_op_randn(self.ctx, int(seed), int(stream), int(element_offset), int(n), int(guard), _ptr(buf)))
+        return buf
+
+    def op_u8_to_frames(self, frames_tchw):
+        f = np.ascontiguousarray(frames_tchw, dtype=np.uint8)
+        T, _, H, W = f.shape
+        out = np.empty((T, H, W, 3), np.float32)
+        self._ck(self.lib.ug_op_u8_to_frames(self.ctx, _ptr(f), T, H, W, _ptr(out)))
+        return out
 
     def run(self, steps, decode_chunk=8, with_normals=False, window=0, overlap=0):
         if window:

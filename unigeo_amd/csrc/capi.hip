@@ -122,6 +122,14 @@ int ug_bind_clip(ug_ctx* x, const ug_clip_config* g) {
 int ug_dc_set_inputs(ug_ctx* x, const float* frames, int T, int H, int W, const float* nl, const float* na, const float* K) {
   UG_TRY(x, dc_set_inputs(x->c, frames, T, H, W, nl, na, K));
 }
+int ug_dc_set_inputs_ex(ug_ctx* x, const void* frames, int frames_format, int T, int H, int W, const float* nl, const float* na,
+                        uint64_t noise_seed, const float* K) {
+  UG_TRY(x, {
+    UG_REQUIRE(frames_format == UG_FRAMES_F32_THWC || frames_format == UG_FRAMES_U8_TCHW, "frames_format must be UG_FRAMES_F32_THWC or UG_FRAMES_U8_TCHW");
+    dc_set_inputs_ex(x->c, frames, frames_format == UG_FRAMES_U8_TCHW, T, H, W, nl, na, noise_seed, K);
+  });
+}
+int ug_dc_get_noise(ug_ctx* x, float* nl, float* na) { UG_TRY(x, dc_get_noise(x->c, nl, na)); }
 int ug_dc_run(ug_ctx* x, int steps, int chunk, int with_normals) { UG_TRY(x, dc_run(x->c, steps, chunk, with_normals)); }
 int ug_dc_run_windows(ug_ctx* x, int steps, int chunk, int with_normals, int window, int overlap) {
   UG_TRY(x, dc_run(x->c, steps, chunk, with_normals, window, overlap));
@@ -980,6 +988,44 @@ int ug_op_euler_step(ug_ctx* x, const float* v, float* lat, long n, float sigma,
     f16* dv = up16(c, v, n); f16* dl = up16(c, lat, n);
     launch_euler_step(dv, dl, n, sigma, sigma_next, c.stream);
     down16(c, dl, lat, n);
+  });
+}
+
+// ---- clip inputs made on the device (kernels/noise.hip): op-level entry points of the parity tests
+int ug_op_philox_u32(ug_ctx* x, uint64_t seed, uint32_t stream, uint64_t block_offset, long nblocks, uint32_t* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(nblocks >= 1 && out, "nblocks >= 1 and an output buffer");
+    uint32_t* d = c.ws.get<uint32_t>(nblocks * 4);
+    launch_philox_u32(d, nblocks, seed, stream, block_offset, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(out, d, (size_t)nblocks * 16, hipMemcpyDeviceToHost));
+  });
+}
+int ug_op_randn(ug_ctx* x, uint64_t seed, uint32_t stream, uint64_t element_offset, long n, long guard, float* inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(n >= 1 && guard >= 0 && inout, "n >= 1, guard >= 0 and a buffer of n + guard floats");
+    float* d = c.ws.get<float>(n + guard);
+    UG_CHECK(hipMemcpy(d, inout, (size_t)(n + guard) * 4, hipMemcpyHostToDevice));
+    launch_randn(d, n, seed, stream, element_offset, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(inout, d, (size_t)(n + guard) * 4, hipMemcpyDeviceToHost));
+  });
+}
+int ug_op_u8_to_frames(ug_ctx* x, const unsigned char* frames_tchw, int T, int H, int W, float* out_thwc) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && H >= 1 && W >= 1 && ((long)H * W) % 4 == 0, "H * W must be a multiple of 4");
+    const long px = (long)T * H * W;
+    unsigned char* d8 = c.ws.get<unsigned char>(px * 3); float* df = c.ws.get<float>(px * 3);
+    UG_CHECK(hipMemcpy(d8, frames_tchw, (size_t)px * 3, hipMemcpyHostToDevice));
+    launch_u8_to_frames(d8, df, T, (long)H * W, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(out_thwc, df, (size_t)px * 12, hipMemcpyDeviceToHost));
   });
 }
 

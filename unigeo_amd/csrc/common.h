@@ -238,6 +238,15 @@ void launch_normals(const float* depth, const float* K33, float* normals, int T,
                     hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
+// Clip inputs made on the device (kernels/noise.hip)
+// ---------------------------------------------------------------------------------------
+// Philox4x32-10, key = seed (lo, hi), counter = (q lo, q hi, stream, 0): the four words of blocks q0 .. q0 + nblocks - 1
+void launch_philox_u32(uint32_t* out, long nblocks, uint64_t seed, uint32_t stream, uint64_t q0, hipStream_t s);
+// out[i] = standard normal number e0 + i of (seed, stream), i in [0, n): Box-Muller on the words of block (e0 + i) >> 2; writes exactly n floats
+void launch_randn(float* out, long n, uint64_t seed, uint32_t stream, uint64_t e0, hipStream_t s);
+void launch_u8_to_frames(const unsigned char* in_tchw, float* out_thwc, int T, long HW, hipStream_t s);   // planar uint8 -> channels-last f32 x / 255 (HW % 4 == 0)
+
+// ---------------------------------------------------------------------------------------
 // fp32-grade path over fp16 hi/lo pairs (kernels/wide.hip): the VAE encoder, which the reference runs in float32
 // ---------------------------------------------------------------------------------------
 void launch_split_pair(const float* x, f16* y, long M, int C, hipStream_t s);          // [M,C] f32 -> [M,2C] = [hi | lo]

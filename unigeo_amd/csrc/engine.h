@@ -213,6 +213,10 @@ f16* sn_vae_decode(Ctx& c, const f16* z4, int B, int h, int w);                /
 // ---- pipeline ----
 void dc_set_inputs(Ctx& c, const float* frames, int T, int H, int W, const float* noise_lat, const float* noise_aug,
                    const float* K33);
+// frames: float32 [T,H,W,3] or (frames_u8) uint8 planar [T,3,H,W]; noise arrays both given, or both NULL = generated on the device from noise_seed
+void dc_set_inputs_ex(Ctx& c, const void* frames, int frames_u8, int T, int H, int W, const float* noise_lat, const float* noise_aug,
+                      uint64_t noise_seed, const float* K33);
+void dc_get_noise(Ctx& c, float* noise_lat, float* noise_aug);   // resident noise of the current inputs -> host; either pointer may be NULL
 void dc_run(Ctx& c, int steps, int chunk, int with_normals, int window = 0, int overlap = 0);
 void dc_get_outputs(Ctx& c, float* frames, float* depth, float* normals);
 

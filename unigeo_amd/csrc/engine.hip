@@ -1523,8 +1523,8 @@ f16* clip_embed(Ctx& c, const f16* video_m11, int T, int H, int W) {
 }
 
 // ----------------------------------------------------------------------------- pipeline
-void dc_set_inputs(Ctx& c, const float* frames, int T, int H, int W, const float* noise_lat, const float* noise_aug,
-                   const float* K33) {
+// resident I/O buffers of a clip (released by the next set-inputs call)
+static void dc_alloc_io(Ctx& c, int T, int H, int W) {
   UG_REQUIRE(H % 64 == 0 && W % 64 == 0, "height and width must be multiples of 64 (VAE /8, UNet /8)");
   UG_REQUIRE(T >= 1 && T <= 4096, "1..4096 frames (at most 128 per denoising window)");
   if (c.io_ready) { c.ws.release(c.io_mark); c.io_ready = false; }
@@ -1535,6 +1535,12 @@ void dc_set_inputs(Ctx& c, const float* frames, int T, int H, int W, const float
   c.d_noise_lat = c.ws.get<float>(lp * 4); c.d_K = c.ws.get<float>((long)T * 9);
   c.d_out_frames = c.ws.get<float>(px * 3); c.d_depth = c.ws.get<float>(px); c.d_normals = c.ws.get<float>(px * 3);
   c.d_mm = c.ws.get<float>(64);
+}
+
+void dc_set_inputs(Ctx& c, const float* frames, int T, int H, int W, const float* noise_lat, const float* noise_aug,
+                   const float* K33) {
+  dc_alloc_io(c, T, H, W);
+  const long px = (long)T * H * W, lp = (long)T * (H / 8) * (W / 8);
   UG_CHECK(hipMemcpyAsync(c.d_frames, frames, px * 3 * 4, hipMemcpyHostToDevice, c.stream));
   UG_CHECK(hipMemcpyAsync(c.d_noise_aug, noise_aug, px * 3 * 4, hipMemcpyHostToDevice, c.stream));
   UG_CHECK(hipMemcpyAsync(c.d_noise_lat, noise_lat, lp * 4 * 4, hipMemcpyHostToDevice, c.stream));
@@ -1542,6 +1548,47 @@ void dc_set_inputs(Ctx& c, const float* frames, int T, int H, int W, const float
   else UG_CHECK(hipMemsetAsync(c.d_K, 0, (size_t)T * 9 * 4, c.stream));
   UG_CHECK(hipStreamSynchronize(c.stream));
   c.io_ready = true;
+}
+
+// The opt-in input modes: frames as float32 channels-last (as dc_set_inputs) or uint8 planar [T,3,H,W] (converted on the device,
+// a quarter of the upload), noise as two host arrays (as dc_set_inputs) or a 64-bit seed (both tensors generated on the stream into the same buffers,
+// same layout: stream 0 = noise_aug, stream 1 = noise_latents).  dc_run reads the same buffers either way.
+void dc_set_inputs_ex(Ctx& c, const void* frames, int frames_u8, int T, int H, int W, const float* noise_lat, const float* noise_aug,
+                      uint64_t noise_seed, const float* K33) {
+  UG_REQUIRE(frames != nullptr, "frames must not be NULL");
+  UG_REQUIRE((noise_lat == nullptr) == (noise_aug == nullptr), "pass both noise arrays, or neither (noise from the seed)");
+  dc_alloc_io(c, T, H, W);
+  const long px = (long)T * H * W, lp = (long)T * (H / 8) * (W / 8);
+  const size_t mk = c.ws.mark();
+  if (frames_u8) {
+    unsigned char* d_u8 = c.ws.get<unsigned char>(px * 3);       // transient: released below, after the stream has drained
+    void* hin = pinned(c, 0, (size_t)px * 3);                    // page-locked staging: one memcpy + one DMA at link rate
+    memcpy(hin, frames, (size_t)px * 3);
+    UG_CHECK(hipMemcpyAsync(d_u8, hin, (size_t)px * 3, hipMemcpyHostToDevice, c.stream));
+    launch_u8_to_frames(d_u8, c.d_frames, T, (long)H * W, c.stream);
+  } else {
+    UG_CHECK(hipMemcpyAsync(c.d_frames, frames, px * 3 * 4, hipMemcpyHostToDevice, c.stream));
+  }
+  if (noise_lat) {
+    UG_CHECK(hipMemcpyAsync(c.d_noise_aug, noise_aug, px * 3 * 4, hipMemcpyHostToDevice, c.stream));
+    UG_CHECK(hipMemcpyAsync(c.d_noise_lat, noise_lat, lp * 4 * 4, hipMemcpyHostToDevice, c.stream));
+  } else {
+    launch_randn(c.d_noise_aug, px * 3, noise_seed, 0u, 0, c.stream);
+    launch_randn(c.d_noise_lat, lp * 4, noise_seed, 1u, 0, c.stream);
+  }
+  if (K33) UG_CHECK(hipMemcpyAsync(c.d_K, K33, (size_t)T * 9 * 4, hipMemcpyHostToDevice, c.stream));
+  else UG_CHECK(hipMemsetAsync(c.d_K, 0, (size_t)T * 9 * 4, c.stream));
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  c.ws.release(mk);
+  c.io_ready = true;
+}
+
+void dc_get_noise(Ctx& c, float* noise_lat, float* noise_aug) {
+  UG_REQUIRE(c.io_ready, "no resident inputs: set the inputs of a clip first");
+  const long px = (long)c.T * c.H * c.W, lp = (long)c.T * (c.H / 8) * (c.W / 8);
+  if (noise_lat) UG_CHECK(hipMemcpy(noise_lat, c.d_noise_lat, lp * 4 * 4, hipMemcpyDeviceToHost));
+  if (noise_aug) UG_CHECK(hipMemcpy(noise_aug, c.d_noise_aug, px * 3 * 4, hipMemcpyDeviceToHost));
 }
 
 static void karras_sigmas(int n, std::vector<float>& sig, std::vector<float>& ts) {

@@ -10,6 +10,9 @@ Differences that are deliberate and visible:
     step (40 s per clip on the reference's CPU path) run on the GPU inside one C-ABI call;
   * noise comes from a seeded CPU generator (``seed`` kwarg + the sample's dataset index, so clips get independent noise
     like the reference's fresh draws) instead of the un-seeded global CUDA RNG;
+  * ``noise="device"`` (kwarg / YAML model_params; default ``"host"``): the dataset's uint8 images are uploaded as they are and both noise tensors are
+    generated on the GPU from the same per-clip seed (counter-based generator) - no host draw, no prefetch thread, no noise
+    held between calls; a different (equally reproducible, rank-independent) noise sequence than the CPU generator's;
   * ``num_inference_steps`` defaults to the reference's shipped value 5 (:86) and is a kwarg;
   * ``guidance_scale`` (kwarg / YAML model_params) defaults to the reference's 1.0 (:85); > 1 switches on classifier-free guidance;
   * without checkpoints on disk the constructor raises unless ``synthetic_weights=True`` is passed.
@@ -26,6 +29,9 @@ class DepthCrafter:
         self.num_inference_steps = int(kwargs.get("num_inference_steps", 5))
         self.seed = int(kwargs.get("seed", 0))
         self.guidance_scale = float(kwargs.get("guidance_scale", 1.0))   # the reference passes 1.0 (:85); > 1 = classifier-free guidance
+        self.noise = str(kwargs.get("noise", "host"))                    # "host": seeded CPU generator (+ prefetch thread); "device": generated on the GPU from the seed
+        if self.noise not in ("host", "device"):
+            raise ValueError('noise must be "host" or "device"')
         self._calls = 0
         device_id = int(kwargs.get("device_id", 0))
         self.device = f"hip:{device_id}"
@@ -92,7 +98,21 @@ class DepthCrafter:
         th.start()
         self._noise_pf = ((shape, seed), th, box)
 
+    def _forward_device_noise(self, data):
+        """``noise="device"``: uint8 planar frames up, one seed down to the library; nothing drawn, started or kept on the host."""
+        frames = np.stack([np.asarray(x).astype(np.uint8) for x in data["images"]], axis=0)       # [T,3,H,W]: prepare_input without the transpose and the division
+        K = np.stack([np.asarray(k, dtype=np.float32).reshape(3, 3) for k in data["intrinsics"]], 0)
+        clip_seed = self.seed + int(data["_index"]) if "_index" in data else self.seed + self._calls
+        self._calls += 1
+        res = self.pipeline(frames, height=frames.shape[2], width=frames.shape[3], output_type="np",
+                            guidance_scale=getattr(self, "guidance_scale", 1.0), num_inference_steps=self.num_inference_steps,
+                            window_size=len(frames), overlap=25, track_time=False, seed=clip_seed, noise="device",
+                            intrinsics=K, with_normals=True, return_frames=False)
+        return self.prepare_output(list(res.depth), data, _device_normals=res.normals)
+
     def forward(self, data):
+        if getattr(self, "noise", "host") == "device":
+            return self._forward_device_noise(data)
         frames = self.prepare_input(data)
         K = np.stack([np.asarray(k, dtype=np.float32).reshape(3, 3) for k in data["intrinsics"]], 0)
         # the reference draws fresh noise per clip from the global RNG; here: a per-clip seed derived from the sample's

@@ -10,6 +10,8 @@ Reference interface (``/root/reference/model/depthcrafter.py``):
 
 Everything heavy happens inside libunigeo_hip.so; this file is argument checking, noise generation
 (explicit CPU generator - the reference uses the un-seeded global CUDA RNG) and weight upload.
+``noise="device"`` leaves the draw to the library as well: both noise tensors are generated on the GPU from the seed
+(counter-based), and uint8 planar frames are converted there.
 """
 import dataclasses
 from types import SimpleNamespace
@@ -82,11 +84,25 @@ class DepthCrafterPipelineHIP:
     def __call__(self, video, height=None, width=None, num_inference_steps=25, guidance_scale=1.0,
                  window_size=110, noise_aug_strength=0.02, decode_chunk_size=None, output_type="np",
                  overlap=25, track_time=False, noise_latents=None, noise_aug=None, seed=None,
-                 intrinsics=None, with_normals=False, return_frames=True):
-        video = np.asarray(video, dtype=np.float32)
-        if video.ndim != 4 or video.shape[-1] != 3:
-            raise ValueError("video must be [T,H,W,3] float in [0,1]")
-        T, H, Wd, _ = video.shape
+                 intrinsics=None, with_normals=False, return_frames=True, noise="host"):
+        """``noise="host"`` (default): ``noise_latents`` / ``noise_aug``, or a draw from ``make_noise(seed)``.  ``noise="device"``: both tensors
+        are generated on the GPU from ``seed`` (or ``self.seed``); passing noise arrays as well is an error.  ``video``: float ``[T,H,W,3]``
+        in [0,1], or a uint8 array ``[T,3,H,W]`` (planar, as the dataset delivers it) that the device converts to ``x / 255``."""
+        if noise not in ("host", "device"):
+            raise ValueError('noise must be "host" or "device"')
+        if noise == "device" and (noise_latents is not None or noise_aug is not None):
+            raise ValueError('noise="device" generates the noise from the seed: do not pass noise_latents / noise_aug')
+        u8 = getattr(video, "dtype", None) == np.uint8
+        if u8:
+            video = np.asarray(video)
+            if video.ndim != 4 or video.shape[1] != 3:
+                raise ValueError("uint8 video must be planar [T,3,H,W]")
+            T, _, H, Wd = video.shape
+        else:
+            video = np.asarray(video, dtype=np.float32)
+            if video.ndim != 4 or video.shape[-1] != 3:
+                raise ValueError("video must be [T,H,W,3] float in [0,1]")
+            T, H, Wd, _ = video.shape
         if (height not in (None, H)) or (width not in (None, Wd)):
             raise ValueError("height/width must equal the frame size (the reference passes frames.shape)")
         if H % 64 or Wd % 64:
@@ -102,11 +118,20 @@ class DepthCrafterPipelineHIP:
             raise NotImplementedError("noise_aug_strength is fixed at the pipeline default 0.02")
         if output_type != "np":
             raise NotImplementedError('only output_type="np" (what the reference requests)')
-        if noise_latents is None or noise_aug is None:
-            noise_latents, noise_aug = make_noise(T, H, Wd, self.seed if seed is None else seed)
+        seed = self.seed if seed is None else seed
+        if noise == "device":
+            if not 0 <= int(seed) < 1 << 64:
+                raise ValueError("the noise seed must be in [0, 2**64)")
+        elif noise_latents is None or noise_aug is None:
+            noise_latents, noise_aug = make_noise(T, H, Wd, seed)
         chunk = decode_chunk_size or self.decode_chunk_size
         eng = self.engine
-        eng.set_inputs(video, noise_latents, noise_aug, intrinsics)
+        if noise == "device":
+            eng.set_inputs_ex(video, seed=int(seed), intrinsics=intrinsics)
+        elif u8:
+            eng.set_inputs_ex(video, noise_latents=noise_latents, noise_aug=noise_aug, intrinsics=intrinsics)
+        else:
+            eng.set_inputs(video, noise_latents, noise_aug, intrinsics)
         # classifier-free guidance (> 1; upstream DepthCrafter's scalar guidance, restated - unpinned): engine state, set on every call so that a
         # call with 1.0 after a guided one is the unguided path again
         eng.set_guidance(guidance_scale)
