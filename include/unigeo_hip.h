@@ -174,6 +174,26 @@ int ug_eval_depth(ug_ctx* ctx, const float* pred_depth, const float* gt_depth, c
                   float max_depth, double* out11);
 int ug_eval_normal(ug_ctx* ctx, const float* pred_normals, const float* gt_normals, const unsigned char* mask, long n,
                    double* out8);
+/* ug_eval_depth with the other alignment modes of the reference's depth_evaluation (metrics/eval_depth.py:59-204):
+ * p = clamp(pred, pre_clip) on mask1 = gt > 0 (and gt < max_depth) -> (s, t) of the mode -> p' = clamp(s p + t, post_clip) -> the same metrics.
+ *   UG_ALIGN_LSTSQ  (align_with_lstsq=True)  least-squares scale and shift, as ug_eval_depth, fitted on the pre-clipped p
+ *   UG_ALIGN_MEDIAN (the reference's default) s = median(gt) / median(p), float32 division of the exact LOWER medians (torch.median), t = 0
+ *   UG_ALIGN_SCALE  (align_with_scale=True)  s0 = mean(gt) / mean(p), ten Weiszfeld steps w = 1 / (|s p - gt| + 1e-8), s = sum(w p gt) / sum(w p p),
+ *                   s = max(s, 1e-3), t = 0; sums and s in float64 with a fixed order: the same input gives the same bits.  The 1 / |r| weights make
+ *                   this mode ill-conditioned at clip size - s moves by 1e-4 .. 3e-3 with the summation order alone, and the reference's float32
+ *                   value is as far from any float64 one - so the value is deterministic, but no more "the" answer than another order's
+ *   UG_ALIGN_METRIC (metric_scale=True)      s = 1, t = 0
+ * out11 as ug_eval_depth.  err_map_out (host, [n], may be NULL) = |s * pred + t - gt| / gt on mask1 and 0 elsewhere, from the ORIGINAL
+ * (unclipped) prediction - the reference's second return value.  No valid pixel: zero metrics, (s, t) = (1, 0) for METRIC, (0, 0) otherwise.
+ * An unknown alignment is an error (ug_last_error).  With the default options the result equals ug_eval_depth's bit for bit.
+ * align_with_lad / align_with_lad2 (BFGS / 1000-step Adam on a non-smooth objective: no reproducible answer) and disp_input (calls a
+ * function the reference never defines) have no counterpart. */
+enum { UG_ALIGN_LSTSQ = 0, UG_ALIGN_MEDIAN = 1, UG_ALIGN_SCALE = 2, UG_ALIGN_METRIC = 3 };
+typedef struct { int alignment; float max_depth;            /* <= 0 or NaN: gt > 0 only */
+                 float pre_clip_min, pre_clip_max, post_clip_min, post_clip_max; /* NaN: off */ } ug_depth_eval_opts;
+void ug_depth_eval_opts_default(ug_depth_eval_opts* o);     /* LSTSQ, 80, all clips off */
+int ug_eval_depth_ex(ug_ctx* ctx, const float* pred_depth /* NULL: resident depth */, const float* gt_depth, const unsigned char* custom_mask,
+                     long n, const ug_depth_eval_opts* opts, double* out11, float* err_map_out /* [n] or NULL */);
 
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */

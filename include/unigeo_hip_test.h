@@ -79,6 +79,11 @@ int ug_op_euler_step(ug_ctx* ctx, const float* v, float* latents_inout, long n, 
 int ug_op_philox_u32(ug_ctx* ctx, uint64_t seed, uint32_t stream, uint64_t block_offset, long nblocks, uint32_t* out);
 int ug_op_randn(ug_ctx* ctx, uint64_t seed, uint32_t stream, uint64_t element_offset, long n, long guard, float* inout);
 int ug_op_u8_to_frames(ug_ctx* ctx, const unsigned char* frames_tchw, int T, int H, int W, float* out_thwc);
+/* The exact masked selection behind UG_ALIGN_MEDIAN alone (kernels/metrics.hip): out_medians = the lower medians (element (count - 1) / 2 of the
+ * sorted values) of clamp(pred, pre_clip_min, pre_clip_max) and of gt over gt > 0 (and gt < max_depth; <= 0 or NaN: off), *out_count = how many
+ * pixels that is.  NaN clip bounds are off.  count = 0 leaves the medians 0. */
+int ug_op_masked_median(ug_ctx* ctx, const float* pred, const float* gt, long n, float max_depth, float pre_clip_min, float pre_clip_max,
+                        float* out_medians /*[2]*/, long* out_count);
 /* Tuning aids (not on the product path): GEMM / implicit-conv microbenchmark on device-resident random data,
  * and an override of the tile/split-K heuristic (-1 = heuristic). ms_out: [ms per launch, cfg, split, M, K]. */
 /* GroupNorm launch-scheme A/B (mode: launch_groupnorm in kernels/norm.hip); tuning aid, no reference counterpart. */

@@ -19,7 +19,7 @@ EXPORTS = [
     "ug_create", "ug_destroy", "ug_last_error", "ug_workspace_peak",
     "ug_load_tensor", "ug_bind_unet", "ug_bind_vae", "ug_bind_clip",
     "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_dc_set_inputs_ex", "ug_dc_get_noise", "ug_op_philox_u32", "ug_op_randn", "ug_op_u8_to_frames", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
-    "ug_eval_depth", "ug_eval_normal", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
+    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
@@ -49,6 +49,13 @@ class CLIPConfigC(C.Structure):
                 ("num_attention_heads", C.c_int), ("image_size", C.c_int), ("patch_size", C.c_int),
                 ("projection_dim", C.c_int), ("layer_norm_eps", C.c_float)]
 
+
+class DepthEvalOptsC(C.Structure):
+    _fields_ = [("alignment", C.c_int), ("max_depth", C.c_float), ("pre_clip_min", C.c_float), ("pre_clip_max", C.c_float),
+                ("post_clip_min", C.c_float), ("post_clip_max", C.c_float)]
+
+
+DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_ALIGN_* of include/unigeo_hip.h
 
 _lib = None
 
@@ -99,6 +106,10 @@ def load_library():
     lib.ug_dc_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.ug_eval_depth.argtypes = [vp, vp, vp, vp, C.c_long, C.c_float, vp]
     lib.ug_eval_normal.argtypes = [vp, vp, vp, vp, C.c_long, vp]
+    lib.ug_depth_eval_opts_default.restype = None
+    lib.ug_depth_eval_opts_default.argtypes = [C.POINTER(DepthEvalOptsC)]
+    lib.ug_eval_depth_ex.argtypes = [vp, vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, vp]
+    lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -510,15 +521,41 @@ class Engine:
     DEPTH_KEYS = ["Abs Rel", "Sq Rel", "RMSE", "Log RMSE", "delta < 1.", "delta < 1.25", "delta < 1.25^2", "delta < 1.25^3"]
     NORMAL_KEYS = ["normal mean", "normal median", "normal rmse", "angle < 5", "angle < 7.5", "angle < 11.25", "angle < 22.5", "angle < 30"]
 
-    def eval_depth(self, gt, mask=None, pred=None, max_depth=80.0):
+    def eval_depth(self, gt, mask=None, pred=None, max_depth=80.0, alignment="lstsq", pre_clip_min=None, pre_clip_max=None,
+                   post_clip_min=None, post_clip_max=None, return_error_map=False):
+        """Depth metrics on the device -> ``(res, (s, t))``, with ``return_error_map=True`` ``(res, (s, t), error_map)``.
+        ``alignment``: "lstsq" | "median" | "scale" | "metric" (``ug_eval_depth_ex``); the clip bounds clamp the
+        prediction before / after the alignment; ``max_depth=None`` keeps every ``gt > 0``.  The defaults call ``ug_eval_depth``."""
+        if alignment not in DEPTH_ALIGNMENTS:
+            raise ValueError(f"alignment must be one of {sorted(DEPTH_ALIGNMENTS)}, not {alignment!r}")
         g = _f32(gt); n = g.size
         p = None if pred is None else _f32(pred)
         m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
         out = np.zeros(11, np.float64)
-        self._ck(self.lib.ug_eval_depth(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, float(max_depth), _ptr(out)))
+        clips = (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)
+        emap = None
+        if alignment == "lstsq" and max_depth is not None and not return_error_map and all(c is None for c in clips):
+            self._ck(self.lib.ug_eval_depth(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, float(max_depth), _ptr(out)))
+        else:
+            o = DepthEvalOptsC(DEPTH_ALIGNMENTS[alignment], float("nan") if max_depth is None else float(max_depth),
+                               *[float("nan") if c is None else float(c) for c in clips])
+            emap = np.empty(g.shape, np.float32) if return_error_map else None
+            self._ck(self.lib.ug_eval_depth_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, C.byref(o), _ptr(out), _ptr(emap)))
         res = dict(zip(self.DEPTH_KEYS, out[:8].tolist()))
         res["valid_pixels"] = int(out[8])
+        if return_error_map:
+            return res, (float(out[9]), float(out[10])), emap
         return res, (float(out[9]), float(out[10]))
+
+    def op_masked_median(self, pred, gt, max_depth=80.0, pre_clip_min=None, pre_clip_max=None):
+        """The exact masked selection alone -> (lower median of clamp(pred), lower median of gt, count) over the valid ``gt``."""
+        p, g = _f32(pred).reshape(-1), _f32(gt).reshape(-1)
+        med = np.zeros(2, np.float32); cnt = C.c_long(0)
+        nan = float("nan")
+        self._ck(self.lib.ug_op_masked_median(self.ctx, _ptr(p), _ptr(g), p.size, nan if max_depth is None else float(max_depth),
+                                              nan if pre_clip_min is None else float(pre_clip_min),
+                                              nan if pre_clip_max is None else float(pre_clip_max), _ptr(med), C.byref(cnt)))
+        return med[0], med[1], int(cnt.value)
 
     def eval_normal(self, gt, mask=None, pred=None):
         g = _f32(gt); n = g.size // 3

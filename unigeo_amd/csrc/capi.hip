@@ -426,44 +426,136 @@ int ug_resize_bilinear(ug_ctx* x, const float* in, int B, int Hi, int Wi, int C,
   });
 }
 
+// least squares of g ~ s*p + t from the normal-equation sums n, sum p, sum p^2, sum g, sum p*g:  [sum p^2, sum p; sum p, n] [s; t] = [sum pg; sum g]
+static void lstsq_solve(const double* a, double& s_, double& t_) {
+  const double det = a[2] * a[0] - a[1] * a[1];
+  // Degenerate clips do not abort the evaluation run (the reference's np.linalg.lstsq returns the minimum-norm solution
+  // and its loop continues, metrics/alignment.py:150-167): no valid pixel -> s = t = 0 and zero metrics below; rank-1
+  // system (one pixel / constant prediction p = c) -> [s, t] = mean(g) / (c^2 + 1) * [c, 1].
+  s_ = 0.0; t_ = 0.0;
+  if (a[0] >= 1) {
+    if (fabs(det) > 1e-12 * fmax(1.0, a[2] * a[0])) { s_ = (a[4] * a[0] - a[1] * a[3]) / det; t_ = (a[2] * a[3] - a[1] * a[4]) / det; }
+    else { const double cm = a[1] / a[0], gm = a[3] / a[0]; s_ = cm * gm / (cm * cm + 1.0); t_ = gm / (cm * cm + 1.0); }
+  }
+}
+static void depth_metrics_out(const double* m, double s_, double t_, double* out) {
+  const double cnt = m[0];
+  if (cnt > 0) {
+    out[0] = m[1] / cnt; out[1] = m[2] / cnt; out[2] = sqrt(m[3] / cnt); out[3] = sqrt(m[4] / cnt);
+    for (int k = 0; k < 4; ++k) out[4 + k] = m[5 + k] / cnt;
+  } else { for (int k = 0; k < 8; ++k) out[k] = 0; }
+  out[8] = cnt; out[9] = s_; out[10] = t_;
+}
+struct DepthEvalBufs { const float* dp; float* dg; unsigned char* dm; };
+static DepthEvalBufs depth_eval_upload(Ctx& c, const float* pred, const float* gt, const unsigned char* cmask, long n) {
+  DepthEvalBufs b{nullptr, nullptr, nullptr};
+  if (pred) { float* d = c.ws.get<float>(n); UG_CHECK(hipMemcpy(d, pred, n * 4, hipMemcpyHostToDevice)); b.dp = d; }
+  else { UG_REQUIRE(c.io_ready && n == (long)c.T * c.H * c.W, "no resident depth of that size"); b.dp = c.d_depth; }
+  b.dg = c.ws.get<float>(n); UG_CHECK(hipMemcpy(b.dg, gt, n * 4, hipMemcpyHostToDevice));
+  if (cmask) { b.dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(b.dm, cmask, n, hipMemcpyHostToDevice)); }
+  return b;
+}
+static void eval_depth_lstsq(Ctx& c, const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, double* out) {
+  const DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
+  double* part = c.ws.get<double>(1024 * 9);
+  std::vector<double> h(1024 * 9);
+  int nb = 0;
+  launch_depth_fit(d.dp, d.dg, n, max_depth, part, &nb, c.stream);
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(h.data(), part, (size_t)nb * 5 * 8, hipMemcpyDeviceToHost));
+  double a[5] = {0, 0, 0, 0, 0};
+  for (int b = 0; b < nb; ++b) for (int k = 0; k < 5; ++k) a[k] += h[b * 5 + k];
+  double s_, t_;
+  lstsq_solve(a, s_, t_);
+  launch_depth_metrics(d.dp, d.dg, d.dm, n, max_depth, (float)s_, (float)t_, part, &nb, c.stream);
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(h.data(), part, (size_t)nb * 9 * 8, hipMemcpyDeviceToHost));
+  double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < nb; ++b) for (int k = 0; k < 9; ++k) m[k] += h[b * 9 + k];
+  depth_metrics_out(m, s_, t_, out);
+}
+
 int ug_eval_depth(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, double* out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
-    const float* dp;
-    if (pred) { float* d = c.ws.get<float>(n); UG_CHECK(hipMemcpy(d, pred, n * 4, hipMemcpyHostToDevice)); dp = d; }
-    else { UG_REQUIRE(c.io_ready && n == (long)c.T * c.H * c.W, "no resident depth of that size"); dp = c.d_depth; }
-    float* dg = c.ws.get<float>(n); UG_CHECK(hipMemcpy(dg, gt, n * 4, hipMemcpyHostToDevice));
-    unsigned char* dm = nullptr;
-    if (cmask) { dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(dm, cmask, n, hipMemcpyHostToDevice)); }
+    eval_depth_lstsq(c, pred, gt, cmask, n, max_depth, out);
+  });
+}
+
+void ug_depth_eval_opts_default(ug_depth_eval_opts* o) {
+  o->alignment = UG_ALIGN_LSTSQ; o->max_depth = 80.f;
+  o->pre_clip_min = o->pre_clip_max = o->post_clip_min = o->post_clip_max = NAN;
+}
+static inline float clip_lo(float v) { return std::isnan(v) ? -INFINITY : v; }
+static inline float clip_hi(float v) { return std::isnan(v) ? INFINITY : v; }
+static inline float depth_bound(float v) { return (std::isnan(v) || v <= 0.f) ? NAN : v; }   // NaN: the kernels test gt > 0 only
+
+int ug_eval_depth_ex(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, const ug_depth_eval_opts* o,
+                     double* out, float* emap_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(o != nullptr, "options must not be NULL");
+    UG_REQUIRE(o->alignment >= UG_ALIGN_LSTSQ && o->alignment <= UG_ALIGN_METRIC, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC)");
+    UG_REQUIRE(n >= 0 && n < (1L << 32), "pixel count");
+    const bool clips = !std::isnan(o->pre_clip_min) || !std::isnan(o->pre_clip_max) || !std::isnan(o->post_clip_min) || !std::isnan(o->post_clip_max);
+    if (o->alignment == UG_ALIGN_LSTSQ && !clips && !emap_out && o->max_depth > 0.f) {   // what ug_eval_depth computes: its launches, its bits
+      eval_depth_lstsq(c, pred, gt, cmask, n, o->max_depth, out);
+      return 0;
+    }
+    const float md = depth_bound(o->max_depth);
+    const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
+    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
     double* part = c.ws.get<double>(1024 * 9);
     std::vector<double> h(1024 * 9);
     int nb = 0;
-    launch_depth_fit(dp, dg, n, max_depth, part, &nb, c.stream);
-    UG_CHECK(hipStreamSynchronize(c.stream));
-    UG_CHECK(hipMemcpy(h.data(), part, (size_t)nb * 5 * 8, hipMemcpyDeviceToHost));
-    double a[5] = {0, 0, 0, 0, 0};
-    for (int b = 0; b < nb; ++b) for (int k = 0; k < 5; ++k) a[k] += h[b * 5 + k];
-    // least squares of g ~ s*p + t:  [sum p^2, sum p; sum p, n] [s; t] = [sum pg; sum g]
-    const double det = a[2] * a[0] - a[1] * a[1];
-    // Degenerate clips do not abort the evaluation run (the reference's np.linalg.lstsq returns the minimum-norm solution
-    // and its loop continues, metrics/alignment.py:150-167): no valid pixel -> s = t = 0 and zero metrics below; rank-1
-    // system (one pixel / constant prediction p = c) -> [s, t] = mean(g) / (c^2 + 1) * [c, 1].
     double s_ = 0.0, t_ = 0.0;
-    if (a[0] >= 1) {
-      if (fabs(det) > 1e-12 * fmax(1.0, a[2] * a[0])) { s_ = (a[4] * a[0] - a[1] * a[3]) / det; t_ = (a[2] * a[3] - a[1] * a[4]) / det; }
-      else { const double cm = a[1] / a[0], gm = a[3] / a[0]; s_ = cm * gm / (cm * cm + 1.0); t_ = gm / (cm * cm + 1.0); }
-    }
-    launch_depth_metrics(dp, dg, dm, n, max_depth, (float)s_, (float)t_, part, &nb, c.stream);
+    if (o->alignment == UG_ALIGN_LSTSQ) {
+      launch_depth_fit_ex(d.dp, d.dg, n, md, lo, hi, part, &nb, c.stream);
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      UG_CHECK(hipMemcpy(h.data(), part, (size_t)nb * 5 * 8, hipMemcpyDeviceToHost));
+      double a[5] = {0, 0, 0, 0, 0};
+      for (int b = 0; b < nb; ++b) for (int k = 0; k < 5; ++k) a[k] += h[b * 5 + k];
+      lstsq_solve(a, s_, t_);
+    } else if (o->alignment == UG_ALIGN_MEDIAN) {
+      unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
+      launch_masked_median(d.dp, d.dg, n, md, lo, hi, sel, c.stream);
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      unsigned r[3];
+      UG_CHECK(hipMemcpy(r, sel + SEL_COUNT, sizeof(r), hipMemcpyDeviceToHost));
+      float mp, mg; memcpy(&mp, &r[1], 4); memcpy(&mg, &r[2], 4);
+      if (r[0] > 0) { const float sf = mg / mp; s_ = sf; }
+    } else if (o->alignment == UG_ALIGN_SCALE) {
+      double* wz = c.ws.get<double>(2);
+      launch_weiszfeld_scale(d.dp, d.dg, n, md, lo, hi, 10, wz, part, c.stream);
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      double r[2];
+      UG_CHECK(hipMemcpy(r, wz, sizeof(r), hipMemcpyDeviceToHost));
+      if (r[1] >= 1) s_ = r[0] < 1e-3 ? 1e-3 : r[0];
+    } else s_ = 1.0;
+    float* dmap = emap_out ? c.ws.get<float>(n) : nullptr;
+    launch_depth_metrics_ex(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, (float)s_, (float)t_, part, dmap, &nb, c.stream);
     UG_CHECK(hipStreamSynchronize(c.stream));
     UG_CHECK(hipMemcpy(h.data(), part, (size_t)nb * 9 * 8, hipMemcpyDeviceToHost));
+    if (emap_out) UG_CHECK(hipMemcpy(emap_out, dmap, n * 4, hipMemcpyDeviceToHost));
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int b = 0; b < nb; ++b) for (int k = 0; k < 9; ++k) m[k] += h[b * 9 + k];
-    const double cnt = m[0];
-    if (cnt > 0) {
-      out[0] = m[1] / cnt; out[1] = m[2] / cnt; out[2] = sqrt(m[3] / cnt); out[3] = sqrt(m[4] / cnt);
-      for (int k = 0; k < 4; ++k) out[4 + k] = m[5 + k] / cnt;
-    } else { for (int k = 0; k < 8; ++k) out[k] = 0; }
-    out[8] = cnt; out[9] = s_; out[10] = t_;
+    depth_metrics_out(m, s_, t_, out);
+  });
+}
+
+int ug_op_masked_median(ug_ctx* x, const float* pred, const float* gt, long n, float max_depth, float pre_clip_min, float pre_clip_max,
+                        float* out_medians, long* out_count) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(n >= 1 && n < (1L << 32), "pixel count");
+    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, nullptr, n);
+    unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
+    launch_masked_median(d.dp, d.dg, n, depth_bound(max_depth), clip_lo(pre_clip_min), clip_hi(pre_clip_max), sel, c.stream);
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    unsigned r[3];
+    UG_CHECK(hipMemcpy(r, sel + SEL_COUNT, sizeof(r), hipMemcpyDeviceToHost));
+    *out_count = (long)r[0];
+    memcpy(out_medians, &r[1], 8);
   });
 }
 

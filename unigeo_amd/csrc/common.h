@@ -271,3 +271,15 @@ void launch_depth_metrics(const float* pred, const float* gt, const unsigned cha
 void launch_normal_err(const float* pn, const float* gn, const unsigned char* mask, long n, float* err, double* part,
                        unsigned* hist, int* nb, hipStream_t s);
 void launch_collect_bin(const float* err, long n, int bin, float* out, unsigned* count, unsigned cap, hipStream_t s);
+// depth alignment modes beyond least squares (kernels/metrics.hip)
+#define SEL_PREFIX 2048       // select state (unsigned words): 4 x 2 x 256 histogram words, then prefix[2], rank[2], count, median[2]
+#define SEL_RANK 2050
+#define SEL_COUNT 2052
+#define SEL_MED 2053
+#define SEL_WORDS 2056
+void launch_masked_median(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* sel, hipStream_t s);
+void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, int iters, double* wz,
+                            double* part, hipStream_t s);
+void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s);
+void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
+                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s);

@@ -104,6 +104,163 @@ __global__ void k_collect_bin(const float* err, long n, int bin, float* out, uns
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Alignment modes beyond least squares (restated from /root/reference/metrics/eval_depth.py:59-204 and
+// metrics/alignment.py:170-195): optional clamps of the prediction before / after the alignment, the ratio of the (lower) medians,
+// the Weiszfeld L1 scale, and the per-pixel error map.  mask1 = gt > 0 && !(gt >= max_depth); max_depth = NaN switches the upper
+// bound off.  Clip bounds arrive as -inf / +inf when off, so the clamp is the identity.
+__device__ __forceinline__ bool depth_valid(float g, float max_depth) { return g > 0.f && !(g >= max_depth); }
+__device__ __forceinline__ float clipf(float p, float lo, float hi) { return fminf(fmaxf(p, lo), hi); }
+// order-preserving 32-bit key of a float: negative values have all bits flipped, the others only the sign bit (-0.0 sorts just below 0.0)
+__device__ __forceinline__ unsigned f32_key(float f) { const unsigned u = __float_as_uint(f); return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u); }
+__device__ __forceinline__ float key_f32(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
+
+// Exact masked selection: radix select of element (count - 1) / 2 of the sorted clamp(pred) and of the sorted gt over mask1, both in the
+// same passes, 8 key bits per pass from the top.  Select state in device memory (unsigned words, zeroed before pass 0):
+//   [(pass * 2 + a) * 256 + bin] histograms, a = 0 prediction / 1 ground truth; SEL_PREFIX + a the key bits fixed so far;
+//   SEL_RANK + a the rank still to find inside that prefix; SEL_COUNT the mask1 count; SEL_MED + a the selected float (bits).
+// (offsets in common.h.)  Counts are integers: the result does not depend on the order in which workgroups arrive.
+
+template <int PASS>
+__global__ __launch_bounds__(MB) void k_select_hist(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
+                                                    unsigned* sel) {
+  __shared__ unsigned h[2][256];
+  const int tid = threadIdx.x;
+  h[0][tid] = 0; h[1][tid] = 0;
+  __syncthreads();
+  constexpr int shift = 24 - 8 * PASS;
+  const unsigned pp = sel[SEL_PREFIX], pg = sel[SEL_PREFIX + 1];
+  for (long i = (long)blockIdx.x * MB + tid; i < n; i += (long)gridDim.x * MB) {
+    const float g = gt[i];
+    if (!depth_valid(g, max_depth)) continue;
+    const unsigned kp = f32_key(clipf(pred[i], lo, hi)), kg = f32_key(g);
+    if constexpr (PASS == 0) {
+      atomicAdd(&h[0][kp >> 24], 1u);
+      atomicAdd(&h[1][kg >> 24], 1u);
+    } else {
+      if ((kp >> (shift + 8)) == (pp >> (shift + 8))) atomicAdd(&h[0][(kp >> shift) & 255u], 1u);
+      if ((kg >> (shift + 8)) == (pg >> (shift + 8))) atomicAdd(&h[1][(kg >> shift) & 255u], 1u);
+    }
+  }
+  __syncthreads();
+  for (int a = 0; a < 2; ++a) {
+    const unsigned cnt = h[a][tid];
+    if (cnt) atomicAdd(&sel[(PASS * 2 + a) * 256 + tid], cnt);
+  }
+}
+
+// one workgroup: pick the bin that holds the wanted rank and the rank inside it; the last pass turns the finished key back into the float
+template <int PASS>
+__global__ __launch_bounds__(256) void k_select_scan(unsigned* sel) {
+  __shared__ unsigned sc[256];
+  const int tid = threadIdx.x;
+  constexpr int shift = 24 - 8 * PASS;
+  for (int a = 0; a < 2; ++a) {
+    const unsigned cnt = sel[(PASS * 2 + a) * 256 + tid];
+    sc[tid] = cnt;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const unsigned v = tid >= o ? sc[tid - o] : 0u;
+      __syncthreads();
+      sc[tid] += v;
+      __syncthreads();
+    }
+    const unsigned incl = sc[tid], excl = incl - cnt, total = sc[255];
+    const unsigned k = PASS == 0 ? (total ? (total - 1) / 2 : 0u) : sel[SEL_RANK + a];
+    __syncthreads();   // every thread has read the rank and sc[255] before one of them writes
+    if (PASS == 0 && a == 0 && tid == 0) sel[SEL_COUNT] = total;
+    if (cnt && excl <= k && k < incl) {
+      const unsigned prefix = sel[SEL_PREFIX + a] | ((unsigned)tid << shift);
+      sel[SEL_PREFIX + a] = prefix;
+      sel[SEL_RANK + a] = k - excl;
+      if (PASS == 3) sel[SEL_MED + a] = __float_as_uint(key_f32(prefix));
+    }
+  }
+}
+
+// Weiszfeld chain for the L1 scale: wz[0] = s, wz[1] = mask1 count.  INIT: partials of n, sum p, sum g -> s0 = mean(g) / mean(p);
+// otherwise w = 1 / (|s p - g| + 1e-8), partials of sum(w p g), sum(w p p) -> s.  fp64 throughout, fixed grid, fixed order.
+template <bool INIT>
+__global__ __launch_bounds__(MB) void k_wz_pass(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
+                                                const double* wz, double* part) {
+  __shared__ double sh[MB];
+  const double s = INIT ? 0.0 : wz[0];
+  double a[3] = {0, 0, 0};
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const float gf = gt[i];
+    if (!depth_valid(gf, max_depth)) continue;
+    const double p = clipf(pred[i], lo, hi), g = gf;
+    if (INIT) { a[0] += 1.0; a[1] += p; a[2] += g; }
+    else { const double w = 1.0 / (fabs(s * p - g) + 1e-8); a[0] += w * p * g; a[1] += w * p * p; }
+  }
+  for (int k = 0; k < 3; ++k) {
+    const double r = block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 3 + k] = r;
+  }
+}
+
+// one workgroup: the partials summed in block order by one thread, the next s written for the next pass
+template <bool INIT>
+__global__ __launch_bounds__(MB) void k_wz_reduce(const double* part, int nb, double* wz) {
+  __shared__ double sh[MAXB * 3];
+  for (int i = threadIdx.x; i < nb * 3; i += MB) sh[i] = part[i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a[3] = {0, 0, 0};
+    for (int b = 0; b < nb; ++b) for (int k = 0; k < 3; ++k) a[k] += sh[b * 3 + k];
+    if (INIT) { wz[1] = a[0]; wz[0] = (a[2] / a[0]) / (a[1] / a[0]); }
+    else wz[0] = a[0] / a[1];
+  }
+}
+
+// k_depth_fit on the pre-clipped prediction
+__global__ __launch_bounds__(MB) void k_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
+                                                     double* part) {
+  __shared__ double sh[MB];
+  double a[5] = {0, 0, 0, 0, 0};
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const float g = gt[i];
+    if (depth_valid(g, max_depth)) {
+      const double p = clipf(pred[i], lo, hi);
+      a[0] += 1.0; a[1] += p; a[2] += p * p; a[3] += g; a[4] += p * (double)g;
+    }
+  }
+  for (int k = 0; k < 5; ++k) {
+    const double r = block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + k] = r;
+  }
+}
+
+// k_depth_metrics of p' = clamp(s * clamp(p, lo, hi) + t, plo, phi); optional error map |s * pred + t - gt| / gt on mask1 (0 elsewhere) from
+// the ORIGINAL prediction.  The product and the sum round separately, as the reference's tensor expressions do: a fused multiply-add moves
+// the map by more than its tolerance where the residual is small.
+__global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n,
+                                                         float max_depth, float lo, float hi, float plo, float phi, float s, float t,
+                                                         double* part, float* emap) {
+  __shared__ double sh[MB];
+  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const float g = gt[i];
+    const bool v1 = depth_valid(g, max_depth);
+    const float p0 = pred[i];
+    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(__fadd_rn(__fmul_rn(p0, s), t), g)) / g : 0.f;
+    if (v1 && (!cmask || cmask[i])) {
+      const float p = clipf(__fadd_rn(__fmul_rn(s, clipf(p0, lo, hi)), t), plo, phi);
+      const float d = p - g;
+      a[0] += 1.0; a[1] += fabsf(d) / g; a[2] += d * d / g; a[3] += d * d;
+      const float pc = fmaxf(p, 1e-5f);
+      const float l = logf(pc) - logf(g);
+      a[4] += l * l;
+      const float r = fmaxf(pc / g, g / pc);
+      a[5] += r < 1.0f; a[6] += r < 1.25f; a[7] += r < 1.5625f; a[8] += r < 1.953125f;
+    }
+  }
+  for (int k = 0; k < 9; ++k) {
+    const double r = block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
+  }
+}
+
 static int nblocks(long n) { long b = (n + MB - 1) / MB; return (int)(b > MAXB ? MAXB : (b < 1 ? 1 : b)); }
 
 void launch_depth_fit(const float* pred, const float* gt, long n, float max_depth, double* part, int* nb, hipStream_t s) {
@@ -122,4 +279,38 @@ void launch_normal_err(const float* pn, const float* gn, const unsigned char* ma
 }
 void launch_collect_bin(const float* err, long n, int bin, float* out, unsigned* count, unsigned cap, hipStream_t s) {
   hipLaunchKernelGGL(k_collect_bin, dim3(nblocks(n)), dim3(MB), 0, s, err, n, bin, out, count, cap);
+}
+
+// the four histogram / scan pairs back to back on one stream: sel (SEL_WORDS unsigned words) ends with the count and the two medians
+void launch_masked_median(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* sel, hipStream_t s) {
+  (void)hipMemsetAsync(sel, 0, SEL_WORDS * sizeof(unsigned), s);
+  const dim3 g(nblocks(n)), b(MB);
+  hipLaunchKernelGGL(k_select_hist<0>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
+  hipLaunchKernelGGL(k_select_scan<0>, dim3(1), dim3(256), 0, s, sel);
+  hipLaunchKernelGGL(k_select_hist<1>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
+  hipLaunchKernelGGL(k_select_scan<1>, dim3(1), dim3(256), 0, s, sel);
+  hipLaunchKernelGGL(k_select_hist<2>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
+  hipLaunchKernelGGL(k_select_scan<2>, dim3(1), dim3(256), 0, s, sel);
+  hipLaunchKernelGGL(k_select_hist<3>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
+  hipLaunchKernelGGL(k_select_scan<3>, dim3(1), dim3(256), 0, s, sel);
+}
+// initial means + iters Weiszfeld steps, no host synchronisation in between: wz[0] = s, wz[1] = mask1 count; part holds MAXB * 3 doubles
+void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, int iters, double* wz,
+                            double* part, hipStream_t s) {
+  const int nb = nblocks(n);
+  hipLaunchKernelGGL(k_wz_pass<true>, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, wz, part);
+  hipLaunchKernelGGL(k_wz_reduce<true>, dim3(1), dim3(MB), 0, s, part, nb, wz);
+  for (int it = 0; it < iters; ++it) {
+    hipLaunchKernelGGL(k_wz_pass<false>, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, wz, part);
+    hipLaunchKernelGGL(k_wz_reduce<false>, dim3(1), dim3(MB), 0, s, part, nb, wz);
+  }
+}
+void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s) {
+  *nb = nblocks(n);
+  hipLaunchKernelGGL(k_depth_fit_ex, dim3(*nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, part);
+}
+void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
+                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s) {
+  *nb = nblocks(n);
+  hipLaunchKernelGGL(k_depth_metrics_ex, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
 }

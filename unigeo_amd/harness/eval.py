@@ -8,7 +8,7 @@ import importlib
 import os
 
 from .io_utils import prepare_gt_label
-from .metrics import MetricsManager, depth_evaluation, normal_evaluation
+from .metrics import DEPTH_ALIGNMENTS, MetricsManager, depth_evaluation, normal_evaluation
 
 
 def import_class_from_module(module_name, class_name):
@@ -33,6 +33,17 @@ def parse_metric_config(config):
     return names
 
 
+def parse_depth_eval_config(config):
+    """``eval_depth.depth_alignment`` (lstsq | median | scale | metric, default lstsq), optional ``max_depth`` and the four clip keys ->
+    (alignment, max_depth, clips).  An unknown alignment is a ``ValueError``."""
+    cfg = config.get("eval_depth") or {}
+    alignment = cfg.get("depth_alignment", "lstsq")
+    if alignment not in DEPTH_ALIGNMENTS:
+        raise ValueError(f"eval_depth.depth_alignment must be one of {list(DEPTH_ALIGNMENTS)}, not {alignment!r}")
+    clips = {k: cfg[k] for k in ("pre_clip_min", "pre_clip_max", "post_clip_min", "post_clip_max") if cfg.get(k) is not None}
+    return alignment, cfg.get("max_depth", 80), clips
+
+
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
              device_metrics=False, models=None):
     """Run the reference's per-clip loop.  With ``world > 1`` this rank only evaluates clips
@@ -41,7 +52,12 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     (``ug_eval_depth`` / ``ug_eval_normal``) instead of on the host copies.
     ``models`` = several instances of the plugin on ONE GPU (round 5): this rank's k-th clip runs on ``models[k % len(models)]``, each instance on its own host
     thread - independent clips in flight on one GPU, the sharding over GPUs one level down (+10 % aggregate frames/s with two DepthCrafter contexts: a second
-    clip fills the CUs that one clip's tile tails and under-filled launches leave idle).  Rows / CSV come out in dataset order, identical to the serial loop."""
+    clip fills the CUs that one clip's tile tails and under-filled launches leave idle).  Rows / CSV come out in dataset order, identical to the serial loop.
+    ``eval_depth.depth_alignment`` (lstsq | median | scale | metric, default lstsq), ``eval_depth.max_depth`` and the four ``eval_depth.*_clip_*`` keys select
+    the alignment of the depth metrics on both the host and the device path; an unknown value raises ``ValueError`` before the first clip runs.  A deliberate
+    difference: the reference reads ``depth_alignment`` (eval.py:48) and always aligns with least squares."""
+    alignment, max_depth, clips = parse_depth_eval_config(config)
+    host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
     if dataset is None:
         dataset = import_class_from_module("unigeo_amd.harness", config["dataset"])(**parse_dataset_config(config))
     if model is None and not models:
@@ -60,9 +76,9 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
         eng = getattr(getattr(mdl, "pipeline", None), "engine", None) if device_metrics else None
         if "eval_depth" in config:
             if eng is not None:
-                res = eng.eval_depth(gt["gt_depths"].numpy(), gt["gt_masks"].numpy())
+                res = eng.eval_depth(gt["gt_depths"].numpy(), gt["gt_masks"].numpy(), max_depth=max_depth, alignment=alignment, **clips)
             else:
-                res = depth_evaluation(output["pred_depths"], gt["gt_depths"], custom_mask=gt["gt_masks"], align_with_lstsq=True)
+                res = depth_evaluation(output["pred_depths"], gt["gt_depths"], max_depth=max_depth, custom_mask=gt["gt_masks"], **host_mode, **clips)
             metric.update(res[0])
         if "eval_normal" in config:
             if eng is not None:

@@ -2,12 +2,13 @@
 
 * ``depth_evaluation``  <- ``/root/reference/metrics/eval_depth.py:6-246`` restricted to the call the harness makes
   (``eval.py:49``: ``align_with_lstsq=True`` + ``custom_mask``): mask 0 < gt < 80, least-squares scale/shift
-  (``metrics/alignment.py:150-167``), then AbsRel / SqRel / RMSE / LogRMSE / delta thresholds on the custom mask.
+  (``metrics/alignment.py:150-167``), then AbsRel / SqRel / RMSE / LogRMSE / delta thresholds on the custom mask;
+  plus its median / L1-scale / metric alignment modes and the pre- and post-alignment clamps.
 * ``normal_evaluation`` <- ``/root/reference/metrics/eval_normal.py:4-72``: angular error in degrees, mean / median /
   rmse / % under 5, 7.5, 11.25, 22.5, 30 degrees.
 * ``MetricsManager``    <- ``/root/reference/metrics/save_utils.py:5-90``: one row per sequence, NaN for missing
   metrics, trailing ``Average`` row (NaN-skipping mean), ``%.5f``.
-Other alignment modes of the reference function are not used by the hot-path configs and raise here.
+The lad / lad2 / disp_input modes of the reference function raise here (see ``depth_evaluation``).
 """
 import math
 import os
@@ -21,19 +22,76 @@ def _np(x):
     return np.asarray(x)
 
 
+DEPTH_ALIGNMENTS = ("lstsq", "median", "scale", "metric")
+
+
+def _scale_l1(p, g):
+    """The reference's ``align_with_scale_torch`` (``metrics/alignment.py:170-195``) in float64, sums in plain index order
+    (``np.cumsum`` adds sequentially; ``np.sum`` would add pairwise).  The 1 / |residual| weights make the result move with
+    the summation order alone at clip size, hence the fixed order."""
+    p, g = p.astype(np.float64), g.astype(np.float64)
+    s = (np.cumsum(g)[-1] / g.size) / (np.cumsum(p)[-1] / p.size)
+    for _ in range(10):
+        w = 1.0 / (np.abs(s * p - g) + 1e-8)
+        s = np.cumsum(w * p * g)[-1] / np.cumsum(w * p * p)[-1]
+    return float(s)
+
+
 def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_depth=80, custom_mask=None,
-                     align_with_lstsq=False, **unsupported):
-    if not align_with_lstsq or any(v for v in unsupported.values()):
-        raise NotImplementedError("only align_with_lstsq=True (the mode eval.py uses) is restated")
+                     post_clip_min=None, post_clip_max=None, pre_clip_min=None, pre_clip_max=None,
+                     align_with_lstsq=False, align_with_lad=False, align_with_lad2=False, metric_scale=False,
+                     align_with_scale=False, disp_input=False, lr=1e-4, max_iters=1000, use_gpu=False, return_error_map=False,
+                     **unsupported):
+    """``depth_evaluation`` of the reference (``metrics/eval_depth.py:59-204``) -> ``(res, (s, t))``, with
+    ``return_error_map=True`` ``(res, (s, t), error_map)``.
+
+    On mask1 = ``gt > 0`` (and ``gt < max_depth`` unless that is ``None``): clamp the prediction to the pre-clip bounds,
+    align, clamp to the post-clip bounds, apply the custom mask, compute the metrics.  The alignment keeps the
+    reference's precedence: ``metric_scale`` (s = 1), then ``align_with_lstsq`` (scale and shift), then
+    ``align_with_scale`` (Weiszfeld L1 scale, here in float64 and plain index order; clamped to >= 1e-3), then the
+    default: ``s = median(gt) / median(pred)`` with ``torch.median``'s LOWER median, element ``(n - 1) // 2`` of the
+    sorted values.  The error map is ``|s * pred + t - gt| / gt`` on mask1 and 0 elsewhere, from the ORIGINAL prediction
+    (neither clamp applied), as the reference computes it.  No valid pixel: zero metrics and ``(s, t) = (1, 0)`` under
+    ``metric_scale``, ``(0, 0)`` otherwise.
+
+    Still rejected with ``NotImplementedError``: ``align_with_lad`` / ``align_with_lad2`` run a scipy BFGS and a
+    1000-step Adam on a non-smooth objective, which gives no reproducible answer; ``disp_input`` calls ``depth2disparity``,
+    which the reference defines nowhere, so its own call raises ``NameError``.  ``lr`` / ``max_iters`` (lad2 only) and
+    ``use_gpu`` (tensor placement) are accepted and have no effect.
+    """
+    if align_with_lad or align_with_lad2 or disp_input or any(v for v in unsupported.values()):
+        raise NotImplementedError("align_with_lad / align_with_lad2 (no reproducible optimum) and disp_input (undefined in the "
+                                  "reference) are not restated")
+    f32 = np.float32
     pred = _np(predicted_depth_original).astype(np.float32).reshape(-1)
     gt = _np(ground_truth_depth_original).astype(np.float32).reshape(-1)
     cm = None if custom_mask is None else _np(custom_mask).astype(bool).reshape(-1)
     mask = (gt > 0) & (gt < max_depth) if max_depth is not None else gt > 0
     p, g = pred[mask], gt[mask]
-    A = np.stack([p, np.ones_like(p)], 1)
-    sol = np.linalg.lstsq(A, g[:, None], rcond=None)[0]
-    s, t = np.float32(sol[0, 0]), np.float32(sol[1, 0])
+    if pre_clip_min is not None:
+        p = np.maximum(p, f32(pre_clip_min))
+    if pre_clip_max is not None:
+        p = np.minimum(p, f32(pre_clip_max))
+    if metric_scale:
+        s, t = f32(1), f32(0)
+    elif align_with_lstsq:
+        A = np.stack([p, np.ones_like(p)], 1)
+        sol = np.linalg.lstsq(A, g[:, None], rcond=None)[0]
+        s, t = f32(sol[0, 0]), f32(sol[1, 0])
+    elif p.size == 0:
+        s, t = f32(0), f32(0)
+    elif align_with_scale:
+        s, t = max(_scale_l1(p, g), 1e-3), f32(0)
+    else:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s, t = np.sort(g)[(g.size - 1) // 2] / np.sort(p)[(p.size - 1) // 2], f32(0)
+    s_ret = float(s)
+    s = f32(s)
     p = s * p + t
+    if post_clip_min is not None:
+        p = np.maximum(p, f32(post_clip_min))
+    if post_clip_max is not None:
+        p = np.minimum(p, f32(post_clip_max))
     if cm is not None:
         sel = cm[mask]
         p, g = p[sel], g[sel]
@@ -41,7 +99,6 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
     if n == 0:
         vals = [0, 0, 0, 0, 0, 0, 0, 0]
     else:
-        f32 = np.float32
         abs_rel = float(np.mean(np.abs(p - g) / g, dtype=f32))
         sq_rel = float(np.mean((p - g) ** 2 / g, dtype=f32))
         rmse = float(np.sqrt(np.mean((p - g) ** 2, dtype=f32)))
@@ -53,7 +110,11 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
     keys = ["Abs Rel", "Sq Rel", "RMSE", "Log RMSE", "delta < 1.", "delta < 1.25", "delta < 1.25^2", "delta < 1.25^3"]
     res = dict(zip(keys, vals))
     res["valid_pixels"] = n
-    return res, (float(s), float(t))
+    if not return_error_map:
+        return res, (s_ret, float(t))
+    emap = np.zeros(gt.shape, f32)
+    emap[mask] = np.abs((pred[mask] * s + t) - gt[mask]) / gt[mask]
+    return res, (s_ret, float(t)), emap.reshape(np.shape(_np(ground_truth_depth_original)))
 
 
 def normal_evaluation(predicted_normal_original, ground_truth_normal_original, custom_mask=None):
