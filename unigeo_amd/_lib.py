@@ -60,6 +60,16 @@ DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_AL
 _lib = None
 
 
+def _set_argtypes(lib, table):
+    """argtypes of entry points that an explicitly selected OLDER build (UG_LIB_PATH, tools/ab A/B runs) may lack, one call per group that arrived together; the in-tree build must have them."""
+    try:
+        for name, argtypes in table.items():
+            getattr(lib, name).argtypes = argtypes
+    except AttributeError:
+        if not os.environ.get("UG_LIB_PATH"):
+            raise
+
+
 def load_library():
     """dlopen the in-tree library; raises (never falls back) when it is absent."""
     global _lib
@@ -88,21 +98,17 @@ def load_library():
     lib.ug_dc_get_outputs.argtypes = [vp, vp, vp, vp]
     lib.ug_dc_set_trace.argtypes = [vp, vp, ip]
     lib.ug_set_vae_encode_fp32.argtypes = [vp, ip]
-    try:
-        lib.ug_set_fp8_linears.argtypes = [vp, ip]
-        lib.ug_set_concurrency.argtypes = [vp, ip]
-        lib.ug_set_coscheduled.argtypes = [vp, ip]
-        lib.ug_set_ff_fused.argtypes = [vp, ip]
-        lib.ug_bench_ff.argtypes = [vp, ip, ip, ip, ip, vp]
-        lib.ug_bench_flash.argtypes = [vp, ip, ip, ip, ip, ip, vp]
-        lib.ug_tune_flash.argtypes = [vp, ip]
-        lib.ug_tune_ff.argtypes = [vp, ip]
-        lib.ug_op_ff.argtypes = [vp, vp, ip, ip, vp, vp, vp, vp, vp, C.c_float, C.c_float, ip, vp]
-        lib.ug_op_ln_ff.argtypes = [vp, vp, ip, ip, vp, vp, C.c_float, vp, ip, vp, vp, vp, vp, C.c_float, C.c_float, ip, vp]
-        lib.ug_op_linear_mx8.argtypes = [vp, vp, ip, ip, vp, ip, vp, ip, vp, vp, vp]
-    except AttributeError:
-        if not os.environ.get("UG_LIB_PATH"):      # only an explicitly selected OLDER build (tools/ab A/B runs) may lack these
-            raise
+    _set_argtypes(lib, {
+        "ug_set_fp8_linears": [vp, ip], "ug_set_concurrency": [vp, ip], "ug_set_coscheduled": [vp, ip], "ug_set_ff_fused": [vp, ip],
+        "ug_bench_ff": [vp, ip, ip, ip, ip, vp], "ug_bench_flash": [vp, ip, ip, ip, ip, ip, vp], "ug_tune_flash": [vp, ip], "ug_tune_ff": [vp, ip],
+        "ug_op_ff": [vp, vp, ip, ip, vp, vp, vp, vp, vp, C.c_float, C.c_float, ip, vp],
+        "ug_op_ln_ff": [vp, vp, ip, ip, vp, vp, C.c_float, vp, ip, vp, vp, vp, vp, C.c_float, C.c_float, ip, vp],
+        "ug_op_linear_mx8": [vp, vp, ip, ip, vp, ip, vp, ip, vp, vp, vp]})
+    _set_argtypes(lib, {"ug_dc_set_guidance": [vp, C.c_float], "ug_unet_forward_pair": [vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp, vp]})
+    _set_argtypes(lib, {
+        "ug_dc_set_inputs_ex": [vp, vp, ip, ip, ip, ip, vp, vp, C.c_uint64, vp], "ug_dc_get_noise": [vp, vp, vp],
+        "ug_op_philox_u32": [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_long, vp],
+        "ug_op_randn": [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_long, C.c_long, vp], "ug_op_u8_to_frames": [vp, vp, ip, ip, ip, vp]})
     lib.ug_dc_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.ug_eval_depth.argtypes = [vp, vp, vp, vp, C.c_long, C.c_float, vp]
     lib.ug_eval_normal.argtypes = [vp, vp, vp, vp, C.c_long, vp]
@@ -114,21 +120,6 @@ def load_library():
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_unet_forward.argtypes = [vp, vp, ip, ip, ip, C.c_float, vp, vp]
-    try:
-        lib.ug_dc_set_guidance.argtypes = [vp, C.c_float]
-        lib.ug_unet_forward_pair.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, C.c_float, vp, vp]
-    except AttributeError:
-        if not os.environ.get("UG_LIB_PATH"):      # an explicitly selected OLDER build (tools/ab A/B runs) may lack these
-            raise
-    try:
-        lib.ug_dc_set_inputs_ex.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp, C.c_uint64, vp]
-        lib.ug_dc_get_noise.argtypes = [vp, vp, vp]
-        lib.ug_op_philox_u32.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_long, vp]
-        lib.ug_op_randn.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_long, C.c_long, vp]
-        lib.ug_op_u8_to_frames.argtypes = [vp, vp, ip, ip, ip, vp]
-    except AttributeError:
-        if not os.environ.get("UG_LIB_PATH"):      # an explicitly selected OLDER build (tools/ab A/B runs) may lack these
-            raise
     lib.ug_normals_from_depth.argtypes = [vp, vp, vp, ip, ip, ip, vp]
     lib.ug_op_linear.argtypes = [vp, vp, ip, ip, vp, ip, vp, vp, C.c_float, C.c_float, ip, ip, vp]
     lib.ug_op_conv.argtypes = [vp, vp, ip, vp, ip, ip, ip, ip, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp]
@@ -150,6 +141,7 @@ def load_library():
     lib.ug_profile_begin.argtypes = [vp]
     lib.ug_bench_gemm.argtypes = [vp] + [ip] * 16 + [vp]
     lib.ug_bench_groupnorm.argtypes = [vp, ip, ip, ip, ip, ip, ip, ip, vp]
+    lib.ug_bench_mfma_peak.argtypes = [vp, ip, vp]
     lib.ug_tune_force.argtypes = [vp, ip, ip]
     lib.ug_profile_begin_shapes.argtypes = [vp]
     lib.ug_profile_end.restype = C.c_char_p
@@ -169,6 +161,39 @@ def _ptr(a):
 def _fill8(dst, vals):
     for i in range(8):
         dst[i] = int(vals[i]) if i < len(vals) else 0
+
+
+def _unet_c(cfg):
+    """ug_unet_config of a UNet config object; a StableNormal (SD) config lacks the SVD-only attributes, which go over as 0."""
+    c = UNetConfigC()
+    c.in_channels, c.out_channels, c.num_levels = cfg.in_channels, cfg.out_channels, len(cfg.block_out_channels)
+    _fill8(c.block_out_channels, cfg.block_out_channels)
+    _fill8(c.num_attention_heads, cfg.num_attention_heads)
+    _fill8(c.down_has_attn, [int(b) for b in cfg.down_has_attn])
+    c.layers_per_block, c.cross_attention_dim, c.norm_groups = cfg.layers_per_block, cfg.cross_attention_dim, cfg.norm_groups
+    for name in ("addition_time_embed_dim", "projection_class_embeddings_input_dim",
+                 "eps_cross_attn_blocks", "eps_plain_down_block", "eps_mid_block", "eps_up_blocks"):
+        setattr(c, name, getattr(cfg, name, 0))
+    return c
+
+
+def _vae_c(cfg):
+    c = VAEConfigC()
+    c.in_channels, c.out_channels, c.latent_channels = cfg.in_channels, cfg.out_channels, cfg.latent_channels
+    c.num_levels = len(cfg.block_out_channels)
+    _fill8(c.block_out_channels, cfg.block_out_channels)
+    c.layers_per_block, c.norm_groups, c.scaling_factor = cfg.layers_per_block, cfg.norm_groups, cfg.scaling_factor
+    return c
+
+
+def _clip_c(cfg):
+    """ug_clip_config of a CLIP / DINOv2 tower config; a DINOv2 config has no projection_dim (0)."""
+    c = CLIPConfigC()
+    c.hidden_size, c.intermediate_size = cfg.hidden_size, cfg.intermediate_size
+    c.num_hidden_layers, c.num_attention_heads = cfg.num_hidden_layers, cfg.num_attention_heads
+    c.image_size, c.patch_size, c.layer_norm_eps = cfg.image_size, cfg.patch_size, cfg.layer_norm_eps
+    c.projection_dim = getattr(cfg, "projection_dim", 0)
+    return c
 
 
 class Engine:
@@ -211,55 +236,20 @@ class Engine:
             self._ck(self.lib.ug_load_tensor(self.ctx, (prefix + name).encode(), dt, max(a.ndim, 1), shape, _ptr(a)))
 
     def bind_unet(self, cfg):
-        c = UNetConfigC()
-        c.in_channels, c.out_channels = cfg.in_channels, cfg.out_channels
-        c.num_levels = len(cfg.block_out_channels)
-        _fill8(c.block_out_channels, cfg.block_out_channels)
-        _fill8(c.num_attention_heads, cfg.num_attention_heads)
-        _fill8(c.down_has_attn, [int(b) for b in cfg.down_has_attn])
-        c.layers_per_block, c.cross_attention_dim = cfg.layers_per_block, cfg.cross_attention_dim
-        c.addition_time_embed_dim = cfg.addition_time_embed_dim
-        c.projection_class_embeddings_input_dim = cfg.projection_class_embeddings_input_dim
-        c.norm_groups = cfg.norm_groups
-        c.eps_cross_attn_blocks, c.eps_plain_down_block = cfg.eps_cross_attn_blocks, cfg.eps_plain_down_block
-        c.eps_mid_block, c.eps_up_blocks = cfg.eps_mid_block, cfg.eps_up_blocks
-        self._ck(self.lib.ug_bind_unet(self.ctx, C.byref(c)))
+        self._ck(self.lib.ug_bind_unet(self.ctx, C.byref(_unet_c(cfg))))
         self.unet_cfg = cfg
 
     def bind_vae(self, cfg):
-        c = VAEConfigC()
-        c.in_channels, c.out_channels, c.latent_channels = cfg.in_channels, cfg.out_channels, cfg.latent_channels
-        c.num_levels = len(cfg.block_out_channels)
-        _fill8(c.block_out_channels, cfg.block_out_channels)
-        c.layers_per_block, c.norm_groups, c.scaling_factor = cfg.layers_per_block, cfg.norm_groups, cfg.scaling_factor
-        self._ck(self.lib.ug_bind_vae(self.ctx, C.byref(c)))
+        self._ck(self.lib.ug_bind_vae(self.ctx, C.byref(_vae_c(cfg))))
         self.vae_cfg = cfg
 
     def bind_clip(self, cfg):
-        c = CLIPConfigC()
-        c.hidden_size, c.intermediate_size = cfg.hidden_size, cfg.intermediate_size
-        c.num_hidden_layers, c.num_attention_heads = cfg.num_hidden_layers, cfg.num_attention_heads
-        c.image_size, c.patch_size, c.projection_dim = cfg.image_size, cfg.patch_size, cfg.projection_dim
-        c.layer_norm_eps = cfg.layer_norm_eps
-        self._ck(self.lib.ug_bind_clip(self.ctx, C.byref(c)))
+        self._ck(self.lib.ug_bind_clip(self.ctx, C.byref(_clip_c(cfg))))
         self.clip_cfg = cfg
 
     # ---- StableNormal
     def bind_stablenormal(self, ucfg, vcfg, dcfg):
-        u = UNetConfigC()
-        u.in_channels, u.out_channels, u.num_levels = ucfg.in_channels, ucfg.out_channels, len(ucfg.block_out_channels)
-        _fill8(u.block_out_channels, ucfg.block_out_channels); _fill8(u.num_attention_heads, ucfg.num_attention_heads)
-        _fill8(u.down_has_attn, [int(b) for b in ucfg.down_has_attn])
-        u.layers_per_block, u.cross_attention_dim, u.norm_groups = ucfg.layers_per_block, ucfg.cross_attention_dim, ucfg.norm_groups
-        v = VAEConfigC()
-        v.in_channels, v.out_channels, v.latent_channels = vcfg.in_channels, vcfg.out_channels, vcfg.latent_channels
-        v.num_levels = len(vcfg.block_out_channels)
-        _fill8(v.block_out_channels, vcfg.block_out_channels)
-        v.layers_per_block, v.norm_groups, v.scaling_factor = vcfg.layers_per_block, vcfg.norm_groups, vcfg.scaling_factor
-        d = CLIPConfigC()
-        d.hidden_size, d.intermediate_size, d.num_hidden_layers = dcfg.hidden_size, dcfg.intermediate_size, dcfg.num_hidden_layers
-        d.num_attention_heads, d.image_size, d.patch_size, d.layer_norm_eps = dcfg.num_attention_heads, dcfg.image_size, dcfg.patch_size, dcfg.layer_norm_eps
-        self._ck(self.lib.ug_bind_stablenormal(self.ctx, C.byref(u), C.byref(v), C.byref(d)))
+        self._ck(self.lib.ug_bind_stablenormal(self.ctx, C.byref(_unet_c(ucfg)), C.byref(_vae_c(vcfg)), C.byref(_clip_c(dcfg))))
         self.sn_cfgs = (ucfg, vcfg, dcfg)
 
     def sn_run(self, images, prompt_embeds, yoso_t, timesteps, ca, cb):
@@ -649,7 +639,6 @@ class Engine:
     def bench_mfma_peak(self, iters=20000):
         """Calibration: chip-wide fp16 MFMA TFLOP/s with operands in registers (kernels/probe.hip)."""
         out = np.zeros(1, np.float32)
-        self.lib.ug_bench_mfma_peak.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         self._ck(self.lib.ug_bench_mfma_peak(self.ctx, int(iters), _ptr(out)))
         return float(out[0])
 

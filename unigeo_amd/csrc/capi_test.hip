@@ -1,0 +1,651 @@
+// extern "C" surface of libunigeo_hip.so, test half: exactly the functions declared in include/unigeo_hip_test.h - stage- and op-level entry points
+// of the parity tests (host in / host out), tuning overrides and micro-benchmarks.  The drop-in boundary is capi.hip.
+#include "capi_util.h"
+
+// ------------------------------------------------------------------ weight layouts, as the engine binds them
+// W [N][K] / b [N] (b may be NULL: bp stays empty) in the engine's GEGLU row order: blocks of 16 rows = [8 value | 8 gate] (geglu_src_row, bind_geglu)
+static void pack_geglu(const float* W, const float* b, int N, int K, std::vector<float>& Wp, std::vector<float>& bp) {
+  Wp.resize((size_t)N * K); if (b) bp.resize(N);
+  for (int v = 0; v < N; ++v) {
+    const int src = geglu_src_row(v, N / 2);
+    memcpy(&Wp[(size_t)v * K], &W[(size_t)src * K], (size_t)K * 4);
+    if (b) bp[v] = b[src];
+  }
+}
+// weight [O][I][taps] -> the GEMM's K order: [O][taps][I] (tap-major), or chunk-major [O][I/64][taps][64] (GemmP::kchunk, I % 64 == 0)
+static std::vector<float> pack_conv_weight(const float* weight, int O, int I, int taps, bool chunk_major) {
+  std::vector<float> wp((size_t)O * taps * I);
+  for (int o = 0; o < O; ++o) for (int i = 0; i < I; ++i) for (int tp = 0; tp < taps; ++tp)
+    wp[chunk_major ? (((size_t)o * (I / 64) + i / 64) * taps + tp) * 64 + i % 64 : ((size_t)o * taps + tp) * I + i] = weight[((size_t)o * I + i) * taps + tp];
+  return wp;
+}
+
+// ------------------------------------------------------------------ GEMM parameter blocks
+static GemmP blank_gemm(Ctx& c) {
+  GemmP p; memset(&p, 0, sizeof(p));
+  p.zero = c.zero; p.nb_inner = 1; p.c0 = 1.f;
+  return p;
+}
+// Out[M][ldo] = A[M][K] W[N][K]^T + bias
+static GemmP dense_gemm(Ctx& c, const f16* A, int M, int K, const f16* W, int N, const f16* bias, f16* Out, long ldo) {
+  GemmP p = blank_gemm(c);
+  p.A0 = A; p.C0 = K; p.M = M; p.N = N; p.K = K; p.W = W; p.ldw = K; p.bias = bias; p.Out = Out; p.ldo = ldo;
+  return p;
+}
+// implicit-GEMM convolution of one / two channels-last sources [T][H][W][C0 | C1], (kt, k, k) taps, O output channels
+static GemmP conv_gemm(Ctx& c, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int kt, int k, int stride, int pad_t, int pad_l, int ups,
+                       const f16* Wt, int O, const f16* bias, f16* Out) {
+  GemmP p = blank_gemm(c);
+  p.conv = 1; p.A0 = x0; p.A1 = x1; p.C0 = C0; p.C1 = C1; p.T = T; p.Hi = H; p.Wi = W; p.Ho = H * ups / stride; p.Wo = W * ups / stride;
+  p.ups = ups; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l; p.kt = kt; p.ky = k; p.kx = k;
+  p.M = T * p.Ho * p.Wo; p.N = O; p.K = (C0 + C1) * kt * k * k; p.W = Wt; p.ldw = p.K; p.bias = bias; p.Out = Out; p.ldo = O;
+  return p;
+}
+// the context's tuning overrides, then the planner's tile config and split-K factor (+ the split-K scratch, from c.ws)
+static void plan_gemm(Ctx& c, GemmP& p) {
+  gemm_apply_tune(p, c.tune);
+  int cf, sp;
+  gemm_plan(p, 1, &cf, &sp);
+  p.cfg_p1 = cf + 1; p.splitk = sp;
+  if (sp > 1) p.partial = c.ws.get<float>((long)sp * p.M * p.N);
+}
+// the unfused feed-forward: mid = GEGLU(X W1^T + b1) [M][4C], Out = c0 * (mid W2^T + b2) + c1 * res.  Not planned: the launcher picks the first GEMM's
+// tile and split (splitk = 0), the down-projection runs unsplit.
+static void ff_two_launch(Ctx& c, const f16* X, int M, int C, const f16* W1, const f16* b1, const f16* W2, const f16* b2, const f16* res, float c0, float c1,
+                          f16* mid, f16* Out) {
+  const int I = 4 * C;
+  GemmP g1 = dense_gemm(c, X, M, C, W1, 2 * I, b1, mid, I);
+  g1.flags = UG_F_GEGLU;
+  gemm_apply_tune(g1, c.tune); launch_gemm(g1, 1, c.stream);
+  GemmP g2 = dense_gemm(c, mid, M, I, W2, C, b2, Out, C);
+  g2.c0 = c0; g2.R1 = res; g2.ldr1 = C; g2.c1 = c1; g2.splitk = 1;
+  gemm_apply_tune(g2, c.tune); launch_gemm(g2, 1, c.stream);
+}
+static FFusedP ff_fused(Ctx& c, const f16* X, int M, int C, const f16* W1, const f16* b1, const f16* W2, const f16* b2, const f16* res, float c0, float c1, f16* Out) {
+  FFusedP p; memset(&p, 0, sizeof(p));
+  p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.R1 = res; p.c0 = c0; p.c1 = c1; p.Out = Out; p.M = M; p.C = C; p.zero = c.zero; p.variant = c.ff_variant;
+  return p;
+}
+
+// ------------------------------------------------------------------ timing
+struct Event {     // destroyed on every way out of its scope, a throwing UG_CHECK included
+  hipEvent_t e = nullptr;
+  Event() { UG_CHECK(hipEventCreate(&e)); }
+  ~Event() { (void)hipEventDestroy(e); }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+};
+// `warm` untimed launches, then the time of `iters` launches together, in milliseconds; launch(i) enqueues timed launch i on c.stream (warm-up: i = 0)
+template <class Fn> static float time_launches_ms(Ctx& c, int warm, int iters, Fn&& launch) {
+  for (int i = 0; i < warm; ++i) launch(0);
+  Event e0, e1;
+  UG_CHECK(hipEventRecord(e0.e, c.stream));
+  for (int i = 0; i < iters; ++i) launch(i);
+  UG_CHECK(hipEventRecord(e1.e, c.stream));
+  UG_CHECK(hipEventSynchronize(e1.e));
+  float ms = 0.f;
+  UG_CHECK(hipEventElapsedTime(&ms, e0.e, e1.e));
+  return ms;
+}
+
+// [px][3] float host -> [px][8] f16 device (channels 3 .. 7 zero): the VAE encoders' input
+static f16* upload_rgb_pad8(Ctx& c, const float* video, long px) {
+  std::vector<f16> v((size_t)px * 8, (f16)0.f);
+  for (long p = 0; p < px; ++p) for (int ch = 0; ch < 3; ++ch) v[p * 8 + ch] = (f16)video[p * 3 + ch];
+  f16* d = c.ws.get<f16>(px * 8);
+  UG_CHECK(hipMemcpy(d, v.data(), v.size() * 2, hipMemcpyHostToDevice));
+  return d;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------ per-context switches and overrides
+int ug_set_ff_fused(ug_ctx* x, int on) {
+  if (!x) return -1;
+  x->c.ff_fused = on & 3; x->c.lane_need.clear();   // bit 0: fused feed-forward kernel, bit 1: its pre-LayerNorm inside the kernel (a feature toggle changes the transient memory a lane task needs)
+  return 0;
+}
+int ug_dc_set_trace(ug_ctx* x, float* host_latents, int steps) {
+  if (!x) return -1;
+  x->c.trace_host = host_latents; x->c.trace_steps = host_latents ? steps : 0;
+  return 0;
+}
+int ug_profile_begin_shapes(ug_ctx* x) { UG_TRY(x, prof_begin(x->c, true)); }
+int ug_tune_force(ug_ctx* x, int cfg, int split) {
+  if (!x) return -1;
+  if (cfg <= -100) {                                         // knob mask: ug_tune_force(ctx, -100 - knobs, 0)
+    x->c.tune.knobs = (-cfg - 100) & ~4194304;
+    if (x->c.cosched) x->c.tune.knobs |= 4194304;            // the co-scheduled planner rule belongs to ug_set_coscheduled alone: a forced mask neither sets nor drops it
+  }
+  else { x->c.tune.cfg = cfg; x->c.tune.split = split; }
+  x->c.lane_need.clear();    // forced split-K / tile configs change the partial buffers a lane task needs
+  return 0;
+}
+int ug_tune_flash(ug_ctx* x, int variant) { if (!x) return -1; x->c.flash_variant = variant; return 0; }
+int ug_tune_ff(ug_ctx* x, int variant) { if (!x) return -1; x->c.ff_variant = variant; x->c.lane_need.clear(); return 0; }
+
+// ------------------------------------------------------------------ stage level
+int ug_clip_embed(ug_ctx* x, const float* frames, int T, int H, int W, float* emb_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const long px = (long)T * H * W;
+    float* df = c.ws.get<float>(px * 3); float* dn = c.ws.get<float>(px * 3);
+    UG_CHECK(hipMemcpy(df, frames, px * 3 * 4, hipMemcpyHostToDevice));
+    UG_CHECK(hipMemsetAsync(dn, 0, px * 3 * 4, c.stream));
+    f16* src = c.ws.get<f16>(px * 3); f16* vin = c.ws.get<f16>(px * 8);
+    launch_prep_video(df, dn, src, vin, T, H, W, 0.f, c.stream);
+    f16* e = clip_embed(c, src, T, H, W);
+    down16(c, e, emb_out, (long)T * c.clip.cfg.proj);
+  });
+}
+
+int ug_vae_encode(ug_ctx* x, const float* video, int T, int H, int W, float* lat_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    f16* l = vae_encode(c, upload_rgb_pad8(c, video, (long)T * H * W), T, H, W);
+    down_nchw(c, l, lat_out, T, c.vae.cfg.lat, H / 8, W / 8);
+  });
+}
+
+int ug_vae_decode(ug_ctx* x, const float* z, int T, int h, int w, float* frames_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    f16* dz = up_nchw(c, z, T, c.vae.cfg.lat, h, w, c.vae.cfg.lat);
+    const long px = (long)T * h * 8 * w * 8;
+    float* out = c.ws.get<float>(px * 3);
+    vae_decode(c, dz, T, h, w, out);
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(frames_out, out, px * 3 * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int ug_unet_forward(ug_ctx* x, const float* sample, int T, int h, int w, float timestep, const float* clip_emb, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const UNetCfg& g = c.unet.cfg;
+    f16* dx = up_nchw(c, sample, T, g.in_ch, h, w, g.in_ch);
+    f16* de = up16(c, clip_emb, (long)T * g.cross_dim);
+    unet_prepare(c, T, de, &timestep, 1);
+    f16* y = unet_forward(c, dx, T, h, w, 0);
+    down_nchw(c, y, out, T, g.out_ch, h, w);
+  });
+}
+
+// one batched UNet pass over two videos stacked [2][T] (the classifier-free-guidance pass of ug_dc_run, without the combine)
+int ug_unet_forward_pair(ug_ctx* x, const float* sample_a, const float* emb_a, const float* sample_b, const float* emb_b, int T, int h, int w,
+                         float timestep, float* out_a, float* out_b) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const UNetCfg& g = c.unet.cfg;
+    UG_REQUIRE(sample_a && emb_a && sample_b && emb_b && out_a && out_b && T >= 1, "ug_unet_forward_pair: null buffer / no frames");
+    const long ns = (long)T * h * w * g.in_ch, ne = (long)T * g.cross_dim;
+    f16* dx = c.ws.get<f16>(2 * ns);
+    f16* de = c.ws.get<f16>(2 * ne);
+    const float* smp[2] = {sample_a, sample_b};
+    const float* emb[2] = {emb_a, emb_b};
+    for (int v = 0; v < 2; ++v) {     // straight into the stacked [2][T] buffers
+      upload_nchw(smp[v], T, g.in_ch, h, w, g.in_ch, dx + v * ns);
+      upload16(emb[v], ne, de + v * ne);
+    }
+    unet_prepare(c, T, de, &timestep, 1, 2);
+    f16* y = unet_forward(c, dx, T, h, w, 0, 2);
+    const long no = (long)T * h * w * g.out_ch;
+    down_nchw(c, y, out_a, T, g.out_ch, h, w);
+    down_nchw(c, y + no, out_b, T, g.out_ch, h, w);
+  });
+}
+
+// ------------------------------------------------------------------ StableNormal stages
+int ug_sn_unet_forward(ug_ctx* x, int which, const float* sample, const float* zimg, int B, int h, int w, float t_unet, float t_ctrl,
+                       const float* prompt, const float* dino_tokens, int use_ctrl, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    SN& s = c.sn;
+    UG_REQUIRE(s.bound, "StableNormal weights are not bound");
+    f16* ds = up_nchw(c, sample, B, 4, h, w, 4);
+    f16* dz = zimg ? up_nchw(c, zimg, B, 4, h, w, 4) : nullptr;
+    f16* dp = up16(c, prompt, 77L * s.cfg.cross_dim);
+    const int g = s.dino.cfg.image / s.dino.cfg.patch;
+    f16* dt = dino_tokens ? up16(c, dino_tokens, (long)B * g * g * s.dino.cfg.hidden) : nullptr;
+    UG_REQUIRE(!use_ctrl || dz, "ControlNet evaluation needs the image latent");
+    f16* y = sn_unet_eval(c, which, ds, dz, B, h, w, t_unet, t_ctrl, dp, dt, use_ctrl);
+    down_nchw(c, y, out, B, 4, h, w);
+  });
+}
+int ug_sn_dino(ug_ctx* x, const float* images01, int B, int H, int W, float* tokens_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const long px = (long)B * H * W;
+    float* df = c.ws.get<float>(px * 3);
+    UG_CHECK(hipMemcpy(df, images01, px * 3 * 4, hipMemcpyHostToDevice));
+    f16* src = c.ws.get<f16>(px * 3); f16* vin = c.ws.get<f16>(px * 8);
+    launch_prep_video(df, df, src, vin, B, H, W, 0.f, c.stream);
+    f16* t = sn_dino_tokens(c, src, B, H, W);
+    const int g = c.sn.dino.cfg.image / c.sn.dino.cfg.patch;
+    down16(c, t, tokens_out, (long)B * g * g * c.sn.dino.cfg.hidden);
+  });
+}
+int ug_sn_vae_decode(ug_ctx* x, const float* z, int B, int h, int w, float* out_bhwc) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    f16* dz = up_nchw(c, z, B, 4, h, w, 4);
+    f16* rgb = sn_vae_decode(c, dz, B, h, w);
+    const long px = (long)B * h * 8 * w * 8;
+    std::vector<f16> v((size_t)px * 8);
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(v.data(), rgb, v.size() * 2, hipMemcpyDeviceToHost));
+    for (long p = 0; p < px; ++p) for (int ch = 0; ch < 3; ++ch) out_bhwc[p * 3 + ch] = (float)v[p * 8 + ch];
+  });
+}
+int ug_sn_vae_encode(ug_ctx* x, const float* video, int B, int H, int W, float* lat_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    f16* l = vae_encode_v(c, c.sn.vae, upload_rgb_pad8(c, video, (long)B * H * W), B, H, W, false);
+    down_nchw(c, l, lat_out, B, c.sn.vae.cfg.lat, H / 8, W / 8);
+  });
+}
+
+// ------------------------------------------------------------------ op level
+int ug_op_masked_median(ug_ctx* x, const float* pred, const float* gt, long n, float max_depth, float pre_clip_min, float pre_clip_max,
+                        float* out_medians, long* out_count) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(n >= 1 && n < (1L << 32), "pixel count");
+    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, nullptr, n);
+    unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
+    launch_masked_median(d.dp, d.dg, n, depth_bound(max_depth), clip_lo(pre_clip_min), clip_hi(pre_clip_max), sel, c.stream);
+    unsigned cnt;
+    read_masked_median(c, sel, cnt, out_medians[0], out_medians[1]);
+    *out_count = (long)cnt;
+  });
+}
+
+int ug_op_linear(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, const float* R1,
+                 float c0, float c1, int act, int geglu, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    std::vector<float> Wp, bp;
+    if (geglu) { pack_geglu(W, bias, N, K, Wp, bp); W = Wp.data(); if (bias) bias = bp.data(); }
+    const int Nout = geglu ? N / 2 : N;
+    f16* dA = up16(c, A, (long)M * K); f16* dW = up16(c, W, (long)N * K);
+    f16* db = up16_opt(c, bias, N); f16* dR = up16_opt(c, R1, (long)M * Nout);
+    f16* dO = c.ws.get<f16>((long)M * Nout);
+    GemmP p = dense_gemm(c, dA, M, K, dW, N, db, dO, Nout);
+    p.R1 = dR; p.ldr1 = Nout; p.c0 = c0; p.c1 = c1; p.act = act; p.flags = geglu ? UG_F_GEGLU : 0;
+    plan_gemm(c, p);
+    launch_gemm(p, 1, c.stream);
+    down16(c, dO, out, (long)M * Nout);
+  });
+}
+
+// out = c0 * FF(LayerNorm(x') * gamma + beta) + c1 * x',  x' = fp16(X + addvec[row / rows_per_vec]) (addvec may be NULL: x' = X).
+// mode 0: LayerNorm launch + two GEMM launches; 1: LayerNorm launch + fused feed-forward; 2: everything inside the fused kernel.
+int ug_op_ln_ff(ug_ctx* x, const float* X, int M, int C, const float* gamma, const float* beta, float eps, const float* addvec, int rows_per_vec,
+                const float* W1, const float* b1, const float* W2, const float* b2, float c0, float c1, int mode, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int I = 4 * C;
+    std::vector<float> w1, bb1;
+    pack_geglu(W1, b1, 2 * I, C, w1, bb1);
+    const int nvec = addvec ? (M + rows_per_vec - 1) / rows_per_vec : 0;
+    f16* dX = up16(c, X, (long)M * C); f16* dW1 = up16(c, w1.data(), (long)2 * I * C); f16* db1 = up16(c, bb1.data(), 2 * I);
+    f16* dW2 = up16(c, W2, (long)C * I); f16* db2 = up16(c, b2, C);
+    f16* dg = up16(c, gamma, C); f16* dbt = up16(c, beta, C); f16* dav = addvec ? up16(c, addvec, (long)nvec * C) : nullptr;
+    f16* dO = c.ws.get<f16>((long)M * C);
+    if (mode == 2) {
+      FFusedP p = ff_fused(c, dX, M, C, dW1, db1, dW2, db2, dX, c0, c1, dO);
+      p.ln_g = dg; p.ln_b = dbt; p.ln_eps = eps; p.addvec = dav; p.rows_per_vec = rows_per_vec;
+      launch_ff_fused(p, c.stream);
+    } else {
+      f16* t1 = c.ws.get<f16>((long)M * C); f16* xo = c.ws.get<f16>((long)M * C);
+      LayerNormP l; memset(&l, 0, sizeof(l));
+      l.X = dX; l.Y = t1; l.M = M; l.C = C; l.eps = eps; l.gamma = dg; l.beta = dbt; l.addvec = dav; l.rows_per_vec = rows_per_vec; l.Xout = dav ? xo : nullptr;
+      launch_layernorm(l, c.stream);
+      const f16* res = dav ? xo : dX;
+      if (mode == 1) launch_ff_fused(ff_fused(c, t1, M, C, dW1, db1, dW2, db2, res, c0, c1, dO), c.stream);
+      else ff_two_launch(c, t1, M, C, dW1, db1, dW2, db2, res, c0, c1, c.ws.get<f16>((long)M * I), dO);
+    }
+    down16(c, dO, out, (long)M * C);
+  });
+}
+
+int ug_op_ff(ug_ctx* x, const float* X, int M, int C, const float* W1, const float* b1, const float* W2, const float* b2, const float* R1,
+             float c0, float c1, int fused, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int I = 4 * C;
+    std::vector<float> w1, bb1;
+    pack_geglu(W1, b1, 2 * I, C, w1, bb1);
+    f16* dX = up16(c, X, (long)M * C); f16* dW1 = up16(c, w1.data(), (long)2 * I * C); f16* db1 = up16(c, bb1.data(), 2 * I);
+    f16* dW2 = up16(c, W2, (long)C * I); f16* db2 = up16(c, b2, C); f16* dR = up16_opt(c, R1, (long)M * C);
+    f16* dO = c.ws.get<f16>((long)M * C);
+    if (fused) launch_ff_fused(ff_fused(c, dX, M, C, dW1, db1, dW2, db2, dR, c0, c1, dO), c.stream);
+    else ff_two_launch(c, dX, M, C, dW1, db1, dW2, db2, dR, c0, c1, c.ws.get<f16>((long)M * I), dO);
+    down16(c, dO, out, (long)M * C);
+  });
+}
+
+int ug_op_linear_mx8(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, int geglu, float* out,
+                     unsigned char* a8_out, unsigned* sa_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(K % 128 == 0 && N % 8 == 0, "op_linear_mx8: K % 128 == 0, N % 8 == 0");
+    std::vector<float> Wp, bp;
+    if (geglu) { pack_geglu(W, bias, N, K, Wp, bp); W = Wp.data(); if (bias) bias = bp.data(); }
+    f16* dA = up16(c, A, (long)M * K); f16* dW = up16(c, W, (long)N * K);
+    f16* db = up16_opt(c, bias, N);
+    const long ld_sa = (M + 255) / 256 * 256, ld_sw = (N + 255) / 256 * 256;
+    unsigned char* a8 = (unsigned char*)c.ws.alloc((size_t)M * K); unsigned char* w8 = (unsigned char*)c.ws.alloc((size_t)N * K);
+    unsigned* sa = (unsigned*)c.ws.alloc((size_t)(K / 128) * ld_sa * 4); unsigned* sw = (unsigned*)c.ws.alloc((size_t)(K / 128) * ld_sw * 4);
+    UG_CHECK(hipMemsetAsync(sa, 0, (size_t)(K / 128) * ld_sa * 4, c.stream)); UG_CHECK(hipMemsetAsync(sw, 0, (size_t)(K / 128) * ld_sw * 4, c.stream));
+    launch_quant_mx8(dA, K, M, K, a8, sa, ld_sa, c.stream);
+    launch_quant_mx8(dW, K, N, K, w8, sw, ld_sw, c.stream);
+    const int nout = geglu ? N / 2 : N;
+    f16* dO = c.ws.get<f16>((long)M * nout);
+    GemmP p = dense_gemm(c, (const f16*)a8, M, K, (const f16*)w8, N, db, dO, nout);
+    p.flags = geglu ? UG_F_GEGLU : 0;
+    p.sa = sa; p.ld_sa = ld_sa; p.sw = sw; p.ld_sw = ld_sw;
+    gemm_apply_tune(p, c.tune);
+    launch_gemm_mx8(p, c.stream);
+    down16(c, dO, out, (long)M * nout);
+    if (a8_out) UG_CHECK(hipMemcpy(a8_out, a8, (size_t)M * K, hipMemcpyDeviceToHost));
+    if (sa_out) UG_CHECK(hipMemcpy(sa_out, sa, (size_t)(K / 128) * ld_sa * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int ug_op_conv(ug_ctx* x, const float* x0, int C0, const float* x1, int C1, int T, int H, int W, const float* weight,
+               const float* bias, int O, int kt, int k, int stride, int pad_t, int pad_l, int ups, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int I = C0 + C1, taps = kt * k * k;
+    const bool kch = (I % 64 == 0) && taps > 1 && !getenv("UG_NO_KCHUNK");     // the engine's chunk-major K order (GemmP::kchunk); UG_NO_KCHUNK: tap-major weights -> general path
+    const std::vector<float> wp = pack_conv_weight(weight, O, I, taps, kch);
+    const long px = (long)T * H * W;
+    f16* d0 = up16(c, x0, px * C0); f16* d1 = C1 ? up16(c, x1, px * C1) : nullptr;
+    f16* dW = up16(c, wp.data(), (long)wp.size()); f16* db = up16_opt(c, bias, O);
+    const int Ho = H * ups / stride, Wo = W * ups / stride;
+    f16* dO = c.ws.get<f16>((long)T * Ho * Wo * O);
+    GemmP p = conv_gemm(c, d0, C0, d1, C1, T, H, W, kt, k, stride, pad_t, pad_l, ups, dW, O, db, dO);
+    p.kchunk = kch;
+    plan_gemm(c, p);
+    launch_gemm(p, 1, c.stream);
+    down16(c, dO, out, (long)T * Ho * Wo * O);
+  });
+}
+
+// conv (3x3 pad 1, or (kt,1,1) temporal) + optional residual, then GroupNorm (+SiLU) of its output two ways: statistics pass over the stored tensor
+// (y_pass) and statistics from the convolution's epilogue (GemmP::stat_part -> GroupNormP::part; y_epi).  rb_out: rows per statistics block the
+// launch reported (0: the planner's kernel cannot, y_epi then equals y_pass by construction).  conv_out: the convolution's output (both runs: must be bit-identical).
+int ug_op_conv_gn(ug_ctx* x, const float* x0, int C0, int T, int H, int W, const float* weight, const float* bias, const float* res, int O, int kt, int k,
+                  int G, float eps, int temporal, const float* gamma, const float* beta, float* conv_out, float* y_pass, float* y_epi, int* rb_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int I = C0, taps = kt * k * k;
+    UG_REQUIRE(I % 64 == 0, "ug_op_conv_gn: channels must be a multiple of 64");
+    const std::vector<float> wp = pack_conv_weight(weight, O, I, taps, true);
+    const long M = (long)T * H * W;
+    f16* d0 = up16(c, x0, M * C0); f16* dW = up16(c, wp.data(), (long)wp.size()); f16* db = up16_opt(c, bias, O);
+    f16* dR = up16_opt(c, res, M * O);
+    f16* dg = up16(c, gamma, O); f16* dbt = up16(c, beta, O);
+    f16* o1 = c.ws.get<f16>(M * O); f16* o2 = c.ws.get<f16>(M * O); f16* y1 = c.ws.get<f16>(M * O); f16* y2 = c.ws.get<f16>(M * O);
+    float2* part = (float2*)c.ws.get<float>(((M + 47) / 48) * (long)O * 2);
+    int rb = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+      GemmP p = conv_gemm(c, d0, C0, nullptr, 0, T, H, W, kt, k, 1, k / 2, k / 2, 1, dW, O, db, pass ? o2 : o1);
+      p.R1 = dR; p.ldr1 = O; p.c1 = 1.f; p.kchunk = taps > 1;
+      const size_t mk = c.ws.mark();
+      plan_gemm(c, p);
+      if (pass) { p.stat_part = part; p.stat_hw = H * W; launch_gemm(p, 1, c.stream, &rb); } else launch_gemm(p, 1, c.stream);
+      c.ws.release(mk);
+      GroupNormP g; memset(&g, 0, sizeof(g));
+      g.X0 = pass ? o2 : o1; g.C0 = O; g.T = T; g.HW = H * W; g.G = G; g.eps = eps; g.temporal = temporal; g.silu = 1; g.gamma = dg; g.beta = dbt;
+      g.Y = pass ? y2 : y1; g.ws = c.ws.get<float>((long)groupnorm_ws_floats(T, H * W, O, G));
+      if (pass && rb > 0) { g.part = part; g.part_rb = rb; }
+      const bool used = launch_groupnorm(g, c.stream);
+      if (pass && !used) rb = 0;              // the convolution wrote partial sums but GroupNorm took its slab / small form: report "no epilogue statistics"
+      c.ws.release(mk);
+    }
+    *rb_out = rb;
+    down16(c, o1, conv_out, M * O);
+    std::vector<float> tmp((size_t)M * O);
+    down16(c, o2, tmp.data(), M * O);
+    UG_REQUIRE(memcmp(tmp.data(), conv_out, tmp.size() * 4) == 0, "ug_op_conv_gn: the statistics epilogue changed the convolution's output");
+    down16(c, y1, y_pass, M * O); down16(c, y2, y_epi, M * O);
+  });
+}
+
+int ug_op_groupnorm(ug_ctx* x, const float* x0, int C0, const float* x1, int C1, int T, int HW, int G, float eps,
+                    int temporal, int silu, const float* gamma, const float* beta, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int C = C0 + C1; const long M = (long)T * HW;
+    GroupNormP p; memset(&p, 0, sizeof(p));
+    p.X0 = up16(c, x0, M * C0); p.X1 = C1 ? up16(c, x1, M * C1) : nullptr; p.C0 = C0; p.C1 = C1;
+    p.T = T; p.HW = HW; p.G = G; p.eps = eps; p.temporal = temporal; p.silu = silu;
+    p.gamma = up16(c, gamma, C); p.beta = up16(c, beta, C);
+    f16* y = c.ws.get<f16>(M * C); p.Y = y;
+    p.ws = c.ws.get<float>((long)groupnorm_ws_floats(T, HW, C, G));
+    launch_groupnorm(p, c.stream);
+    down16(c, y, out, M * C);
+  });
+}
+
+int ug_op_layernorm(ug_ctx* x, const float* xin, int M, int C, float eps, const float* gamma, const float* beta,
+                    const float* addvec, int rows_per_vec, float* out, float* xout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    LayerNormP p; memset(&p, 0, sizeof(p));
+    p.X = up16(c, xin, (long)M * C); p.M = M; p.C = C; p.eps = eps; p.gamma = up16(c, gamma, C); p.beta = up16(c, beta, C);
+    f16* y = c.ws.get<f16>((long)M * C); p.Y = y;
+    f16* xo = nullptr;
+    if (addvec) {
+      const int nv = (M + rows_per_vec - 1) / rows_per_vec;
+      p.addvec = up16(c, addvec, (long)nv * C); p.rows_per_vec = rows_per_vec;
+      xo = c.ws.get<f16>((long)M * C); p.Xout = xo;
+    }
+    launch_layernorm(p, c.stream);
+    down16(c, y, out, (long)M * C);
+    if (xo && xout) down16(c, xo, xout, (long)M * C);
+  });
+}
+
+int ug_op_flash_attn(ug_ctx* x, const float* qkv, int B, int H, int S, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int C = H * 64; const long M = (long)B * S;
+    f16* d = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
+    FlashP p; p.Q = d; p.K = d + C; p.V = d + 2 * C; p.ldq = p.ldk = p.ldv = 3 * C; p.O = o; p.ldo = C; p.variant = c.flash_variant;
+    p.B = B; p.H = H; p.S = S; p.scale = 0.125f;
+    launch_flash_attn64(p, c.stream);
+    down16(c, o, out, M * C);
+  });
+}
+
+int ug_op_temporal_attn(ug_ctx* x, const float* qkv, int T, int HW, int H, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int C = H * 64; const long M = (long)T * HW;
+    f16* d = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
+    TemporalAttnP p; p.Q = d; p.K = d + C; p.V = d + 2 * C; p.ld = 3 * C; p.O = o; p.ldo = C;
+    p.T = T; p.HW = HW; p.H = H; p.scale = 0.125f;
+    launch_temporal_attn64(p, c.stream);
+    down16(c, o, out, M * C);
+  });
+}
+
+int ug_op_attention_generic(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int C = H * d; const long M = (long)B * S;
+    f16* dq = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
+    test_unfused_attention(c, dq, 3 * C, B, S, H, d, o, C);
+    down16(c, o, out, M * C);
+  });
+}
+
+int ug_op_flash_attn_dh(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int C = H * d; const long M = (long)B * S;
+    f16* dq = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
+    FlashP p; p.variant = c.flash_variant; p.Q = dq; p.K = dq + C; p.V = dq + 2 * C; p.ldq = p.ldk = p.ldv = 3 * C; p.O = o; p.ldo = C; p.B = B; p.H = H; p.S = S;
+    p.scale = 1.0f / sqrtf((float)d);
+    launch_flash_attn_dh(p, d, c.stream);
+    down16(c, o, out, M * C);
+  });
+}
+
+int ug_op_euler_step(ug_ctx* x, const float* v, float* lat, long n, float sigma, float sigma_next) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    f16* dv = up16(c, v, n); f16* dl = up16(c, lat, n);
+    launch_euler_step(dv, dl, n, sigma, sigma_next, c.stream);
+    down16(c, dl, lat, n);
+  });
+}
+
+// ---- clip inputs made on the device (kernels/noise.hip): op-level entry points of the parity tests
+int ug_op_philox_u32(ug_ctx* x, uint64_t seed, uint32_t stream, uint64_t block_offset, long nblocks, uint32_t* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(nblocks >= 1 && out, "nblocks >= 1 and an output buffer");
+    uint32_t* d = c.ws.get<uint32_t>(nblocks * 4);
+    launch_philox_u32(d, nblocks, seed, stream, block_offset, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(out, d, (size_t)nblocks * 16, hipMemcpyDeviceToHost));
+  });
+}
+int ug_op_randn(ug_ctx* x, uint64_t seed, uint32_t stream, uint64_t element_offset, long n, long guard, float* inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(n >= 1 && guard >= 0 && inout, "n >= 1, guard >= 0 and a buffer of n + guard floats");
+    float* d = c.ws.get<float>(n + guard);
+    UG_CHECK(hipMemcpy(d, inout, (size_t)(n + guard) * 4, hipMemcpyHostToDevice));
+    launch_randn(d, n, seed, stream, element_offset, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(inout, d, (size_t)(n + guard) * 4, hipMemcpyDeviceToHost));
+  });
+}
+int ug_op_u8_to_frames(ug_ctx* x, const unsigned char* frames_tchw, int T, int H, int W, float* out_thwc) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && H >= 1 && W >= 1 && ((long)H * W) % 4 == 0, "H * W must be a multiple of 4");
+    const long px = (long)T * H * W;
+    unsigned char* d8 = c.ws.get<unsigned char>(px * 3); float* df = c.ws.get<float>(px * 3);
+    UG_CHECK(hipMemcpy(d8, frames_tchw, (size_t)px * 3, hipMemcpyHostToDevice));
+    launch_u8_to_frames(d8, df, T, (long)H * W, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(out_thwc, df, (size_t)px * 12, hipMemcpyDeviceToHost));
+  });
+}
+
+// ------------------------------------------------------------------ micro-benchmarks on device-resident pseudo-random data
+int ug_bench_flash(ug_ctx* x, int B, int H, int S, int variant, int iters, float* us_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const long M = (long)B * S; const int C = H * 64;
+    f16* qkv = c.ws.get<f16>(M * 3 * C); f16* o = c.ws.get<f16>(M * C);
+    launch_fill_random(qkv, M * 3 * C, 7, c.stream);
+    FlashP p; p.Q = qkv; p.K = qkv + C; p.V = qkv + 2 * C; p.ldq = p.ldk = p.ldv = 3 * C; p.O = o; p.ldo = C; p.B = B; p.H = H; p.S = S; p.scale = 0.125f;
+    p.variant = variant;     // passed with the launch: the process default (and every other launch) is untouched
+    *us_out = time_launches_ms(c, 2, iters, [&](int) { launch_flash_attn64(p, c.stream); }) * 1000.f / iters;
+  });
+}
+int ug_bench_ff(ug_ctx* x, int M, int C, int fused, int iters, float* us_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int I = 4 * C;
+    f16* dX = c.ws.get<f16>((long)M * C); f16* dW1 = c.ws.get<f16>((long)2 * I * C); f16* db1 = c.ws.get<f16>(2 * I);
+    f16* dW2 = c.ws.get<f16>((long)C * I); f16* db2 = c.ws.get<f16>(C); f16* dR = c.ws.get<f16>((long)M * C);
+    f16* dO = c.ws.get<f16>((long)M * C); f16* mid = c.ws.get<f16>((long)M * I);
+    launch_fill_random(dX, (long)M * C, 1, c.stream); launch_fill_random(dW1, (long)2 * I * C, 2, c.stream); launch_fill_random(db1, 2 * I, 3, c.stream);
+    launch_fill_random(dW2, (long)C * I, 4, c.stream); launch_fill_random(db2, C, 5, c.stream); launch_fill_random(dR, (long)M * C, 6, c.stream);
+    launch_scale_f16(dW1, dW1, 0.05f, (long)2 * I * C, c.stream); launch_scale_f16(dW2, dW2, 0.03f, (long)C * I, c.stream);
+    *us_out = time_launches_ms(c, 2, iters, [&](int) {
+      if (fused) launch_ff_fused(ff_fused(c, dX, M, C, dW1, db1, dW2, db2, dR, 1.f, 1.f, dO), c.stream);
+      else ff_two_launch(c, dX, M, C, dW1, db1, dW2, db2, dR, 1.f, 1.f, mid, dO);
+    }) * 1000.f / iters;
+  });
+}
+int ug_bench_groupnorm(ug_ctx* x, int C0, int C1, int T, int HW, int temporal, int mode, int iters, float* us_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int C = C0 + C1; const long M = (long)T * HW;
+    GroupNormP p; memset(&p, 0, sizeof(p));
+    f16* a0 = c.ws.get<f16>(M * C0); f16* a1 = C1 ? c.ws.get<f16>(M * C1) : nullptr;
+    launch_fill_random(a0, M * C0, 1, c.stream); if (C1) launch_fill_random(a1, M * C1, 2, c.stream);
+    f16* gm = c.ws.get<f16>(C); f16* bt = c.ws.get<f16>(C);
+    launch_fill_random(gm, C, 3, c.stream); launch_fill_random(bt, C, 4, c.stream);
+    p.X0 = a0; p.X1 = a1; p.C0 = C0; p.C1 = C1; p.T = T; p.HW = HW; p.G = 32; p.eps = 1e-5f; p.temporal = temporal; p.silu = 1;
+    p.gamma = gm; p.beta = bt; p.Y = c.ws.get<f16>(M * C); p.mode = mode;
+    p.ws = c.ws.get<float>((long)groupnorm_ws_floats(T, HW, C, 32));
+    us_out[0] = time_launches_ms(c, 3, iters, [&](int) { launch_groupnorm(p, c.stream); }) * 1000.f / iters;
+  });
+}
+int ug_bench_mfma_peak(ug_ctx* x, int iters, float* tflops_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    float* scratch = c.ws.get<float>(256 * 512);
+    *tflops_out = bench_mfma_peak(scratch, iters > 0 ? iters : 20000, c.stream);
+  });
+}
+
+// GEMM / conv microbenchmark: average ms per launch over `iters`.
+int ug_bench_gemm(ug_ctx* x, int M, int N, int K, int conv, int T, int Hi, int Wi, int C0, int C1, int kt, int k,
+                  int stride, int ups, int cfg, int split, int iters, float* ms_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    GemmP p = conv ? conv_gemm(c, nullptr, C0, nullptr, C1, T, Hi, Wi, kt, k, stride, k / 2, k / 2, ups, nullptr, N, nullptr, nullptr)
+                   : dense_gemm(c, nullptr, M, K, nullptr, N, nullptr, nullptr, N);
+    M = p.M; K = p.K;                            // conv: the im2col problem, T * Ho * Wo x (C0 + C1) * taps
+    const long asz = conv ? (long)T * Hi * Wi * C0 : (long)M * K;
+    // rotate through enough distinct A / output buffers to exceed the 256 MiB Infinity Cache: in the pipeline the
+    // activation operand was just streamed out by the previous kernel and does not sit in cache
+    const long a1sz = C1 ? (long)T * Hi * Wi * C1 : 0;
+    const long per = (asz + a1sz + (long)M * N) * 2;
+    int nbuf = (int)std::min<long>(16, std::max<long>(2, (600L << 20) / std::max<long>(per, 1) + 1));
+    if (getenv("UG_BENCH_WARM")) nbuf = 1;
+    std::vector<f16*> As(nbuf), A1s(nbuf), Os(nbuf);
+    for (int i = 0; i < nbuf; ++i) {
+      As[i] = c.ws.get<f16>(asz); A1s[i] = C1 ? c.ws.get<f16>(a1sz) : nullptr; Os[i] = c.ws.get<f16>((long)M * N);
+      launch_fill_random(As[i], asz, 1 + i, c.stream); if (C1) launch_fill_random(A1s[i], a1sz, 100 + i, c.stream);
+    }
+    f16* Wt = c.ws.get<f16>((long)N * K); f16* b = c.ws.get<f16>(N);
+    launch_fill_random(Wt, (long)N * K, 3, c.stream); launch_fill_random(b, N, 4, c.stream);
+    p.W = Wt; p.bias = b;
+    p.kchunk = (conv && kt * k * k > 1 && (C0 + C1) % 64 == 0 && !getenv("UG_NO_KCHUNK")) ? 1 : 0;   // the engine's chunk-major K order (random weights: the layout itself is immaterial)
+    p.A0 = As[0]; p.A1 = A1s[0]; p.Out = Os[0];
+    if (getenv("UG_BENCH_GEGLU") && !conv && N % 128 == 0) { p.flags |= UG_F_GEGLU; p.ldo = N / 2; }   // A/B aid: GEGLU epilogue
+    if (getenv("UG_BENCH_R1")) { p.R1 = Os[nbuf - 1]; p.ldr1 = N; p.c1 = 1.f; }                          // A/B aid: a residual operand in the epilogue
+    if (getenv("UG_BENCH_NOBIAS")) p.bias = nullptr;
+    gemm_apply_tune(p, c.tune);
+    int cf = cfg, sp = split;                    // forced values win over the planner's
+    if (cf < 0 || sp < 1) { int c2, s2; gemm_plan(p, 1, &c2, &s2); if (cf < 0) cf = c2; if (sp < 1) sp = s2; }
+    p.cfg_p1 = cf + 1; p.splitk = sp;
+    if (sp > 1) p.partial = c.ws.get<float>((long)sp * M * N);
+    unsigned* trace = nullptr;
+    if (getenv("UG_GEMM_TRACE")) { trace = c.ws.get<unsigned>(3 * 24 * 5); UG_CHECK(hipMemsetAsync(trace, 0, 3 * 24 * 5 * 4, c.stream)); p.trace = trace; }
+    const float ms = time_launches_ms(c, 2, iters, [&](int i) { p.A0 = As[i % nbuf]; p.A1 = A1s[i % nbuf]; p.Out = Os[i % nbuf]; launch_gemm(p, 1, c.stream); });
+    if (trace) {   // per K-step: [MFMAs issued .. operands landed .. barrier passed .. fetch issued .. MFMAs issued]
+      std::vector<unsigned> h(3 * 24 * 5);
+      UG_CHECK(hipMemcpy(h.data(), trace, h.size() * 4, hipMemcpyDeviceToHost));
+      for (int w = 0; w < 3; ++w) {
+        if (w == 2 && h[2 * 24 * 5] == 0) break;   // only the producer / consumer kernel has a third traced wave (a fetch wave)
+        printf("wave %d: step  stamp0->1   1->2   2->3   3->next0   total   (gemm_kernel: vmcnt-wait, barrier, fetch-issue, reads+MFMA;"
+               " gemm_ws consumer: reads+MFMA, epilogue+lgkm, barrier, -; producer: fetch-issue, vmcnt-wait, barrier, -)\n", w * 4);
+        for (int st = 0; st + 1 < 24; ++st) {
+          auto at = [&](int s2, int k) { return h[(size_t)w * 24 * 5 + (size_t)s2 * 5 + k]; };
+          auto d = [&](unsigned a, unsigned b) { return (b - a) & 0xFFFFF; };
+          printf("        %4d  %10u  %7u  %11u  %10u  %6u\n", st + 8, d(at(st, 0), at(st, 1)), d(at(st, 1), at(st, 2)), d(at(st, 2), at(st, 3)),
+                 d(at(st, 3), at(st + 1, 0)), d(at(st, 0), at(st + 1, 0)));
+        }
+      }
+    }
+    ms_out[0] = ms / iters; ms_out[1] = (float)cf; ms_out[2] = (float)sp; ms_out[3] = (float)M; ms_out[4] = (float)K;
+  });
+}
+
+}  // extern "C"

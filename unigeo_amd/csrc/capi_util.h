@@ -1,0 +1,90 @@
+// Private to the two extern "C" units: capi.hip (include/unigeo_hip.h, the drop-in boundary) and capi_test.hip (include/unigeo_hip_test.h,
+// test / tuning entry points).  The context handle, the error funnel and the host <-> device helpers both sides use.
+#pragma once
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "../../include/unigeo_hip.h"
+#include "../../include/unigeo_hip_test.h"
+#include "engine.h"
+
+using namespace ug;
+
+struct ug_ctx { Ctx c; };
+
+#define UG_TRY(ctx, ...)                                   \
+  if (!(ctx)) return -1;                                   \
+  try { UG_CHECK(hipSetDevice((ctx)->c.device)); __VA_ARGS__; return 0; } \
+  catch (const std::exception& e) { (ctx)->c.err = e.what(); (void)hipGetLastError(); return 1; } \
+  catch (...) { (ctx)->c.err = "unknown error"; return 2; }
+
+// ------------------------------------------------------------------ host <-> device helpers
+struct Scope {
+  Ctx& c; size_t mk;
+  explicit Scope(Ctx& c_) : c(c_), mk(c_.ws.mark()) {}
+  ~Scope() { (void)hipStreamSynchronize(c.stream); c.ws.release(mk); }
+};
+static inline void upload16(const float* h, long n, f16* d) {   // float host -> f16 device, into d
+  std::vector<f16> v((size_t)n);
+  for (long i = 0; i < n; ++i) v[i] = (f16)h[i];
+  UG_CHECK(hipMemcpy(d, v.data(), (size_t)n * 2, hipMemcpyHostToDevice));
+}
+static inline f16* up16(Ctx& c, const float* h, long n) {
+  f16* d = c.ws.get<f16>(n);
+  upload16(h, n, d);
+  return d;
+}
+static inline f16* up16_opt(Ctx& c, const float* h, long n) { return h ? up16(c, h, n) : nullptr; }
+static inline void down16(Ctx& c, const f16* d, float* h, long n) {
+  std::vector<f16> v((size_t)n);
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(v.data(), d, (size_t)n * 2, hipMemcpyDeviceToHost));
+  for (long i = 0; i < n; ++i) h[i] = (float)v[i];
+}
+// NCHW float host -> NHWC(+channel pad) f16 device, into d (T*H*W*Cpad elements)
+static inline void upload_nchw(const float* h, int T, int C, int H, int W, int Cpad, f16* d) {
+  std::vector<f16> v((size_t)T * H * W * Cpad, (f16)0.f);
+  for (int t = 0; t < T; ++t)
+    for (int ch = 0; ch < C; ++ch)
+      for (long p = 0; p < (long)H * W; ++p) v[((size_t)t * H * W + p) * Cpad + ch] = (f16)h[((size_t)t * C + ch) * H * W + p];
+  UG_CHECK(hipMemcpy(d, v.data(), v.size() * 2, hipMemcpyHostToDevice));
+}
+static inline f16* up_nchw(Ctx& c, const float* h, int T, int C, int H, int W, int Cpad) {
+  f16* d = c.ws.get<f16>((long)T * H * W * Cpad);
+  upload_nchw(h, T, C, H, W, Cpad, d);
+  return d;
+}
+static inline void down_nchw(Ctx& c, const f16* d, float* h, int T, int C, int H, int W) {
+  std::vector<f16> v((size_t)T * H * W * C);
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(v.data(), d, v.size() * 2, hipMemcpyDeviceToHost));
+  for (int t = 0; t < T; ++t)
+    for (int ch = 0; ch < C; ++ch)
+      for (long p = 0; p < (long)H * W; ++p) h[((size_t)t * C + ch) * H * W + p] = (float)v[((size_t)t * H * W + p) * C + ch];
+}
+
+// ------------------------------------------------------------------ depth evaluation: what ug_eval_depth* (product) and ug_op_masked_median (test) share
+static inline float clip_lo(float v) { return std::isnan(v) ? -INFINITY : v; }
+static inline float clip_hi(float v) { return std::isnan(v) ? INFINITY : v; }
+static inline float depth_bound(float v) { return (std::isnan(v) || v <= 0.f) ? NAN : v; }   // NaN: the kernels test gt > 0 only
+struct DepthEvalBufs { const float* dp; float* dg; unsigned char* dm; };
+static inline DepthEvalBufs depth_eval_upload(Ctx& c, const float* pred, const float* gt, const unsigned char* cmask, long n) {
+  DepthEvalBufs b{nullptr, nullptr, nullptr};
+  if (pred) { float* d = c.ws.get<float>(n); UG_CHECK(hipMemcpy(d, pred, n * 4, hipMemcpyHostToDevice)); b.dp = d; }
+  else { UG_REQUIRE(c.io_ready && n == (long)c.T * c.H * c.W, "no resident depth of that size"); b.dp = c.d_depth; }
+  b.dg = c.ws.get<float>(n); UG_CHECK(hipMemcpy(b.dg, gt, n * 4, hipMemcpyHostToDevice));
+  if (cmask) { b.dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(b.dm, cmask, n, hipMemcpyHostToDevice)); }
+  return b;
+}
+// the result words of launch_masked_median, once the stream is idle: how many pixels were selected, the lower medians of prediction and ground truth
+static inline void read_masked_median(Ctx& c, const unsigned* sel, unsigned& count, float& mp, float& mg) {
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  unsigned r[3];
+  UG_CHECK(hipMemcpy(r, sel + SEL_COUNT, sizeof(r), hipMemcpyDeviceToHost));
+  count = r[0]; memcpy(&mp, &r[1], 4); memcpy(&mg, &r[2], 4);
+}

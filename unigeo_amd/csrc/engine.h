@@ -185,6 +185,9 @@ void bind_unet(Ctx& c, const UNetCfg& cfg, const std::string& prefix);
 void bind_vae(Ctx& c, const VAECfg& cfg, const std::string& prefix);
 void bind_clip(Ctx& c, const CLIPCfg& cfg, const std::string& prefix);
 void finish_binding(Ctx& c, const std::string& prefix);   // fail on unused tensors, free raw
+// GEGLU projection [2*inner][in] in the bound row order: blocks of 16 rows = [8 value rows | 8 gate rows], so that the GEMM epilogue finds value and
+// gate of the same output column in one lane.  Bound row v holds row geglu_src_row(v, inner) of the state-dict tensor [values | gates].
+inline int geglu_src_row(int v, int inner) { const int blk = v / 16, wv = v % 16; return wv < 8 ? blk * 8 + wv : inner + blk * 8 + (wv - 8); }
 
 // ---- graphs (device pointers, stream-ordered, transient memory from c.ws) ----
 // x [T,h,w,in_ch] f16; clip_emb [T,cross_dim] f16; tsteps host array of continuous timesteps
@@ -198,6 +201,8 @@ void vae_decode(Ctx& c, const f16* z, int T, int h, int w, float* frames_out);  
 f16* clip_embed(Ctx& c, const f16* video_m11, int T, int H, int W);       // [T,H,W,3] -> [T,proj]
 
 f16* vae_encode_v(Ctx& c, VAE& v, const f16* x8, int T, int H, int W, bool fp32_grade);
+// the unfused attention path (scores GEMM, softmax, value GEMM) on its own: exposed for the op-level tests
+void test_unfused_attention(Ctx& c, const f16* qkv, long ld, int B, int S, int H, int d, f16* out, long ldo);
 
 // ---- StableNormal (sn_graphs.inc) ----
 void bind_sn(Ctx& c, const UNetCfg& ucfg, const VAECfg& vcfg, const CLIPCfg& dcfg, const std::string& prefix);   // "<prefix>{vae,unet_yoso,controlnet_yoso,unet,controlnet_dino,dino}."

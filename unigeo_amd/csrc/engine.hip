@@ -252,10 +252,21 @@ void* pinned(Ctx& c, int slot, size_t bytes) {
 }
 
 static inline long pad256(long x) { return (x + 255) / 256 * 256; }
+// what the fp16 and the MX-fp8 form of linear() share: bias, epilogue operands and the output, leading dimensions defaulting to the output width
+static void set_epilogue(GemmP& p, const Lin& l, const Epi& e, f16* out, long ldo) {
+  const int nout = (e.flags & UG_F_GEGLU) ? l.out / 2 : l.out;
+  p.bias = l.b; p.bias2 = e.bias2;
+  p.R1 = e.R1; p.ldr1 = e.ldr1; p.c1 = e.c1; p.R2 = e.R2; p.ldr2 = e.ldr2; p.c2 = e.c2; p.c0 = e.c0;
+  p.act = e.act; p.flags = e.flags;
+  p.Out = out; p.ldo = ldo ? ldo : nout;
+  if (p.R1 && !p.ldr1) p.ldr1 = nout;
+  if (p.R2 && !p.ldr2) p.ldr2 = nout;
+}
 // Out[M, lin.out] = A[M, lin.in] W^T (+bias) ...
 static void linear(Ctx& c, const f16* A, long M, const Lin& l, f16* out, const Epi& e = Epi(), long lda = 0,
                    long ldo = 0) {
   GemmP p; memset(&p, 0, sizeof(p));
+  set_epilogue(p, l, e, out, ldo);
   if (c.fp8_linears && l.w8 && M >= 256 && !(e.flags & UG_F_OUT_F32)) {
     // MX-fp8 path: quantise the activation rows (32-element blocks, e8m0 scales), then the same persistent GEMM on e4m3 operands
     const size_t mk = c.ws.mark();
@@ -276,13 +287,8 @@ static void linear(Ctx& c, const f16* A, long M, const Lin& l, f16* out, const E
       launch_quant_mx8(A, lda ? lda : K, M, K, a8w, saw, ld_sa, c.stream);
     }
     p.A0 = (const f16*)a8; p.C0 = K; p.M = (int)M; p.N = l.out; p.K = K;
-    p.W = (const f16*)l.w8; p.ldw = K; p.bias = l.b; p.bias2 = e.bias2;
-    p.R1 = e.R1; p.ldr1 = e.ldr1; p.c1 = e.c1; p.R2 = e.R2; p.ldr2 = e.ldr2; p.c2 = e.c2; p.c0 = e.c0;
-    p.act = e.act; p.flags = e.flags;
+    p.W = (const f16*)l.w8; p.ldw = K;
     const int nout = (e.flags & UG_F_GEGLU) ? l.out / 2 : l.out;
-    p.Out = out; p.ldo = ldo ? ldo : nout;
-    if (p.R1 && !p.ldr1) p.ldr1 = nout;
-    if (p.R2 && !p.ldr2) p.ldr2 = nout;
     p.sa = sa; p.ld_sa = ld_sa; p.sw = l.sw8; p.ld_sw = l.ld_sw8; p.zero = c.zero; p.nb_inner = 1;
     gemm_apply_tune(p, c.tune);
     {
@@ -293,13 +299,7 @@ static void linear(Ctx& c, const f16* A, long M, const Lin& l, f16* out, const E
     return;
   }
   p.A0 = A; p.C0 = (int)(lda ? lda : l.in); p.M = (int)M; p.N = l.out; p.K = l.in;
-  p.W = l.w; p.ldw = l.in; p.bias = l.b; p.bias2 = e.bias2;
-  p.R1 = e.R1; p.ldr1 = e.ldr1; p.c1 = e.c1; p.R2 = e.R2; p.ldr2 = e.ldr2; p.c2 = e.c2; p.c0 = e.c0;
-  p.act = e.act; p.flags = e.flags;
-  const int nout = (e.flags & UG_F_GEGLU) ? l.out / 2 : l.out;
-  p.Out = out; p.ldo = ldo ? ldo : nout;
-  if (p.R1 && !p.ldr1) p.ldr1 = nout;
-  if (p.R2 && !p.ldr2) p.ldr2 = nout;
+  p.W = l.w; p.ldw = l.in;
   run_gemm(c, p, 1, "gemm_linear", e.alg, e.so, e.stat_hw);
 }
 
@@ -457,18 +457,14 @@ static Lin bind_lin_cat(Ctx& c, const std::vector<std::string>& ps, int in, int 
   l.w = w; l.b = b;
   return l;
 }
-// GEGLU projection [2*inner][in]: rows re-ordered in blocks of 16 = [8 value rows | 8 gate rows] so that the
-// GEMM epilogue finds value and gate of the same output column in one lane.
+// GEGLU projection [2*inner][in], rows gathered into the bound order (geglu_src_row)
 static Lin bind_geglu(Ctx& c, const std::string& p, int in, int inner) {
   const int out = 2 * inner;
   UG_REQUIRE(inner % 8 == 0, "GEGLU inner dim must be a multiple of 8");
   RawTensor& tw = raw_get(c, p + ".weight", {out, in});
   RawTensor& tb = raw_get(c, p + ".bias", {out});
   std::vector<int> map(out);
-  for (int v = 0; v < out; ++v) {
-    const int blk = v / 16, wv = v % 16;
-    map[v] = wv < 8 ? blk * 8 + wv : inner + blk * 8 + (wv - 8);
-  }
+  for (int v = 0; v < out; ++v) map[v] = geglu_src_row(v, inner);
   int* dmap = (int*)c.persist.alloc(out * sizeof(int));
   UG_CHECK(hipMemcpy(dmap, map.data(), out * sizeof(int), hipMemcpyHostToDevice));
   Lin l; l.in = in; l.out = out;
