@@ -194,6 +194,22 @@ typedef struct { int alignment; float max_depth;            /* <= 0 or NaN: gt >
 void ug_depth_eval_opts_default(ug_depth_eval_opts* o);     /* LSTSQ, 80, all clips off */
 int ug_eval_depth_ex(ug_ctx* ctx, const float* pred_depth /* NULL: resident depth */, const float* gt_depth, const unsigned char* custom_mask,
                      long n, const ug_depth_eval_opts* opts, double* out11, float* err_map_out /* [n] or NULL */);
+/* Depth evaluation in global coordinates: the reference's depth_evaluation_in_global_coord (metrics/eval_depth.py:250-441,
+ * utils/geometry_utils.py:246-253).  mask1 = gt_depth > 0 (and gt_depth < max_depth) - from the ground-truth DEPTH, never
+ * from the radius.  Fit 1: least squares (s_d, t_d) of clamp(pred, pre_clip) against gt_depth on mask1.  Every pixel, from the ORIGINAL
+ * prediction: d = clamp(s_d * pred + t_d, post_clip) in float32, the product and the sum rounded separately; in float64 from that d,
+ * x = (col - cx) * d / fx, y = (row - cy) * d / fy, z = d (integer pixel indices, no half-pixel offset), world = R (x, y, z) + t with the top
+ * three rows of the frame's pose, r = |world| rounded once to float32.  Fit 2: least squares (s_r, t_r) of r against gt_radius on mask1.
+ * radius_map_out (host, [T*H*W], may be NULL) = s_r * r + t_r for every pixel; the metrics of ug_eval_depth on it against gt_radius over
+ * mask1 & custom_mask, no clamp at that stage.  cam2world_t44: [T,4,4] row-major camera-to-world (OpenCV), intrinsics_t33: [T,3,3].
+ * out13[0..8] as ug_eval_depth, out13[9..10] = (s_r, t_r), out13[11..12] = (s_d, t_d).  Both fits are float64 normal equations with
+ * ug_eval_depth's degenerate cases; no valid pixel: zero metrics, both fits (0, 0), a zero map.  opts: max_depth and the clip bounds as in
+ * ug_eval_depth_ex; alignment must be UG_ALIGN_LSTSQ (the reference asserts it).  Errors (ug_last_error; the context stays usable): another
+ * alignment; NULL opts / gt_depth / gt_radius / cam2world / intrinsics / out13; T, H or W <= 0; 2^32 pixels or more; pred_depth == NULL
+ * without a resident depth of that shape.  A ground-truth radius of 0 on mask1 divides by zero, as in the reference. */
+int ug_eval_depth_global(ug_ctx* ctx, const float* pred_depth /* NULL: resident depth */, const float* gt_depth, const float* gt_radius,
+                         const float* cam2world_t44, const float* intrinsics_t33, const unsigned char* custom_mask /* or NULL */, int T, int H,
+                         int W, const ug_depth_eval_opts* opts, double* out13, float* radius_map_out /* [T*H*W] or NULL */);
 
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */

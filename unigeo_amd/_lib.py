@@ -19,7 +19,7 @@ EXPORTS = [
     "ug_create", "ug_destroy", "ug_last_error", "ug_workspace_peak",
     "ug_load_tensor", "ug_bind_unet", "ug_bind_vae", "ug_bind_clip",
     "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_dc_set_inputs_ex", "ug_dc_get_noise", "ug_op_philox_u32", "ug_op_randn", "ug_op_u8_to_frames", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
-    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
+    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
@@ -115,6 +115,7 @@ def load_library():
     lib.ug_depth_eval_opts_default.restype = None
     lib.ug_depth_eval_opts_default.argtypes = [C.POINTER(DepthEvalOptsC)]
     lib.ug_eval_depth_ex.argtypes = [vp, vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, vp]
+    lib.ug_eval_depth_global.argtypes = [vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -536,6 +537,30 @@ class Engine:
         if return_error_map:
             return res, (float(out[9]), float(out[10])), emap
         return res, (float(out[9]), float(out[10]))
+
+    def eval_depth_global(self, gt_depth, gt_radius, cam2world, intrinsics, mask=None, pred=None, max_depth=80.0, pre_clip_min=None,
+                          pre_clip_max=None, post_clip_min=None, post_clip_max=None, return_radius_map=False):
+        """Depth metrics in global coordinates on the device (``ug_eval_depth_global``) -> ``(res, (s_r, t_r),
+        (s_d, t_d))``, with ``return_radius_map=True`` also the aligned radius map ``[T,H,W]``.  ``gt_depth`` / ``gt_radius`` ``[T,H,W]``,
+        ``cam2world`` ``[T,4,4]``, ``intrinsics`` ``[T,3,3]``; ``pred=None`` evaluates the resident depth; least squares only."""
+        g = _f32(gt_depth)
+        if g.ndim != 3:
+            raise ValueError("eval_depth_global: gt_depth must be [T,H,W]")
+        T, H, W = g.shape
+        gr = _f32(gt_radius).reshape(T, H, W)
+        pose, k = _f32(cam2world).reshape(T, 4, 4), _f32(intrinsics).reshape(T, 3, 3)
+        p = None if pred is None else _f32(pred).reshape(T, H, W)
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8)).reshape(T, H, W)
+        o = DepthEvalOptsC(DEPTH_ALIGNMENTS["lstsq"], float("nan") if max_depth is None else float(max_depth),
+                           *[float("nan") if c is None else float(c) for c in (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)])
+        out = np.zeros(13, np.float64)
+        rmap = np.empty(g.shape, np.float32) if return_radius_map else None
+        self._ck(self.lib.ug_eval_depth_global(self.ctx, _ptr(p), _ptr(g), _ptr(gr), _ptr(pose), _ptr(k), _ptr(m), T, H, W, C.byref(o), _ptr(out),
+                                               _ptr(rmap)))
+        res = dict(zip(self.DEPTH_KEYS, out[:8].tolist()))
+        res["valid_pixels"] = int(out[8])
+        fits = (float(out[9]), float(out[10])), (float(out[11]), float(out[12]))
+        return (res, *fits, rmap) if return_radius_map else (res, *fits)
 
     def op_masked_median(self, pred, gt, max_depth=80.0, pre_clip_min=None, pre_clip_max=None):
         """The exact masked selection alone -> (lower median of clamp(pred), lower median of gt, count) over the valid ``gt``."""

@@ -321,6 +321,44 @@ int ug_eval_depth_ex(ug_ctx* x, const float* pred, const float* gt, const unsign
   });
 }
 
+int ug_eval_depth_global(ug_ctx* x, const float* pred, const float* gt, const float* gt_radius, const float* cam2world, const float* K,
+                         const unsigned char* cmask, int T, int H, int W, const ug_depth_eval_opts* o, double* out, float* rmap_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(o != nullptr, "options must not be NULL");
+    UG_REQUIRE(o->alignment == UG_ALIGN_LSTSQ, "depth alignment in global coordinates must be UG_ALIGN_LSTSQ (the reference asserts least squares)");
+    UG_REQUIRE(gt && gt_radius && cam2world && K && out, "gt_depth, gt_radius, cam2world, intrinsics and out13 must not be NULL");
+    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
+    const long n = (long)T * H * W;
+    UG_REQUIRE(n < (1L << 32), "pixel count");
+    UG_REQUIRE(pred || (c.io_ready && T == c.T && H == c.H && W == c.W), "no resident depth of that shape");
+    const float md = depth_bound(o->max_depth);
+    const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
+    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
+    float* dgr = c.ws.get<float>(n); UG_CHECK(hipMemcpy(dgr, gt_radius, n * 4, hipMemcpyHostToDevice));
+    std::vector<double> tab((size_t)T * 16);      // per frame: fx, fy, cx, cy, R row-major, t
+    for (int f = 0; f < T; ++f) {
+      const float* k = K + (size_t)f * 9; const float* p = cam2world + (size_t)f * 16; double* q = tab.data() + (size_t)f * 16;
+      q[0] = k[0]; q[1] = k[4]; q[2] = k[2]; q[3] = k[5];
+      for (int r = 0; r < 3; ++r) { for (int j = 0; j < 3; ++j) q[4 + r * 3 + j] = p[r * 4 + j]; q[13 + r] = p[r * 4 + 3]; }
+    }
+    double* dcam = c.ws.get<double>((long)T * 16); UG_CHECK(hipMemcpy(dcam, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    float* dr = c.ws.get<float>(n);
+    double* part = c.ws.get<double>(1024 * 9);
+    int nb = 0;
+    double sd = 0.0, td = 0.0, sr = 0.0, tr = 0.0;
+    launch_depth_fit_ex(d.dp, d.dg, n, md, lo, hi, part, &nb, c.stream);
+    fetch_lstsq(c, part, nb, sd, td);
+    launch_world_radius(d.dp, d.dg, dgr, dcam, n, H, W, md, plo, phi, (float)sd, (float)td, dr, part, &nb, c.stream);
+    fetch_lstsq(c, part, nb, sr, tr);
+    float* dmap = rmap_out ? c.ws.get<float>(n) : nullptr;
+    launch_radius_metrics(dr, d.dg, dgr, d.dm, n, md, (float)sr, (float)tr, part, dmap, &nb, c.stream);
+    fetch_depth_metrics(c, part, nb, sr, tr, out);
+    out[11] = sd; out[12] = td;
+    if (rmap_out) UG_CHECK(hipMemcpy(rmap_out, dmap, n * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 int ug_eval_normal(ug_ctx* x, const float* pred, const float* gt, const unsigned char* mask, long n, double* out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);

@@ -283,3 +283,8 @@ void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float ma
 void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s);
 void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
                              float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s);
+// depth evaluation in global coordinates (kernels/metrics.hip); cam: 16 doubles per frame = fx, fy, cx, cy, R row-major, t
+void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
+                         float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s);
+void launch_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask, long n, float max_depth,
+                           float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s);

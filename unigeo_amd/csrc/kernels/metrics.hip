@@ -24,6 +24,17 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   return r;
 }
 
+// one selected pixel's terms of the nine metric sums: n, absrel, sqrel, sq, logsq, d1, d125, d125^2, d125^3 (prediction p, target g > 0)
+__device__ __forceinline__ void metric_terms(float p, float g, double* a) {
+  const float d = p - g;
+  a[0] += 1.0; a[1] += fabsf(d) / g; a[2] += d * d / g; a[3] += d * d;
+  const float pc = fmaxf(p, 1e-5f);
+  const float l = logf(pc) - logf(g);
+  a[4] += l * l;
+  const float r = fmaxf(pc / g, g / pc);
+  a[5] += r < 1.0f; a[6] += r < 1.25f; a[7] += r < 1.5625f; a[8] += r < 1.953125f;
+}
+
 // pass 1: normal-equation sums over mask1 = (0 < gt < max_depth): n, sum p, sum p^2, sum g, sum p*g
 __global__ __launch_bounds__(MB) void k_depth_fit(const float* pred, const float* gt, long n, float max_depth, double* part) {
   __shared__ double sh[MB];
@@ -45,18 +56,12 @@ __global__ __launch_bounds__(MB) void k_depth_fit(const float* pred, const float
 __global__ __launch_bounds__(MB) void k_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n,
                                                       float max_depth, float s, float t, double* part) {
   __shared__ double sh[MB];
-  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // n, absrel, sqrel, sq, logsq, d1, d125, d125^2, d125^3
+  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
     const float g = gt[i];
     if (g > 0.f && g < max_depth && (!cmask || cmask[i])) {
       const float p = s * pred[i] + t;
-      const float d = p - g;
-      a[0] += 1.0; a[1] += fabsf(d) / g; a[2] += d * d / g; a[3] += d * d;
-      const float pc = fmaxf(p, 1e-5f);
-      const float l = logf(pc) - logf(g);
-      a[4] += l * l;
-      const float r = fmaxf(pc / g, g / pc);
-      a[5] += r < 1.0f; a[6] += r < 1.25f; a[7] += r < 1.5625f; a[8] += r < 1.953125f;
+      metric_terms(p, g, a);
     }
   }
   for (int k = 0; k < 9; ++k) {
@@ -246,14 +251,63 @@ __global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, cons
     if (emap) emap[i] = v1 ? fabsf(__fsub_rn(__fadd_rn(__fmul_rn(p0, s), t), g)) / g : 0.f;
     if (v1 && (!cmask || cmask[i])) {
       const float p = clipf(__fadd_rn(__fmul_rn(s, clipf(p0, lo, hi)), t), plo, phi);
-      const float d = p - g;
-      a[0] += 1.0; a[1] += fabsf(d) / g; a[2] += d * d / g; a[3] += d * d;
-      const float pc = fmaxf(p, 1e-5f);
-      const float l = logf(pc) - logf(g);
-      a[4] += l * l;
-      const float r = fmaxf(pc / g, g / pc);
-      a[5] += r < 1.0f; a[6] += r < 1.25f; a[7] += r < 1.5625f; a[8] += r < 1.953125f;
+      metric_terms(p, g, a);
     }
+  }
+  for (int k = 0; k < 9; ++k) {
+    const double r = block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Depth evaluation in global coordinates (restated from /root/reference/metrics/eval_depth.py:250-441 and
+// utils/geometry_utils.py:246-253).  After the first fit (k_depth_fit_ex) gave (s, t): the aligned, post-clipped depth
+// d = clamp(s * pred + t, plo, phi) of EVERY pixel from the ORIGINAL prediction, float32 with the product and the sum rounded separately;
+// then in fp64 from that float32 d: x = (col - cx) * d / fx, y = (row - cy) * d / fy, z = d (integer pixel indices), world = R (x, y, z) + t
+// with the frame's pose, r = |world| rounded once to float32 and written out.  The same pass accumulates the normal-equation sums of the
+// second fit, r against the ground-truth radius over mask1 of the ground-truth DEPTH: n, sum r, sum r^2, sum g_r, sum r * g_r.
+// cam: 16 doubles per frame - fx, fy, cx, cy, R row-major, t - widened from float32 by the host.  The fp64 products and sums stay
+// unfused (__dmul_rn / __dadd_rn): the arithmetic the fixture's generator emulates.
+__global__ __launch_bounds__(MB) void k_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n,
+                                                     int H, int W, float max_depth, float plo, float phi, float s, float t, float* radius,
+                                                     double* part) {
+  __shared__ double sh[MB];
+  double a[5] = {0, 0, 0, 0, 0};
+  const long hw = (long)H * W;
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const long f = i / hw;
+    const long rem = i - f * hw;
+    const int row = (int)(rem / W), col = (int)(rem - (long)row * W);
+    const double* q = cam + f * 16;
+    const double z = clipf(__fadd_rn(__fmul_rn(s, pred[i]), t), plo, phi);
+    const double x = __dmul_rn((double)col - q[2], z) / q[0], y = __dmul_rn((double)row - q[3], z) / q[1];
+    const double wx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[4], x), __dmul_rn(q[5], y)), __dmul_rn(q[6], z)), q[13]);
+    const double wy = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[7], x), __dmul_rn(q[8], y)), __dmul_rn(q[9], z)), q[14]);
+    const double wz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[10], x), __dmul_rn(q[11], y)), __dmul_rn(q[12], z)), q[15]);
+    const float rf = (float)sqrt(__dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz)));
+    radius[i] = rf;
+    if (depth_valid(gt[i], max_depth)) {
+      const double r = rf, g = gt_radius[i];
+      a[0] += 1.0; a[1] += r; a[2] += r * r; a[3] += g; a[4] += r * g;
+    }
+  }
+  for (int k = 0; k < 5; ++k) {
+    const double r = block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + k] = r;
+  }
+}
+
+// the nine metric sums of p' = s * r + t (two roundings, no clamp) against the ground-truth radius on mask1 of the ground-truth DEPTH & custom
+// mask; p' of every pixel goes to rmap when one is asked for
+__global__ __launch_bounds__(MB) void k_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask,
+                                                       long n, float max_depth, float s, float t, double* part, float* rmap) {
+  __shared__ double sh[MB];
+  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const float p = __fadd_rn(__fmul_rn(s, radius[i]), t);
+    if (rmap) rmap[i] = p;
+    if (depth_valid(gt[i], max_depth) && (!cmask || cmask[i])) metric_terms(p, gt_radius[i], a);
   }
   for (int k = 0; k < 9; ++k) {
     const double r = block_sum(a[k], sh);
@@ -313,4 +367,14 @@ void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned 
                              float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s) {
   *nb = nblocks(n);
   hipLaunchKernelGGL(k_depth_metrics_ex, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
+}
+void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
+                         float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s) {
+  *nb = nblocks(n);
+  hipLaunchKernelGGL(k_world_radius, dim3(*nb), dim3(MB), 0, s, pred, gt, gt_radius, cam, n, H, W, max_depth, plo, phi, sc, sh, radius, part);
+}
+void launch_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask, long n, float max_depth,
+                           float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s) {
+  *nb = nblocks(n);
+  hipLaunchKernelGGL(k_radius_metrics, dim3(*nb), dim3(MB), 0, s, radius, gt, gt_radius, cmask, n, max_depth, sc, sh, part, rmap);
 }

@@ -7,8 +7,10 @@ dataset / model classes can be passed as objects, visualisation and the point-cl
 import importlib
 import os
 
+import numpy as np
+
 from .io_utils import prepare_gt_label
-from .metrics import DEPTH_ALIGNMENTS, MetricsManager, depth_evaluation, normal_evaluation
+from .metrics import DEPTH_ALIGNMENTS, MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation
 
 
 def import_class_from_module(module_name, class_name):
@@ -44,6 +46,23 @@ def parse_depth_eval_config(config):
     return alignment, cfg.get("max_depth", 80), clips
 
 
+DEPTH_COORDS = ("camera", "global")
+
+
+def parse_depth_coord(config):
+    """``eval_depth.coord``: ``camera`` (default: the metrics on the depth itself) or ``global`` (the aligned depth moved into the world
+    frame and evaluated as distance from the world origin, ``depth_evaluation_in_global_coord``; least squares only).  An unknown value,
+    or ``global`` with another ``depth_alignment``, is a ``ValueError``."""
+    cfg = config.get("eval_depth") or {}
+    coord = cfg.get("coord", "camera")
+    if coord not in DEPTH_COORDS:
+        raise ValueError(f"eval_depth.coord must be one of {list(DEPTH_COORDS)}, not {coord!r}")
+    alignment = cfg.get("depth_alignment", "lstsq")
+    if coord == "global" and alignment != "lstsq":
+        raise ValueError(f"eval_depth.coord: global aligns with least squares only (depth_alignment: lstsq), not {alignment!r}")
+    return coord
+
+
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
              device_metrics=False, models=None):
     """Run the reference's per-clip loop.  With ``world > 1`` this rank only evaluates clips
@@ -55,8 +74,12 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     clip fills the CUs that one clip's tile tails and under-filled launches leave idle).  Rows / CSV come out in dataset order, identical to the serial loop.
     ``eval_depth.depth_alignment`` (lstsq | median | scale | metric, default lstsq), ``eval_depth.max_depth`` and the four ``eval_depth.*_clip_*`` keys select
     the alignment of the depth metrics on both the host and the device path; an unknown value raises ``ValueError`` before the first clip runs.  A deliberate
-    difference: the reference reads ``depth_alignment`` (eval.py:48) and always aligns with least squares."""
+    difference: the reference reads ``depth_alignment`` (eval.py:48) and always aligns with least squares.
+    ``eval_depth.coord: global`` (default ``camera``) evaluates the depth in world coordinates instead: the radius
+    ``|gt_world_pts|``, the poses of ``prepare_gt_label`` and the sample's intrinsics go to ``depth_evaluation_in_global_coord`` on the host and to
+    ``ug_eval_depth_global`` on the device path; the row keys stay the same.  It goes with ``depth_alignment: lstsq`` only (``ValueError`` otherwise)."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
+    coord = parse_depth_coord(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
     if dataset is None:
         dataset = import_class_from_module("unigeo_amd.harness", config["dataset"])(**parse_dataset_config(config))
@@ -74,7 +97,17 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
         gt = prepare_gt_label(data)
         metric = {"seq_name": seq}
         eng = getattr(getattr(mdl, "pipeline", None), "engine", None) if device_metrics else None
-        if "eval_depth" in config:
+        if "eval_depth" in config and coord == "global":
+            gt_radius = np.linalg.norm(gt["gt_world_pts"].numpy().astype(np.float64), axis=-1).astype(np.float32)      # one rounding
+            K = np.stack([np.asarray(k, dtype=np.float32).reshape(3, 3) for k in data["intrinsics"]], 0)
+            poses = gt["gt_poses"].numpy()
+            if eng is not None:
+                res = eng.eval_depth_global(gt["gt_depths"].numpy(), gt_radius, poses, K, gt["gt_masks"].numpy(), max_depth=max_depth, **clips)
+            else:
+                res = depth_evaluation_in_global_coord(output["pred_depths"], gt["gt_depths"], gt_radius, poses, K, max_depth=max_depth,
+                                                       custom_mask=gt["gt_masks"], align_with_lstsq=True, **clips)
+            metric.update(res[0])
+        elif "eval_depth" in config:
             if eng is not None:
                 res = eng.eval_depth(gt["gt_depths"].numpy(), gt["gt_masks"].numpy(), max_depth=max_depth, alignment=alignment, **clips)
             else:
