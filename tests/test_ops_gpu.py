@@ -356,7 +356,8 @@ def test_flash_attention_full_size_properties(engine):
 
 # ---------------------------------------------------------------------------------------------------
 # Cross-config race screen.  Every tile configuration accumulates K through the same 16x16x32 MFMA chain in the same
-# order, so (split-K aside) all of them must produce bit-identical outputs; a pipeline race in one kernel variant
+# order, so all of them must produce bit-identical outputs (split-K reorders the sum: its own screen, exact on integer data at every factor and on every
+# kernel family, is tests/test_splitk_gpu.py); a pipeline race in one kernel variant
 # (ring slot reuse, counted vmcnt, the asymmetric-loader kernels = configs 34 / 35 / 39, the producer / consumer kernels = 54 / 59 / 60) shows up as a difference.
 # ---------------------------------------------------------------------------------------------------
 def _force(engine, cfg):

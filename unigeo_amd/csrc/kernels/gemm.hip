@@ -154,7 +154,7 @@ __global__ __launch_bounds__(WMW * WNW * 64, (GemmOcc<BM, BN, BK, NST, WMW, WNW>
                 const int tt = t + it - (p.kt >> 1), y = a_y[j] + iy, x = a_x[j] + ix;
                 if (tt >= 0 && tt < p.T && y >= 0 && y < p.Hi * p.ups && x >= 0 && x < p.Wi * p.ups) mk |= 1u << bit;
               }
-          a_mask[j] = a_ok[j] ? mk : 0u;
+          a_mask[j] = (a_ok[j] && kt_lo < kt_hi) ? mk : 0u;   // an empty split has no tap to decode (chunk == C / BK): every row reads zeros
           if (BUFA) {
             const unsigned ap = (unsigned)(((t - (p.kt >> 1)) * p.Hi + a_y[j]) * p.Wi + a_x[j] + cshift);
             a_off[j] = ap * (unsigned)(p.C0 * 2) + a_lc[j] * 16;
