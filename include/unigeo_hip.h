@@ -211,6 +211,32 @@ int ug_eval_depth_global(ug_ctx* ctx, const float* pred_depth /* NULL: resident 
                          const float* cam2world_t44, const float* intrinsics_t33, const unsigned char* custom_mask /* or NULL */, int T, int H,
                          int W, const ug_depth_eval_opts* opts, double* out13, float* radius_map_out /* [T*H*W] or NULL */);
 
+/* Visualisation panels composed on the device: replaces save_depth_normal_maps / colorize / colorize_np (utils/vis_utils.py:38-84,139-199, as
+ * eval.py:58-62 calls them under `vis_depth: True`).  One image per frame, uint8 [T,H,Wp,3] row-major,
+ *   Wp = (rgb ? W : 0) + W + W + (cbar ? 5 + Wc : 0):   rgb | normals | coloured depth | 5 black columns | colour bar.
+ * Every step is one IEEE float32 operation, rounded on its own (fl32), and u8(v) = trunc(v) saturated to 0..255 with NaN -> 0 (numpy's cast is
+ * undefined outside 0..255 - a deliberate difference no reference input reaches):
+ *   rgb        u8(fl32(r * 255))                      r: float32 [T,H,W,3] in [0,1]
+ *   normals    t = fl32(fl32(n * 0.5) + 0.5); u8(fl32(t * 255))
+ *   depth      x = min(max(d, vmin), vmax); u = fl32(fl32(x - vmin) / fl32(vmax - vmin)) (correctly rounded division);
+ *              i = min((int)fl32(u * 256), 255); the bytes are row i of the colour table u8(fl32(lut * 255)), lut: float32 [256,3].
+ *              NaN depth, or vmax == vmin (0 / 0), gives 0,0,0 - matplotlib's "bad" colour
+ *   colour bar u8(fl32(c * 255))                      c: float32 [H,Wc,3], the same strip for every frame
+ * ug_vis_depth_range: out2 = (min, max) of float32 [n], NaN ignored; all NaN or n == 0 gives (0, 0) (the reference's depth_maps.min() / .max()
+ *   propagate NaN instead).  It is a call of its own because the colour bar's tick labels depend on it: the host renders the strip between the
+ *   two calls, and ug_vis_panels takes vmin / vmax as inputs, like colorize(range=...).
+ * depth / normals NULL: the resident outputs of the last ug_dc_run on the current inputs.  rgb_mode: UG_VIS_RGB_NONE no rgb section (rgbs
+ *   ignored), UG_VIS_RGB_HOST rgbs = host [T,H,W,3], UG_VIS_RGB_RESIDENT the input frames of the last ug_dc_set_inputs* (rgbs ignored).
+ *   cbar NULL: no gap and no colour bar, Wc ignored.
+ * Errors (ug_last_error; the context stays usable): NULL lut, panels_out or out2; T, H or W <= 0; n < 0; Wc < 0, or cbar given with Wc == 0;
+ *   unknown rgb_mode; UG_VIS_RGB_HOST with NULL rgbs; a NULL / resident request without a resident tensor of that shape (for normals also when
+ *   the last run had with_normals = 0, or no run followed the last ug_dc_set_inputs*); 2^31 output bytes or more. */
+enum { UG_VIS_RGB_NONE = 0, UG_VIS_RGB_HOST = 1, UG_VIS_RGB_RESIDENT = 2 };
+int ug_vis_depth_range(ug_ctx* ctx, const float* depth /* NULL: resident depth */, long n, float* out2 /* vmin, vmax */);
+int ug_vis_panels(ug_ctx* ctx, const float* depth /* NULL: resident */, const float* normals /* NULL: resident */, const float* rgbs, int rgb_mode,
+                  int T, int H, int W, float vmin, float vmax, const float* lut_256x3, const float* cbar_hwc3 /* [H,Wc,3] or NULL */, int Wc,
+                  unsigned char* panels_out /* host, [T,H,Wp,3] */);
+
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */
 int ug_profile_begin(ug_ctx* ctx);

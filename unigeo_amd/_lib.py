@@ -23,6 +23,7 @@ EXPORTS = [
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
+    "ug_vis_depth_range", "ug_vis_panels",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -117,6 +118,8 @@ def load_library():
     lib.ug_eval_depth_ex.argtypes = [vp, vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_eval_depth_global.argtypes = [vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
+    _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
+                        "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -579,6 +582,59 @@ class Engine:
         out = np.zeros(8, np.float64)
         self._ck(self.lib.ug_eval_normal(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, _ptr(out)))
         return dict(zip(self.NORMAL_KEYS, out.tolist()))
+
+    # ---- visualisation panels on device (depth / normals None: the resident outputs of the last run)
+    VIS_RGB_NONE, VIS_RGB_HOST, VIS_RGB_RESIDENT = 0, 1, 2
+
+    def vis_depth_range(self, depth=None):
+        """(vmin, vmax) of the depth as two ``np.float32``, NaN ignored, ``(0, 0)`` for all-NaN or empty input (``ug_vis_depth_range``)."""
+        out = np.zeros(2, np.float32)
+        if depth is None:
+            T, H, W = self._shape
+            self._ck(self.lib.ug_vis_depth_range(self.ctx, None, T * H * W, _ptr(out)))
+        else:
+            d = _f32(depth)
+            self._ck(self.lib.ug_vis_depth_range(self.ctx, _ptr(d), d.size, _ptr(out)))
+        return out[0], out[1]
+
+    def vis_panels(self, vmin, vmax, lut, depth=None, normals=None, rgbs=None, cbar=None):
+        """The reference's visualisation panels composed on the device (``ug_vis_panels``) -> uint8 ``[T,H,Wp,3]``: rgb | normals | depth through
+        ``lut`` (float32 ``[256,3]``) over ``vmin..vmax`` | 5 black columns | ``cbar`` (float32 ``[H,Wc,3]``).  ``rgbs``: ``None`` (no rgb section),
+        ``"resident"`` (the input frames of the last ``set_inputs*``) or an array ``[T,H,W,3]`` in [0,1]; ``cbar=None`` ends the panel after the
+        depth section."""
+        d = None if depth is None else _f32(depth)
+        n = None if normals is None else _f32(normals)
+        if d is not None:
+            shape = d.shape
+        elif n is not None:
+            shape = n.shape[:3]
+        else:
+            shape = self._shape
+        if len(shape) != 3 or (n is not None and n.shape != (*shape, 3)):
+            raise ValueError("vis_panels: depth must be [T,H,W] and normals [T,H,W,3]")
+        T, H, W = shape
+        r, mode = None, self.VIS_RGB_NONE
+        if isinstance(rgbs, str):
+            if rgbs != "resident":
+                raise ValueError('vis_panels: rgbs must be None, "resident" or an array')
+            mode = self.VIS_RGB_RESIDENT
+        elif rgbs is not None:
+            r, mode = _f32(rgbs), self.VIS_RGB_HOST
+            if r.shape != (T, H, W, 3):
+                raise ValueError("vis_panels: rgbs must be [T,H,W,3]")
+        l = _f32(lut)
+        if l.shape != (256, 3):
+            raise ValueError("vis_panels: lut must be [256,3]")
+        cb, Wc = None, 0
+        if cbar is not None:
+            cb = _f32(cbar)
+            if cb.ndim != 3 or cb.shape[0] != H or cb.shape[2] != 3:
+                raise ValueError("vis_panels: cbar must be [H,Wc,3]")
+            Wc = cb.shape[1]
+        Wp = (W if mode else 0) + 2 * W + (5 + Wc if cb is not None else 0)
+        out = np.empty((T, H, Wp, 3), np.uint8)
+        self._ck(self.lib.ug_vis_panels(self.ctx, _ptr(d), _ptr(n), _ptr(r), mode, T, H, W, float(vmin), float(vmax), _ptr(l), _ptr(cb), Wc, _ptr(out)))
+        return out
 
     # ---- ops (parity tests)
     def op_linear(self, A, W, bias=None, R1=None, c0=1.0, c1=1.0, act=0, geglu=False):

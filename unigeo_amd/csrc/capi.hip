@@ -400,4 +400,56 @@ int ug_eval_normal(ug_ctx* x, const float* pred, const float* gt, const unsigned
   });
 }
 
+// ---------------------------------------------------------------- visualisation panels (kernels/vis.hip)
+int ug_vis_depth_range(ug_ctx* x, const float* depth, long n, float* out2) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(out2 != nullptr, "out2 must not be NULL");
+    UG_REQUIRE(n >= 0, "n must not be negative");
+    UG_REQUIRE(depth || (c.io_ready && n == (long)c.T * c.H * c.W), "no resident depth of that size");
+    out2[0] = out2[1] = 0.f;
+    if (n == 0) return 0;
+    const float* dd = c.d_depth;
+    if (depth) { float* d = c.ws.get<float>(n); UG_CHECK(hipMemcpy(d, depth, (size_t)n * 4, hipMemcpyHostToDevice)); dd = d; }
+    float* part = c.ws.get<float>(2 * 1024 + 2);
+    launch_vis_range(dd, n, part, part + 2 * 1024, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(out2, part + 2 * 1024, 8, hipMemcpyDeviceToHost));
+  });
+}
+
+int ug_vis_panels(ug_ctx* x, const float* depth, const float* normals, const float* rgbs, int rgb_mode, int T, int H, int W, float vmin, float vmax,
+                  const float* lut, const float* cbar, int Wc, unsigned char* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(lut && out, "lut_256x3 and panels_out must not be NULL");
+    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
+    UG_REQUIRE(Wc >= 0 && !(cbar && Wc == 0), "Wc must not be negative, and positive when a colour bar is given");
+    UG_REQUIRE(rgb_mode == UG_VIS_RGB_NONE || rgb_mode == UG_VIS_RGB_HOST || rgb_mode == UG_VIS_RGB_RESIDENT,
+               "unknown rgb_mode (UG_VIS_RGB_NONE / HOST / RESIDENT)");
+    UG_REQUIRE(rgb_mode != UG_VIS_RGB_HOST || rgbs, "rgbs must not be NULL with UG_VIS_RGB_HOST");
+    const long rows = (long)T * H;
+    const long Wp = (rgb_mode != UG_VIS_RGB_NONE ? (long)W : 0) + 2L * W + (cbar ? 5L + Wc : 0);
+    UG_REQUIRE(rows < (1L << 31) && rows * Wp * 3 < (1L << 31), "the panels must stay below 2^31 bytes");
+    const bool same = c.io_ready && T == c.T && H == c.H && W == c.W;
+    UG_REQUIRE(depth || same, "no resident depth of that shape");
+    UG_REQUIRE(normals || (same && c.normals_ready), "no resident normals of that shape (the last run must have had with_normals = 1)");
+    UG_REQUIRE(rgb_mode != UG_VIS_RGB_RESIDENT || same, "no resident input frames of that shape");
+    const long px = rows * W;
+    auto up = [&](const float* h, long n) { float* d = c.ws.get<float>(n); UG_CHECK(hipMemcpyAsync(d, h, (size_t)n * 4, hipMemcpyHostToDevice, c.stream)); return (const float*)d; };
+    const float* dd = depth ? up(depth, px) : c.d_depth;
+    const float* dn = normals ? up(normals, px * 3) : c.d_normals;
+    const float* dr = rgb_mode == UG_VIS_RGB_HOST ? up(rgbs, px * 3) : (rgb_mode == UG_VIS_RGB_RESIDENT ? c.d_frames : nullptr);
+    const float* dl = up(lut, 768);
+    const float* dc = cbar ? up(cbar, (long)H * Wc * 3) : nullptr;
+    const size_t bytes = (size_t)(rows * Wp * 3);
+    unsigned char* dout = (unsigned char*)c.ws.alloc(bytes);
+    launch_vis_panel(dr, dn, dd, dl, dc, dout, T, H, W, Wc, vmin, vmax, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+  });
+}
+
 }  // extern "C"

@@ -288,3 +288,7 @@ void launch_world_radius(const float* pred, const float* gt, const float* gt_rad
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s);
 void launch_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask, long n, float max_depth,
                            float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s);
+// depth / normal visualisation panels (kernels/vis.hip); part: 2 * 1024 floats of scratch, out2 (device) = (vmin, vmax)
+void launch_vis_range(const float* x, long n, float* part, float* out2, hipStream_t s);
+void launch_vis_panel(const float* rgb, const float* normals, const float* depth, const float* lut, const float* cbar, unsigned char* out, int T,
+                      int H, int W, int Wc, float vmin, float vmax, hipStream_t s);

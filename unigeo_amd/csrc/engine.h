@@ -154,6 +154,7 @@ struct Ctx {
   float* d_out_frames = nullptr; float* d_depth = nullptr; float* d_normals = nullptr; float* d_mm = nullptr;
   f16* d_clip_emb = nullptr; f16* d_cond = nullptr; f16* d_lat = nullptr;
   size_t io_mark = 0; bool io_ready = false;
+  bool normals_ready = false;   // d_normals holds the normals of the last dc_run (with_normals = 1) on the current inputs
   // parity instrumentation: when set, dc_run copies the latents after every Euler step to this host buffer ([steps][T*h*w*4] f32)
   float* trace_host = nullptr; int trace_steps = 0;
   // page-locked staging for the host buffers the C ABI hands over (pageable numpy memory): a copy through it is one memcpy + one DMA at

@@ -6,7 +6,9 @@ from .eval import evaluate, parse_dataset_config, parse_depth_coord, parse_metri
 from .dataset import SyntheticGeometryDataset, split_clips
 from .scannetpp import ScannetPPDataset, ScannetPPSequence
 from .distributed import evaluate_sharded
+from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, save_depth_normal_maps
 
 __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_evaluation_in_global_coord",
            "normal_evaluation", "evaluate", "parse_dataset_config", "parse_depth_coord", "parse_metric_config", "import_class_from_module", "SyntheticGeometryDataset",
-           "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence"]
+           "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence",
+           "SPECTRAL_R_LUT", "colorbar_strip", "colorize", "panels_u8", "save_depth_normal_maps"]

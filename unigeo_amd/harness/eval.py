@@ -1,8 +1,9 @@
 """The evaluation loop - mirrors ``/root/reference/eval.py:10-99`` and ``configs/config_utils.py:3-35``.
 
 Differences kept deliberately small: the YAML path is an argument instead of being hard-coded (eval.py:11),
-dataset / model classes can be passed as objects, visualisation and the point-cloud / camera-pose branches
-(not produced by the DepthCrafter / StableNormal plugins) are not reproduced.
+dataset / model classes can be passed as objects, and the point-cloud / camera-pose branches (their inputs are not
+produced by the DepthCrafter / StableNormal plugins) are not reproduced.  ``vis_depth: True`` writes the reference's
+depth / normal panels (eval.py:58-62; ``harness/vis.py``).
 """
 import importlib
 import os
@@ -10,6 +11,7 @@ import os
 import numpy as np
 
 from .io_utils import prepare_gt_label
+from .vis import save_depth_normal_maps
 from .metrics import DEPTH_ALIGNMENTS, MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation
 
 
@@ -77,7 +79,10 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     difference: the reference reads ``depth_alignment`` (eval.py:48) and always aligns with least squares.
     ``eval_depth.coord: global`` (default ``camera``) evaluates the depth in world coordinates instead: the radius
     ``|gt_world_pts|``, the poses of ``prepare_gt_label`` and the sample's intrinsics go to ``depth_evaluation_in_global_coord`` on the host and to
-    ``ug_eval_depth_global`` on the device path; the row keys stay the same.  It goes with ``depth_alignment: lstsq`` only (``ValueError`` otherwise)."""
+    ``ug_eval_depth_global`` on the device path; the row keys stay the same.  It goes with ``depth_alignment: lstsq`` only (``ValueError`` otherwise).
+    ``vis_depth: True`` (the reference's key, eval.py:58-62) writes ``save_dir/depth_{seq}/frame_%04d.webp`` after the clip's metrics: rgb | normals |
+    coloured depth | colour bar, composed on the GPU from the resident outputs under ``device_metrics=True`` and by the numpy mirror otherwise
+    (DESIGN.md section 15).  Rows and CSV do not change."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
     coord = parse_depth_coord(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
@@ -118,6 +123,13 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
                 metric.update(eng.eval_normal(gt["gt_normals"].numpy(), gt["gt_masks"].numpy()))
             else:
                 metric.update(normal_evaluation(output["pred_normals"], gt["gt_normals"], custom_mask=gt["gt_masks"]))
+        if config.get("vis_depth"):
+            vis_dir = os.path.join(save_dir, f"depth_{seq}")
+            os.makedirs(vis_dir, exist_ok=True)
+            if eng is not None:          # depth and normals are still resident: only the bytes of the panels come back
+                save_depth_normal_maps(None, None, vis_dir, rgbs=gt["gt_rgbs"], engine=eng)
+            else:
+                save_depth_normal_maps(output["pred_depths"], output["pred_normals"], vis_dir, rgbs=gt["gt_rgbs"])
         return metric
 
     mine = list(range(rank, len(dataset), world))
