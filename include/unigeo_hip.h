@@ -237,6 +237,37 @@ int ug_vis_panels(ug_ctx* ctx, const float* depth /* NULL: resident */, const fl
                   int T, int H, int W, float vmin, float vmax, const float* lut_256x3, const float* cbar_hwc3 /* [H,Wc,3] or NULL */, int Wc,
                   unsigned char* panels_out /* host, [T,H,Wp,3] */);
 
+/* ScanNet++ clip preparation on the device: replaces the pixel arithmetic of the reference's loader (dataset/scannetpp/scannetpp.py:81-187) and
+ * of its resize transforms (dataset/dataset_core/transforms.py:38-110).  The host decodes the files and builds the tables.
+ * ug_prep_resize_frames: the anti-aliased order-1 input resize (scikit-image's resize recipe: gaussian pre-filter, then grid-mode zoom, both in
+ *   'mirror' mode) as a separable linear map.  frames: host uint8 [T,Hi,Wi,3], channels last.  Per axis a tap table of fixed length,
+ *   row_idx / row_w [Ho,Kr] and col_idx / col_w [Wo,Kc]: output o = sum_k w[o,k] * source[idx[o,k]] (pad a short row with weight 0).  Two
+ *   passes, rows first: mid[t,c,oy,x] = sum_k row_w[oy,k] * frames[t,row_idx[oy,k],x,c] kept in float64, then
+ *   out[t,c,oy,ox] = fl32(sum_k col_w[ox,k] * mid[t,c,oy,col_idx[ox,k]]); both sums in float64 in the table's tap order, ONE rounding to
+ *   float32 at the end.  out: host float32 [T,3,Ho,Wo], planar, 0..255.  The clip is processed in chunks of frames of bounded device size.
+ * ug_prep_gt: the ground truth at the pixels an order-0 target resize keeps.  Output pixel (oy, ox) of frame t is computed from source pixel
+ *   (v, u) = (row_idx[oy], col_idx[ox]) - the identity tables without a resize.  Every fl32 below is ONE IEEE float32 operation:
+ *   depth  d = fl32(float(depth_u16) / depth_divisor)
+ *   camera x = fl32((u - cx) * d / fx), y = fl32((v - cy) * d / fy), each evaluated in float64 from the frame's intrinsics_t33;
+ *          cam_coord = (x, -y, -d)  (OpenGL)
+ *   normal n_j = fl32(fl32(fl32(byte_j / 255) * 2) - 1), n = 0 where all three bytes are 0; normals_u8 NULL: n = 0, and cam_normal_out /
+ *          world_normal_out may then be NULL
+ *   world  world_normal = fl32(M33 n), world_coord = fl32(M33 cam_coord + t), the sums in float64 and rounded once, M33 | t the top three rows
+ *          of the frame's cam2key_t44 (source camera -> key view, row-major)
+ *   bad    = isnan(x) | isnan(y) | isnan(d) | d < 1e-3f | d > max_depth;  all four arrays are 0 on bad, mask = bad ? 0 : 1
+ *   zero   where (Ho, Wo) differs from (Hi, Wi) - the host's order-0 zoom ran - a -0 (y = 0 on the principal row) comes out as +0, as the zoom's
+ *          sum 0 + 1 * v makes it; at the source size the sign of a zero is kept, as the host keeps it
+ *   Outputs are host float32: cam_normal / cam_coord / world_normal / world_coord [T,3,Ho,Wo], mask [T,Ho,Wo].  cam_normal, cam_coord and mask
+ *   equal the host loader's bit for bit; the world arrays differ from its float32 matrix product by that product's rounding.
+ * Errors (ug_last_error; the context stays usable): a NULL required pointer; T, a size or a tap count <= 0; a tap, row or column index outside
+ *   the source (checked on the host before anything is uploaded); 2^31 output elements (T * 3 * Ho * Wo) or more. */
+int ug_prep_resize_frames(ug_ctx* ctx, const unsigned char* frames_thwc3, int T, int Hi, int Wi, int Ho, int Wo, const int* row_idx,
+                          const double* row_w, int Kr, const int* col_idx, const double* col_w, int Kc, float* out /* host, [T,3,Ho,Wo] */);
+int ug_prep_gt(ug_ctx* ctx, const unsigned short* depth_u16 /* [T,Hi,Wi] */, float depth_divisor, const unsigned char* normals_u8 /* [T,Hi,Wi,3] or NULL */,
+               const float* intrinsics_t33, const float* cam2key_t44, int T, int Hi, int Wi, const int* row_idx /* [Ho] */, int Ho,
+               const int* col_idx /* [Wo] */, int Wo, float max_depth, float* cam_normal_out, float* cam_coord_out, float* world_normal_out,
+               float* world_coord_out, float* mask_out);
+
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */
 int ug_profile_begin(ug_ctx* ctx);

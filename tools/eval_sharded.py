@@ -20,7 +20,7 @@ if multi:
     os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1")
     torch.cuda.set_device(local)
     dist.init_process_group("nccl")
-ds = import_class_from_module("unigeo_amd.harness", cfg["dataset"])(**parse_dataset_config(cfg))
+ds = import_class_from_module("unigeo_amd.harness", cfg["dataset"])(device_id=local, **parse_dataset_config(cfg))   # prep: device prepares clips on this rank's GPU
 model = import_class_from_module("unigeo_amd.model", cfg["model_name"])(device_id=local, **cfg["model_params"])
 nfl = max(1, int(os.environ.get("UG_IN_FLIGHT", "1")))
 models = [model] + [import_class_from_module("unigeo_amd.model", cfg["model_name"])(device_id=local, **cfg["model_params"]) for _ in range(nfl - 1)]

@@ -23,7 +23,7 @@ EXPORTS = [
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
-    "ug_vis_depth_range", "ug_vis_panels",
+    "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -120,6 +120,8 @@ def load_library():
     lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
     _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
                         "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
+    _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
+                        "ug_prep_gt": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp]})
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -635,6 +637,56 @@ class Engine:
         out = np.empty((T, H, Wp, 3), np.uint8)
         self._ck(self.lib.ug_vis_panels(self.ctx, _ptr(d), _ptr(n), _ptr(r), mode, T, H, W, float(vmin), float(vmax), _ptr(l), _ptr(cb), Wc, _ptr(out)))
         return out
+
+    # ---- ScanNet++ clip preparation on device
+    def prep_resize_frames(self, frames_u8, Ho, Wo, row_taps=None, col_taps=None):
+        """The loader's anti-aliased input resize (``harness.scannetpp._resize(order=1, anti_alias=True)``) on the device
+        (``ug_prep_resize_frames``): uint8 ``[T,Hi,Wi,3]`` -> float32 ``[T,3,Ho,Wo]``, 0..255.  The per-axis tap tables ``(idx [n_out,K],
+        w [n_out,K])`` come from ``harness.scannetpp.resize_taps`` unless given."""
+        from .harness.scannetpp import resize_taps
+        f = np.asarray(frames_u8)
+        if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3:
+            raise ValueError("prep_resize_frames: frames must be uint8 [T,Hi,Wi,3]")
+        f = np.ascontiguousarray(f)
+        T, Hi, Wi, _ = f.shape
+        Ho, Wo = int(Ho), int(Wo)
+        tabs = []
+        for taps, n_in, n_out in ((row_taps, Hi, Ho), (col_taps, Wi, Wo)):
+            idx, w = resize_taps(n_in, n_out) if taps is None else taps
+            idx, w = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(w, dtype=np.float64)
+            if idx.ndim != 2 or idx.shape != w.shape or idx.shape[0] != n_out:
+                raise ValueError("prep_resize_frames: a tap table must be (idx, w), both [n_out, K]")
+            tabs.append((idx, w))
+        (ri, rw), (ci, cw) = tabs
+        out = np.empty((T, 3, Ho, Wo), np.float32)
+        self._ck(self.lib.ug_prep_resize_frames(self.ctx, _ptr(f), T, Hi, Wi, Ho, Wo, _ptr(ri), _ptr(rw), ri.shape[1], _ptr(ci), _ptr(cw),
+                                                ci.shape[1], _ptr(out)))
+        return out
+
+    def prep_gt(self, depth_u16, normals_u8, intrinsics, cam2key, row_idx, col_idx, depth_divisor=1000.0, max_depth=80.0):
+        """The loader's ground truth at the picked source pixels on the device (``ug_prep_gt``) -> ``(cam_normal, cam_coord, world_normal,
+        world_coord, mask)``, float32 ``[T,3,Ho,Wo]`` x 4 and ``[T,Ho,Wo]``.  ``depth_u16`` ``[T,Hi,Wi]``, ``normals_u8`` ``[T,Hi,Wi,3]`` or
+        ``None`` (zero normals), ``intrinsics`` ``[T,3,3]``, ``cam2key`` ``[T,4,4]`` (source camera -> key view), ``row_idx`` ``[Ho]`` /
+        ``col_idx`` ``[Wo]`` the source row / column of every output row / column (``harness.scannetpp.resize_pick``)."""
+        d = np.asarray(depth_u16)
+        if d.dtype != np.uint16 or d.ndim != 3:
+            raise ValueError("prep_gt: depth must be uint16 [T,Hi,Wi]")
+        d = np.ascontiguousarray(d)
+        T, Hi, Wi = d.shape
+        n = None
+        if normals_u8 is not None:
+            n = np.asarray(normals_u8)
+            if n.dtype != np.uint8 or n.shape != (T, Hi, Wi, 3):
+                raise ValueError("prep_gt: normals must be uint8 [T,Hi,Wi,3]")
+            n = np.ascontiguousarray(n)
+        k, m = _f32(intrinsics).reshape(T, 3, 3), _f32(cam2key).reshape(T, 4, 4)
+        ri, ci = np.ascontiguousarray(row_idx, dtype=np.int32).reshape(-1), np.ascontiguousarray(col_idx, dtype=np.int32).reshape(-1)
+        Ho, Wo = ri.size, ci.size
+        cn, cc, wn, wc = (np.empty((T, 3, Ho, Wo), np.float32) for _ in range(4))
+        mask = np.empty((T, Ho, Wo), np.float32)
+        self._ck(self.lib.ug_prep_gt(self.ctx, _ptr(d), float(depth_divisor), _ptr(n), _ptr(k), _ptr(m), T, Hi, Wi, _ptr(ri), Ho, _ptr(ci), Wo,
+                                     float(max_depth), _ptr(cn), _ptr(cc), _ptr(wn), _ptr(wc), _ptr(mask)))
+        return cn, cc, wn, wc, mask
 
     # ---- ops (parity tests)
     def op_linear(self, A, W, bias=None, R1=None, c0=1.0, c1=1.0, act=0, geglu=False):

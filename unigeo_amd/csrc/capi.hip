@@ -265,6 +265,27 @@ static void eval_depth_lstsq(Ctx& c, const float* pred, const float* gt, const u
   fetch_depth_metrics(c, part, nb, s_, t_, out);
 }
 
+// ---------------------------------------------------------------- clip preparation helpers (ug_prep_*)
+static const size_t PREP_CHUNK_BYTES = (size_t)96 << 20;      // device bytes one chunk of frames may take: the workspace does not grow with T
+static int prep_chunk_frames(int T, size_t per_frame) {
+  const size_t f = PREP_CHUNK_BYTES / (per_frame ? per_frame : 1);
+  return (int)std::min<size_t>((size_t)T, std::max<size_t>(f, 1));
+}
+// [n_out][K] tap table -> tap-major [K][n_out] on the device, after checking every index against the source length
+static void prep_upload_taps(Ctx& c, const int* idx, const double* w, int n_out, int K, int n_in, const int** didx, const double** dw) {
+  std::vector<int> ti((size_t)n_out * K); std::vector<double> tw((size_t)n_out * K);
+  for (int o = 0; o < n_out; ++o)
+    for (int k = 0; k < K; ++k) {
+      const int s = idx[(size_t)o * K + k];
+      UG_REQUIRE(s >= 0 && s < n_in, "a tap index lies outside the source");
+      ti[(size_t)k * n_out + o] = s; tw[(size_t)k * n_out + o] = w[(size_t)o * K + k];
+    }
+  int* di = c.ws.get<int>((long)n_out * K); double* dwt = c.ws.get<double>((long)n_out * K);
+  UG_CHECK(hipMemcpy(di, ti.data(), ti.size() * 4, hipMemcpyHostToDevice));
+  UG_CHECK(hipMemcpy(dwt, tw.data(), tw.size() * 8, hipMemcpyHostToDevice));
+  *didx = di; *dw = dwt;
+}
+
 extern "C" {
 
 int ug_eval_depth(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, double* out) {
@@ -449,6 +470,81 @@ int ug_vis_panels(ug_ctx* x, const float* depth, const float* normals, const flo
     UG_CHECK(hipGetLastError());
     UG_CHECK(hipStreamSynchronize(c.stream));
     UG_CHECK(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+  });
+}
+
+// ---------------------------------------------------------------- ScanNet++ clip preparation (kernels/prep.hip)
+int ug_prep_resize_frames(ug_ctx* x, const unsigned char* frames, int T, int Hi, int Wi, int Ho, int Wo, const int* row_idx, const double* row_w,
+                          int Kr, const int* col_idx, const double* col_w, int Kc, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(frames && row_idx && row_w && col_idx && col_w && out, "frames, the four tap tables and out must not be NULL");
+    UG_REQUIRE(T > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0 && Kr > 0 && Kc > 0, "T, the sizes and the tap counts must be positive");
+    UG_REQUIRE((long)T * 3 * Ho * Wo < (1L << 31), "the output must stay below 2^31 elements");
+    UG_REQUIRE((long)Ho * Kr < (1L << 31) && (long)Wo * Kc < (1L << 31), "tap table size");
+    const int* dri; const double* drw; const int* dci; const double* dcw;
+    prep_upload_taps(c, row_idx, row_w, Ho, Kr, Hi, &dri, &drw);
+    prep_upload_taps(c, col_idx, col_w, Wo, Kc, Wi, &dci, &dcw);
+    const size_t in_f = (size_t)Hi * Wi * 3, mid_f = (size_t)3 * Ho * Wi, out_f = (size_t)3 * Ho * Wo;
+    const int Tc = prep_chunk_frames(T, in_f + mid_f * 8 + out_f * 4);
+    unsigned char* din = (unsigned char*)c.ws.alloc(in_f * Tc);
+    double* dmid = c.ws.get<double>((long)(mid_f * Tc));
+    float* dout = c.ws.get<float>((long)(out_f * Tc));
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+      const int tc = std::min(Tc, T - t0);
+      UG_CHECK(hipMemcpy(din, frames + in_f * t0, in_f * tc, hipMemcpyHostToDevice));
+      launch_prep_resize(din, dri, drw, Kr, dci, dcw, Kc, tc, Hi, Wi, Ho, Wo, dmid, dout, c.stream);
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      UG_CHECK(hipMemcpy(out + out_f * t0, dout, out_f * tc * 4, hipMemcpyDeviceToHost));
+    }
+  });
+}
+
+int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, const unsigned char* normals, const float* K, const float* M, int T,
+               int Hi, int Wi, const int* row_idx, int Ho, const int* col_idx, int Wo, float max_depth, float* cam_normal, float* cam_coord,
+               float* world_normal, float* world_coord, float* mask) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(depth && K && M && row_idx && col_idx, "depth, intrinsics, cam2key, row_idx and col_idx must not be NULL");
+    UG_REQUIRE(cam_coord && world_coord && mask, "cam_coord, world_coord and mask must not be NULL");
+    UG_REQUIRE(!normals || (cam_normal && world_normal), "cam_normal and world_normal must not be NULL when normals are given");
+    UG_REQUIRE(T > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "T and the sizes must be positive");
+    UG_REQUIRE((long)T * 3 * Ho * Wo < (1L << 31), "the outputs must stay below 2^31 elements");
+    for (int i = 0; i < Ho; ++i) UG_REQUIRE(row_idx[i] >= 0 && row_idx[i] < Hi, "a row index lies outside the source");
+    for (int i = 0; i < Wo; ++i) UG_REQUIRE(col_idx[i] >= 0 && col_idx[i] < Wi, "a column index lies outside the source");
+    std::vector<double> tab((size_t)T * 20, 0.0);      // per frame: fx, fy, cx, cy, M33 row-major, t3
+    for (int f = 0; f < T; ++f) {
+      const float* k = K + (size_t)f * 9; const float* m = M + (size_t)f * 16; double* q = tab.data() + (size_t)f * 20;
+      q[0] = k[0]; q[1] = k[4]; q[2] = k[2]; q[3] = k[5];
+      for (int r = 0; r < 3; ++r) { for (int j = 0; j < 3; ++j) q[4 + r * 3 + j] = m[r * 4 + j]; q[13 + r] = m[r * 4 + 3]; }
+    }
+    double* dcam = c.ws.get<double>((long)T * 20); UG_CHECK(hipMemcpy(dcam, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    int* dri = c.ws.get<int>(Ho); UG_CHECK(hipMemcpy(dri, row_idx, (size_t)Ho * 4, hipMemcpyHostToDevice));
+    int* dci = c.ws.get<int>(Wo); UG_CHECK(hipMemcpy(dci, col_idx, (size_t)Wo * 4, hipMemcpyHostToDevice));
+    const size_t src_f = (size_t)Hi * Wi, px_f = (size_t)Ho * Wo;
+    const int Tc = prep_chunk_frames(T, src_f * (normals ? 5 : 2) + px_f * 13 * 4);
+    unsigned short* dd = (unsigned short*)c.ws.alloc(src_f * 2 * Tc);
+    unsigned char* dn = normals ? (unsigned char*)c.ws.alloc(src_f * 3 * Tc) : nullptr;
+    float* o_cn = cam_normal ? c.ws.get<float>((long)(px_f * 3 * Tc)) : nullptr;
+    float* o_wn = world_normal ? c.ws.get<float>((long)(px_f * 3 * Tc)) : nullptr;
+    float* o_cc = c.ws.get<float>((long)(px_f * 3 * Tc));
+    float* o_wc = c.ws.get<float>((long)(px_f * 3 * Tc));
+    float* o_m = c.ws.get<float>((long)(px_f * Tc));
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+      const int tc = std::min(Tc, T - t0);
+      UG_CHECK(hipMemcpy(dd, depth + src_f * t0, src_f * 2 * tc, hipMemcpyHostToDevice));
+      if (normals) { UG_CHECK(hipMemcpy(dn, normals + src_f * 3 * t0, src_f * 3 * tc, hipMemcpyHostToDevice)); }
+      launch_prep_gt(dd, dn, dcam + (size_t)t0 * 20, dri, dci, tc, Hi, Wi, Ho, Wo, depth_divisor, max_depth, o_cn, o_wn, o_cc, o_wc, o_m, c.stream);
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      const size_t n3 = px_f * 3 * tc * 4, off3 = px_f * 3 * t0;
+      if (cam_normal) { UG_CHECK(hipMemcpy(cam_normal + off3, o_cn, n3, hipMemcpyDeviceToHost)); }
+      if (world_normal) { UG_CHECK(hipMemcpy(world_normal + off3, o_wn, n3, hipMemcpyDeviceToHost)); }
+      UG_CHECK(hipMemcpy(cam_coord + off3, o_cc, n3, hipMemcpyDeviceToHost));
+      UG_CHECK(hipMemcpy(world_coord + off3, o_wc, n3, hipMemcpyDeviceToHost));
+      UG_CHECK(hipMemcpy(mask + px_f * t0, o_m, px_f * tc * 4, hipMemcpyDeviceToHost));
+    }
   });
 }
 

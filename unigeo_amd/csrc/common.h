@@ -292,3 +292,10 @@ void launch_radius_metrics(const float* radius, const float* gt, const float* gt
 void launch_vis_range(const float* x, long n, float* part, float* out2, hipStream_t s);
 void launch_vis_panel(const float* rgb, const float* normals, const float* depth, const float* lut, const float* cbar, unsigned char* out, int T,
                       int H, int W, int Wc, float vmin, float vmax, hipStream_t s);
+// ScanNet++ clip preparation (kernels/prep.hip); tap tables tap-major ([K][n_out]), mid: T*3*Ho*Wi doubles of scratch,
+// cam: 20 doubles per frame = fx, fy, cx, cy, M33 row-major, t3; the index tables must have been validated by the caller
+void launch_prep_resize(const unsigned char* frames, const int* ridx, const double* rw, int Kr, const int* cidx, const double* cw, int Kc,
+                        int T, int Hi, int Wi, int Ho, int Wo, double* mid, float* out, hipStream_t s);
+void launch_prep_gt(const unsigned short* depth, const unsigned char* normals, const double* cam, const int* row_idx, const int* col_idx, int T,
+                    int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, float* cam_normal, float* world_normal, float* cam_coord,
+                    float* world_coord, float* mask, hipStream_t s);

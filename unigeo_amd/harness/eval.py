@@ -23,7 +23,8 @@ def parse_dataset_config(config):
     out = {"root": config["root"], "clip_length": config.get("clip_length", 30),
            "clip_overlap": config.get("clip_overlap", 0), "input_size": (config["h"], config["w"]),
            "target_size": (config["h"], config["w"])}
-    for k in ("split", "split_file", "scenes"):      # optional: which scene list the loader walks (default: the split file)
+    for k in ("split", "split_file", "scenes",       # optional: which scene list the loader walks (default: the split file)
+              "prep"):                               # optional: host | device clip preparation of the ScanNet++ loader
         if k in config:
             out[k] = config[k]
     return out

@@ -19,8 +19,13 @@ Pinned by ``tests/golden/scannetpp_golden.npz`` (outputs of the reference's own 
 ``tests/golden/scannetpp_scene``).  The resize step follows scikit-image's published ``transform.resize`` recipe
 (gaussian pre-filter sigma=(s-1)/2 when down-scaling, ``scipy.ndimage.zoom(grid_mode=True, mode='mirror')``) through
 scipy; scikit-image itself is not installed here, so that step is UNPINNED (native-size loads are bit-exact vs the reference).
+
+``prep="device"`` keeps the file decode and the small tables here and runs the pixel arithmetic on the GPU:
+``resize_taps`` / ``resize_pick`` state the two resizes as per-axis tables, ``resize_restated`` is their float64 evaluation on the host.
 """
 import os
+import threading
+import time
 
 import numpy as np
 from PIL import Image
@@ -78,13 +83,105 @@ def _resize(x, ht, wd, order, anti_alias):
     return ndi.zoom(y, [1.0] * lead + [ht / h, wd / w], order=order, mode="mirror", grid_mode=True).astype(x.dtype)
 
 
+def _mirror(i, n):
+    """ndimage's 'mirror' extension (d c b | a b c d | c b a, period 2 (n - 1)) of index i into 0..n-1."""
+    if n == 1:
+        return 0
+    p = 2 * (n - 1)
+    i %= p
+    return i if i < n else p - i
+
+
+def resize_taps(n_in, n_out):
+    """One axis of ``_resize(order=1, anti_alias=True)`` as a table: output ``o`` is ``sum_k w[o, k] * src[idx[o, k]]``.
+    -> (idx int32 [n_out, K], w float64 [n_out, K]).  The gaussian pre-filter (sigma = (s - 1) / 2, radius int(4 sigma + 0.5), mirror) is
+    composed with the two taps of the order-1 ``grid_mode`` zoom; taps that mirror onto the same source index are merged, so a row holds
+    at most 2 r + 2 of them.  K is the longest row; shorter rows are padded with weight 0 on their first index."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("resize_taps: sizes must be positive")
+    if n_in == n_out:                                     # _resize leaves an unchanged axis alone: zoom factor 1, no filter
+        return np.arange(n_in, dtype=np.int32)[:, None], np.ones((n_in, 1), np.float64)
+    s = n_in / n_out
+    sigma = max(0.0, (s - 1) / 2)
+    if sigma > 0:
+        r = int(4.0 * sigma + 0.5)
+        k = np.arange(-r, r + 1)
+        g = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+        g = g / g.sum()
+    else:
+        r, g = 0, np.ones(1)
+    rows = []
+    for o in range(n_out):
+        c = (o + 0.5) * s - 0.5
+        f = int(np.floor(c))
+        t = c - f
+        acc = {}                                          # source index -> weight, in first-appearance order
+        for j, wz in ((f, 1.0 - t), (f + 1, t)):
+            if wz == 0.0:
+                continue
+            j = _mirror(j, n_in)
+            for d in range(-r, r + 1):
+                src = _mirror(j + d, n_in)
+                acc[src] = acc.get(src, 0.0) + wz * g[d + r]
+        rows.append(list(acc.items()))
+    K = max(len(row) for row in rows)
+    idx = np.zeros((n_out, K), np.int32)
+    w = np.zeros((n_out, K), np.float64)
+    for o, row in enumerate(rows):
+        idx[o, :] = row[0][0]
+        for q, (src, wt) in enumerate(row):
+            idx[o, q], w[o, q] = src, wt
+    return idx, w
+
+
+def resize_pick(n_in, n_out):
+    """One axis of ``_resize(order=0)``: the source index each output takes, int32 [n_out] (``floor(c + 0.5)`` of the zoom coordinate
+    ``c = (o + 0.5) * n_in / n_out - 0.5``); the identity without a resize."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError("resize_pick: sizes must be positive")
+    if n_in == n_out:
+        return np.arange(n_in, dtype=np.int32)
+    c = (np.arange(n_out) + 0.5) * (n_in / n_out) - 0.5
+    return np.clip(np.floor(c + 0.5), 0, n_in - 1).astype(np.int32)
+
+
+def resize_restated(x, ht, wd):
+    """``_resize(x, ht, wd, 1, True)`` restated through the tap tables, in float64: the rows first, then the columns, each sum in the
+    table's tap order.  The host mirror of ``ug_prep_resize_frames``; [..., H, W] of any dtype -> float64 [..., ht, wd]."""
+    x = np.asarray(x, dtype=np.float64)
+    ri, rw = resize_taps(x.shape[-2], ht)
+    ci, cw = resize_taps(x.shape[-1], wd)
+    mid = np.zeros(x.shape[:-2] + (ht, x.shape[-1]))
+    for k in range(ri.shape[1]):
+        mid += rw[:, k][:, None] * x[..., ri[:, k], :]
+    out = np.zeros(x.shape[:-2] + (ht, wd))
+    for k in range(ci.shape[1]):
+        out += cw[:, k] * mid[..., ci[:, k]]
+    return out
+
+
+PREP_MODES = ("host", "device")
+
+
 class ScannetPPDataset:
-    """Clip-level dataset in the unified sample format (dataset/Readme.md:22-33); ``dataset[i]`` is one clip."""
+    """Clip-level dataset in the unified sample format (dataset/Readme.md:22-33); ``dataset[i]`` is one clip.
+
+    ``prep="host"`` (default) resizes and prepares the ground truth in numpy.  ``prep="device"`` leaves the host the file decode and the
+    small tables; the anti-aliased frame resize and the ground truth at the target pixels run on the GPU (``ug_prep_resize_frames`` /
+    ``ug_prep_gt``) on ``engine``, or on a weight-less engine of the dataset's own on ``device_id``, created with the
+    first sample.  There is no fallback: without the library or a GPU, ``prep="device"`` raises."""
 
     base_dataset = "scannetpp"
 
     def __init__(self, root, scenes=None, split_file=None, split="test", clip_length=17, clip_overlap=0,
-                 input_size=None, target_size=None, verbose=False, **_):
+                 input_size=None, target_size=None, verbose=False, prep="host", device_id=0, engine=None, **_):
+        if prep not in PREP_MODES:
+            raise ValueError(f"prep must be one of {list(PREP_MODES)}, not {prep!r}")
+        self.prep, self.device_id, self.engine = prep, device_id, engine
+        self._lock = threading.Lock()                       # evaluate(models=[...]) indexes the dataset from several threads
+        self.last_timing = None                             # prep="device": seconds of the last sample's decode / resize / gt stages
         if root is None or not os.path.isdir(root):
             raise FileNotFoundError(f"ScanNet++ root not found: {root!r}")
         if isinstance(scenes, str):
@@ -119,6 +216,11 @@ class ScannetPPDataset:
         if index >= len(self.samples):
             raise IndexError(index)
         seq, _, ids = self.samples[index]
+        if self.prep == "device":
+            out = self._load_clip_device(seq, ids)
+            out["_index"] = index
+            out["_dataset"] = self.base_dataset
+            return out
         out = load_clip(self.root, seq, ids)
         out["_index"] = index
         out["_dataset"] = self.base_dataset
@@ -133,6 +235,62 @@ class ScannetPPDataset:
             for attr in ("cam_normal", "world_normal", "cam_coord", "world_coord", "mask"):
                 out[attr] = [_resize(x, ht, wd, 0, False) for x in out[attr]]
         return out
+
+    def _device_engine(self):
+        if self.engine is None:
+            from .._lib import Engine                        # raises without the library or a GPU: no host fallback
+            self.engine = Engine(self.device_id, workspace_bytes=256 << 20, persist_bytes=1 << 20)
+        return self.engine
+
+    def _load_clip_device(self, seq, ids, keyview_idx=0):
+        """``load_clip`` + the two resizes with the pixel arithmetic on the GPU: same keys, shapes and dtypes."""
+        t0 = time.perf_counter()
+        frames, normals, depth = decode_clip(self.root, seq, ids)
+        t1 = time.perf_counter()
+        T, hi, wi = depth.shape
+        out = {"_base": self.root, "scene_name": "_".join(seq.scene_name.split("/")), "keyview_idx": keyview_idx, "caption": ""}
+        ext = [seq.extrinsics[i].astype(np.float32) for i in ids]
+        K = [seq.intrinsics[i].astype(np.float32) for i in ids]
+        ref = ext[keyview_idx]
+        ref_inv = np.linalg.inv(ref)
+        M = np.stack([ref @ np.linalg.inv(e) for e in ext]).astype(np.float32)      # source camera -> key-view camera, as load_clip
+        K0 = np.broadcast_to(K[0], (T, 3, 3))                                      # scannetpp.py:104: view 0's intrinsics for all views
+        ih, iw = self.input_size if self.input_size is not None else (hi, wi)
+        th, tw = self.target_size if self.target_size is not None else (hi, wi)
+        with self._lock:
+            eng = self._device_engine()
+            images = eng.prep_resize_frames(frames, ih, iw)
+            t2 = time.perf_counter()
+            cn, cc, wn, wc, mask = eng.prep_gt(depth, normals, K0, M, resize_pick(hi, th), resize_pick(wi, tw), depth_divisor=1000.0,
+                                               max_depth=80.0)
+            t3 = time.perf_counter()
+        self.last_timing = {"decode": t1 - t0, "resize": t2 - t1, "gt": t3 - t2}
+        out["images"] = list(images)
+        out["image_names"] = [os.path.basename(seq.rgb_paths[i]) for i in ids]
+        if self.input_size is not None:
+            scale = np.array([[iw / wi] * 3, [ih / hi] * 3, [1.0] * 3], np.float32)
+            K = [k * scale for k in K]
+        out["intrinsics"] = K
+        out.update(cam_normal=list(cn), cam_coord=list(cc), world_normal=list(wn), world_coord=list(wc), mask=list(mask),
+                   extrinsics=[e @ ref_inv for e in ext])
+        return out
+
+
+def decode_clip(root, seq, ids):
+    """The file decode of ``load_clip`` alone: (frames uint8 [T,H,W,3], normals uint8 [T,H,W,3], depth uint16 [T,H,W])."""
+    base = os.path.join(root, seq.scene_name)
+    frames = np.stack([np.array(Image.open(os.path.join(base, seq.rgb_paths[i]))) for i in ids])
+    normals = np.stack([np.array(Image.open(os.path.join(base, seq.normal_paths[i]))) for i in ids])
+    depth = np.stack([np.array(Image.open(os.path.join(base, seq.depth_paths[i]))) for i in ids])
+    if frames.dtype != np.uint8 or normals.dtype != np.uint8 or frames.ndim != 4 or frames.shape[3] != 3 or normals.shape != frames.shape:
+        raise ValueError(f"{base}: images / normals must decode to 8-bit RGB of one size")
+    if depth.dtype != np.uint16:
+        if depth.min() < 0 or depth.max() > 65535:
+            raise ValueError(f"{base}: depth does not fit 16 bits")
+        depth = depth.astype(np.uint16)
+    if depth.shape != frames.shape[:3]:
+        raise ValueError(f"{base}: depth and images differ in size")
+    return frames, normals, depth
 
 
 def load_clip(root, seq, ids, keyview_idx=0):
