@@ -70,6 +70,20 @@ int ug_op_temporal_attn(ug_ctx* ctx, const float* qkv /*[T*HW,3*H*64]*/, int T, 
 int ug_op_attention_generic(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);
 int ug_op_flash_attn_dh(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);   /* fused self-attention, head dim d in {32,48,80,96,112,128}: the CLIP tower's 16 x 80 heads */
 int ug_op_euler_step(ug_ctx* ctx, const float* v, float* latents_inout, long n, float sigma, float sigma_next);
+/* The float32-grade VAE encoder's kernels op by op (kernels/wide.hip and the engine's pair convolution / attention; the reference runs the encoder in
+ * float32 under force_upcast, inside the un-vendored AutoencoderKL).  float32 in and out, no rounding of the inputs to fp16 (weights, bias, gamma and
+ * beta are bound as fp16, as the checkpoint stores them).
+ *   ug_op_split_pair: x [M,C] -> hi = fp16(x), lo = fp16(x - hi), both widened to float32 [M,C]
+ *   ug_op_gn32_pair : GroupNorm (+ SiLU) of x [T,HW,C] in float32, split into its pair
+ *   ug_op_conv_wide : the weight [O][C][k][k] bound and K-doubled exactly as the encoder's convolutions are, x [T,H,W,C] split and convolved with float32
+ *                     output [T,H/stride,W/stride,O]; res (may be NULL): float32 residual added in the epilogue - res_in_place: it is first copied
+ *                     into the output buffer and read from there (the aliasing of a residual block with a shortcut convolution)
+ *   ug_op_attn_wide : qkv [T*S,3C] -> softmax(q k^T / sqrt(C)) v per frame [T*S,C], the three-term products of the mid-block attention */
+int ug_op_split_pair(ug_ctx* ctx, const float* x, long M, int C, float* hi, float* lo);
+int ug_op_gn32_pair(ug_ctx* ctx, const float* x, int T, int HW, int C, int G, float eps, int silu, const float* gamma, const float* beta, float* hi, float* lo);
+int ug_op_conv_wide(ug_ctx* ctx, const float* x_thwc, int T, int H, int W, int C, const float* weight, const float* bias, int O, const float* res, int res_in_place,
+                    int k, int stride, int pad_t, int pad_l, float* out_thwc);
+int ug_op_attn_wide(ug_ctx* ctx, const float* qkv, int T, int S, int C, float* out);
 /* Clip inputs made on the device (kernels/noise.hip; behind ug_dc_set_inputs_ex of the product header).
  *   ug_op_philox_u32  : Philox4x32-10 words of blocks block_offset .. block_offset + nblocks - 1 for key = seed (lo, hi) and counter
  *                       (q lo, q hi, stream, 0) -> out [nblocks][4] uint32 (the generator against the published known-answer vectors)

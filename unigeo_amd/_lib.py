@@ -22,6 +22,7 @@ EXPORTS = [
     "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
+    "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
@@ -137,6 +138,9 @@ def load_library():
     lib.ug_op_attention_generic.argtypes = [vp, vp, ip, ip, ip, ip, vp]
     lib.ug_op_flash_attn_dh.argtypes = [vp, vp, ip, ip, ip, ip, vp]
     lib.ug_op_euler_step.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float]
+    _set_argtypes(lib, {
+        "ug_op_split_pair": [vp, vp, C.c_long, ip, vp, vp], "ug_op_gn32_pair": [vp, vp, ip, ip, ip, ip, C.c_float, ip, vp, vp, vp, vp],
+        "ug_op_conv_wide": [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, ip, ip, ip, ip, ip, vp], "ug_op_attn_wide": [vp, vp, ip, ip, ip, vp]})
     lib.ug_bind_stablenormal.argtypes = [vp, C.POINTER(UNetConfigC), C.POINTER(VAEConfigC), C.POINTER(CLIPConfigC)]
     lib.ug_sn_run.argtypes = [vp, vp, ip, ip, ip, vp, C.c_float, ip, vp, vp, vp, vp]
     lib.ug_sn_unet_forward.argtypes = [vp, ip, vp, vp, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]
@@ -752,6 +756,33 @@ class Engine:
     def op_flash_attn_dh(self, qkv, B, S, H, d):
         q = _f32(qkv); out = np.empty((B * S, H * d), np.float32)
         self._ck(self.lib.ug_op_flash_attn_dh(self.ctx, _ptr(q), B, S, H, d, _ptr(out)))
+        return out
+
+    # the float32-grade VAE encoder's kernels: float32 in / out, inputs not rounded to fp16 (tests/test_wide_gpu.py)
+    def op_split_pair(self, x):
+        x = _f32(x); M, Cc = x.shape
+        hi = np.empty((M, Cc), np.float32); lo = np.empty((M, Cc), np.float32)
+        self._ck(self.lib.ug_op_split_pair(self.ctx, _ptr(x), M, Cc, _ptr(hi), _ptr(lo)))
+        return hi, lo
+
+    def op_gn32_pair(self, x, G, eps, gamma, beta, silu=False):
+        x = _f32(x); T, HW, Cc = x.shape
+        hi = np.empty((T, HW, Cc), np.float32); lo = np.empty((T, HW, Cc), np.float32)
+        self._ck(self.lib.ug_op_gn32_pair(self.ctx, _ptr(x), T, HW, Cc, G, eps, int(silu), _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(hi), _ptr(lo)))
+        return hi, lo
+
+    def op_conv_wide(self, x, weight, bias=None, res=None, res_in_place=False, k=3, stride=1, pad_t=1, pad_l=1):
+        x = _f32(x); T, H, W, Cc = x.shape
+        w = _f32(weight); O = w.shape[0]
+        b = None if bias is None else _f32(bias); r = None if res is None else _f32(res)
+        out = np.empty((T, H // stride, W // stride, O), np.float32)
+        self._ck(self.lib.ug_op_conv_wide(self.ctx, _ptr(x), T, H, W, Cc, _ptr(w), _ptr(b), O, _ptr(r), int(bool(res_in_place)), k, stride, pad_t, pad_l, _ptr(out)))
+        return out
+
+    def op_attn_wide(self, qkv, T, S):
+        q = _f32(qkv); Cc = q.shape[1] // 3
+        out = np.empty((T * S, Cc), np.float32)
+        self._ck(self.lib.ug_op_attn_wide(self.ctx, _ptr(q), T, S, Cc, _ptr(out)))
         return out
 
     def op_euler_step(self, v, lat, sigma, sigma_next):

@@ -504,6 +504,87 @@ int ug_op_euler_step(ug_ctx* x, const float* v, float* lat, long n, float sigma,
   });
 }
 
+// ---- the float32-grade VAE encoder's kernels (kernels/wide.hip; res2d_wide / vattn_wide of engine.hip): float32 in, float32 out, nothing rounded to fp16 on the way in
+static float* up32(Ctx& c, const float* h, long n) {
+  float* d = c.ws.get<float>(n);
+  UG_CHECK(hipMemcpy(d, h, (size_t)n * 4, hipMemcpyHostToDevice));
+  return d;
+}
+static void down32(Ctx& c, const float* d, float* h, long n) {
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(h, d, (size_t)n * 4, hipMemcpyDeviceToHost));
+}
+// pair tensor [M][2C] = [hi | lo] f16 device -> hi [M][C], lo [M][C] float host
+static void down_pair(Ctx& c, const f16* d, float* hi, float* lo, long M, int C) {
+  std::vector<f16> v((size_t)M * 2 * C);
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(v.data(), d, v.size() * 2, hipMemcpyDeviceToHost));
+  for (long m = 0; m < M; ++m)
+    for (int ch = 0; ch < C; ++ch) { hi[m * C + ch] = (float)v[(size_t)m * 2 * C + ch]; lo[m * C + ch] = (float)v[(size_t)m * 2 * C + C + ch]; }
+}
+struct BindScope {   // what a test entry binds leaves the context again on every way out: the bound copies (bind_conv, dup_conv) in c.persist, the raw tensors under `prefix`
+  Ctx& c; size_t mk; std::string prefix;
+  BindScope(Ctx& c_, const std::string& prefix_) : c(c_), mk(c_.persist.mark()), prefix(prefix_) {}
+  ~BindScope() {
+    (void)hipStreamSynchronize(c.stream); c.persist.release(mk);
+    for (auto it = c.raw.begin(); it != c.raw.end();) {
+      if (it->first.compare(0, prefix.size(), prefix) == 0) { (void)hipFree(it->second.dev); it = c.raw.erase(it); } else ++it;
+    }
+  }
+};
+
+int ug_op_split_pair(ug_ctx* x, const float* xin, long M, int C, float* hi, float* lo) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(M >= 1 && C >= 4, "ug_op_split_pair: empty tensor");
+    f16* y = c.ws.get<f16>(M * 2 * C);
+    launch_split_pair(up32(c, xin, M * C), y, M, C, c.stream);
+    down_pair(c, y, hi, lo, M, C);
+  });
+}
+int ug_op_gn32_pair(ug_ctx* x, const float* xin, int T, int HW, int C, int G, float eps, int silu, const float* gamma, const float* beta, float* hi, float* lo) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const long M = (long)T * HW;
+    const float* dx = up32(c, xin, M * C);
+    f16* dg = up16(c, gamma, C); f16* db = up16(c, beta, C);
+    f16* y = c.ws.get<f16>(M * 2 * C);
+    void* ws = c.ws.alloc(gn32_ws_bytes(T, HW, C, G));
+    launch_gn32_pair(dx, y, T, HW, C, G, eps, silu, dg, db, ws, c.stream);
+    down_pair(c, y, hi, lo, M, C);
+  });
+}
+int ug_op_conv_wide(ug_ctx* x, const float* xin, int T, int H, int W, int C, const float* weight, const float* bias, int O, const float* res, int res_in_place,
+                    int k, int stride, int pad_t, int pad_l, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c); BindScope bs(c, "op_conv_wide.");
+    UG_REQUIRE(stride >= 1 && H % stride == 0 && W % stride == 0, "ug_op_conv_wide: stride must divide the frame");
+    UG_REQUIRE(!res_in_place || res, "ug_op_conv_wide: res_in_place needs a residual");
+    const std::string name = "op_conv_wide.conv";
+    upload_raw(c, name + ".weight", 1, {O, C, k, k}, weight);
+    if (bias) upload_raw(c, name + ".bias", 1, {O}, bias);
+    const long Mo = (long)T * (H / stride) * (W / stride);
+    const float* dx = up32(c, xin, (long)T * H * W * C);
+    float* dO = c.ws.get<float>(Mo * O);
+    const float* dR = nullptr;
+    if (res && res_in_place) { UG_CHECK(hipMemcpy(dO, res, (size_t)Mo * O * 4, hipMemcpyHostToDevice)); dR = dO; }   // res2d_wide with a shortcut: the residual is the output buffer
+    else if (res) dR = up32(c, res, Mo * O);
+    test_conv_wide(c, name, bias != nullptr, dx, T, H, W, C, O, k, stride, pad_t, pad_l, dO, dR);
+    finish_binding(c, "op_conv_wide.");   // both tensors were used
+    down32(c, dO, out, Mo * O);
+  });
+}
+int ug_op_attn_wide(ug_ctx* x, const float* qkv, int T, int S, int C, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const long M = (long)T * S;
+    const float* dq = up32(c, qkv, M * 3 * C);
+    float* dO = c.ws.get<float>(M * C);
+    attn_wide_core(c, dq, T, S, C, dO);
+    down32(c, dO, out, M * C);
+  });
+}
+
 // ---- clip inputs made on the device (kernels/noise.hip): op-level entry points of the parity tests
 int ug_op_philox_u32(ug_ctx* x, uint64_t seed, uint32_t stream, uint64_t block_offset, long nblocks, uint32_t* out) {
   UG_TRY(x, {

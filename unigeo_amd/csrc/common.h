@@ -257,7 +257,7 @@ void launch_gn32_pair(const float* X, f16* Y, int T, int HW, int C, int G, float
                       void* ws, hipStream_t s);                                          // GroupNorm(+SiLU) f32 -> pair
 void launch_qk_terms(const float* qkv, f16* Aq, f16* Bk, long M, int C, hipStream_t s);
 void launch_vt_terms(const float* qkv, f16* Vt, int B, int S, int Spad, int C, hipStream_t s);
-void launch_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long rows, int S, hipStream_t s);
+void launch_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long rows, int S, float pscale, hipStream_t s);   // P = [pl | ph | ph] of pscale * softmax
 
 // calibration probe (kernels/probe.hip): chip-wide fp16 MFMA rate, operands in registers; scratch >= 256 * 512 floats
 float bench_mfma_peak(float* scratch, int iters, hipStream_t s);

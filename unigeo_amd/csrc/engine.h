@@ -204,6 +204,12 @@ f16* clip_embed(Ctx& c, const f16* video_m11, int T, int H, int W);       // [T,
 f16* vae_encode_v(Ctx& c, VAE& v, const f16* x8, int T, int H, int W, bool fp32_grade);
 // the unfused attention path (scores GEMM, softmax, value GEMM) on its own: exposed for the op-level tests
 void test_unfused_attention(Ctx& c, const f16* qkv, long ld, int B, int S, int H, int d, f16* out, long ldo);
+// the float32-grade VAE encoder's pieces on their own (kernels/wide.hip): exposed for the op-level tests
+// attention core of the mid block: qkv fp32 [T*S, 3C] -> ao fp32 [T*S, C] (ao may alias qkv)
+void attn_wide_core(Ctx& c, const float* qkv, int T, int S, int C, float* ao);
+// raw tensors name + ".weight" [cout][cin][k][k] (+ ".bias") -> bind_conv -> dup_conv; x fp32 [T,H,W,cin] -> split_pair -> conv_w -> out fp32 (+ res fp32, may be out)
+void test_conv_wide(Ctx& c, const std::string& name, bool bias, const float* x, int T, int H, int W, int cin, int cout, int k, int stride, int pad_t, int pad_l,
+                    float* out, const float* res);
 
 // ---- StableNormal (sn_graphs.inc) ----
 void bind_sn(Ctx& c, const UNetCfg& ucfg, const VAECfg& vcfg, const CLIPCfg& dcfg, const std::string& prefix);   // "<prefix>{vae,unet_yoso,controlnet_yoso,unet,controlnet_dino,dino}."

@@ -1300,13 +1300,14 @@ static void res2d_wide(Ctx& c, const Res2D& r, const float* x, int cin, int T, i
   conv_w(c, a, T, h, w, r.c2, 1, 1, 1, out, res);
   c.ws.release(mk);
 }
-static void vattn_wide(Ctx& c, const VAttn& at, const float* x, int T, int hw, int G, float* out) {
-  const int C = at.C, S = hw, Spad = pad8(S); const long M = (long)T * hw;
+// the attention core of vattn_wide: qkv fp32 [T*S, 3C] -> ao fp32 [T*S, C] = softmax(q k^T / sqrt(C)) v per frame, every product in three terms.
+// ao may alias qkv (its terms are in Aq / Bk / Vt before the PV GEMM writes).  Also the op-level tests' entry (engine.h).
+// The probabilities are split as 2^12 p: lo = p - fp16(p) is an fp16 subnormal (a multiple of 2^-24) whenever p < 2^-3, which a flat softmax row (p ~ 1 / S)
+// is everywhere; scaled, the pair keeps its 22 bits down to p = 2^-15 and 4096 p <= 4096 stays far inside fp16.  The PV GEMM's c0 undoes the power of two exactly.
+static constexpr float kPScale = 4096.f;
+void attn_wide_core(Ctx& c, const float* qkv, int T, int S, int C, float* ao) {
+  const int Spad = pad8(S); const long M = (long)T * S;
   const size_t mk = c.ws.mark();
-  f16* xn = c.ws.get<f16>(M * 2 * C);
-  gn32(c, x, T, hw, G, at.gn, 0, xn);
-  float* qkv = c.ws.get<float>(M * 3 * C);
-  { Epi e; e.flags = UG_F_OUT_F32; e.alg = 0.5f; linear(c, xn, M, at.qkv, (f16*)qkv, e); }
   f16* Aq = c.ws.get<f16>(M * 3 * C); f16* Bk = c.ws.get<f16>(M * 3 * C);
   launch_qk_terms(qkv, Aq, Bk, M, C, c.stream);
   f16* Vt = c.ws.get<f16>((long)T * C * 3 * Spad);
@@ -1320,16 +1321,41 @@ static void vattn_wide(Ctx& c, const VAttn& at, const float* x, int T, int hw, i
   f16* P = c.ws.get<f16>((long)T * S * 3 * Spad);
   {
     ProfScope ps(c, "softmax_rows", 0, (double)T * S * Spad * 10.0);
-    launch_softmax_pair(sc, Spad, P, Spad, (long)T * S, S, c.stream);
+    launch_softmax_pair(sc, Spad, P, Spad, (long)T * S, S, kPScale, c.stream);
   }
-  float* ao = qkv;   // qkv is dead (Aq / Bk / Vt hold its terms)
   GemmP q; memset(&q, 0, sizeof(q));
-  q.A0 = P; q.C0 = 3 * Spad; q.M = S; q.N = C; q.K = 3 * Spad; q.W = Vt; q.ldw = 3 * Spad; q.c0 = 1.f;
+  q.A0 = P; q.C0 = 3 * Spad; q.M = S; q.N = C; q.K = 3 * Spad; q.W = Vt; q.ldw = 3 * Spad; q.c0 = 1.f / kPScale;
   q.Out = ao; q.ldo = C; q.flags = UG_F_OUT_F32; q.nb_inner = 1;
   q.sA_o = (long)S * 3 * Spad; q.sW_o = (long)C * 3 * Spad; q.sO_o = (long)S * C;
   run_gemm(c, q, T, "gemm_attn_pv", 1.f / 3.f);
+  c.ws.release(mk);
+}
+static void vattn_wide(Ctx& c, const VAttn& at, const float* x, int T, int hw, int G, float* out) {
+  const int C = at.C; const long M = (long)T * hw;
+  const size_t mk = c.ws.mark();
+  f16* xn = c.ws.get<f16>(M * 2 * C);
+  gn32(c, x, T, hw, G, at.gn, 0, xn);
+  float* qkv = c.ws.get<float>(M * 3 * C);
+  { Epi e; e.flags = UG_F_OUT_F32; e.alg = 0.5f; linear(c, xn, M, at.qkv, (f16*)qkv, e); }
+  float* ao = qkv;   // qkv is dead once the core has its terms
+  attn_wide_core(c, qkv, T, hw, C, ao);
   split_pair(c, ao, xn, M, C);
   { Epi e; e.flags = UG_F_OUT_F32 | UG_F_R1_F32; e.alg = 0.5f; e.R1 = (const f16*)x; e.ldr1 = C; e.c1 = 1.f; linear(c, xn, M, at.out, (f16*)out, e); }   // + float32 residual in the epilogue
+  c.ws.release(mk);
+}
+// one convolution of the float32-grade encoder on its own (op-level tests): the raw tensors name + ".weight" [cout][cin][k][k] (+ ".bias") bound as every
+// convolution is (bind_conv), K-doubled (dup_conv), then x fp32 [T,H,W,cin] -> hi/lo pair -> conv_w -> out fp32 [T,H/stride,W/stride,cout] (+ res, which may be out).
+// The bound copies live in c.persist: the caller releases its mark.
+void test_conv_wide(Ctx& c, const std::string& name, bool bias, const float* x, int T, int H, int W, int cin, int cout, int k, int stride, int pad_t, int pad_l,
+                    float* out, const float* res) {
+  UG_REQUIRE(cin % 8 == 0, "test_conv_wide: input channels must be a multiple of 8");
+  const Conv base = bind_conv(c, name, cin, cout, 1, k, bias);
+  const Conv cw = dup_conv(c, base);
+  const long M = (long)T * H * W;
+  const size_t mk = c.ws.mark();
+  f16* xp = c.ws.get<f16>(M * 2 * cin);
+  split_pair(c, x, xp, M, cin);
+  conv_w(c, xp, T, H, W, cw, stride, pad_t, pad_l, out, res);
   c.ws.release(mk);
 }
 

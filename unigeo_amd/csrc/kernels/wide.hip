@@ -4,11 +4,22 @@
 //
 // The checkpoint's VAE weights are fp16 values (variant="fp16"), merely widened to fp32 by the up-cast, so a layer
 // y = W x with fp32 x is reproduced exactly (to fp32 rounding of the sum) by splitting only the ACTIVATION:
-//     x = hi + lo,  hi = fp16(x),  lo = fp16(x - hi)            (22 significant bits; |lo| floor 2^-24)
+//     x = hi + lo,  hi = fp16(x),  lo = fp16(x - hi)
 //     y = W hi + W lo                                           (fp16 x fp16 products are exact in the fp32 accumulator)
 // i.e. the same implicit-GEMM kernels run on a K-doubled problem: A' = [hi | lo] per tap, W' = [W | W].  Everything
 // between the GEMMs - residual stream, GroupNorm statistics and affine, SiLU, softmax - lives here in fp32.
-// Activation x activation products (the mid-block attention's QK^T and PV) need three terms: a b ~ ah bh + al bh + ah bl.
+// Activation x activation products (the mid-block attention's QK^T and PV) need three terms: a b ~ al bh + ah bl + ah bh, the two
+// small ones FIRST along K: the GEMM's accumulator is one fp32 chain in K order, and every step rounds at the size of the running sum - small terms
+// added to the finished ah bh sum cost 2/3 of the chain's steps at full size (measured on flat softmax rows with v of mean 1: DESIGN.md section 3).
+//
+// What the pair carries: |x - hi| <= 2^-12 |x|, and lo rounds that to 11 more bits - 22 significant bits - only while lo is a NORMAL fp16 number,
+// |x - hi| >= 2^-14, i.e. for |x| >= 2^-3 or so.  Below that lo is an fp16 subnormal, a multiple of 2^-24: the pair then has an ABSOLUTE error of up to
+// 2^-25 per element whatever |x| is (the MFMA does not flush subnormal operands, so nothing worse), and |x| < 2^-25 is lost altogether.
+//   * conv / linear inputs (split_pair, gn32_pair, qk_terms, vt_terms) are split as they are.  At unit activation scale the floor is below float32's
+//     own rounding of the sum (tests/test_wide_gpu.py: the pair GEMM is as close to fp64 as a float32 GEMM); it grows as the tensor's scale shrinks,
+//     bounded per output by 2^-25 sum_k |w_k| (pinned by the same tests at scales 2^-8 and 2^-12).  A per-tensor scale is not applied.
+//   * softmax probabilities are at most 1 and ~ 1 / S on a flat row - all subnormal lo halves.  k_softmax_pair splits 2^12 p instead (22 bits down to
+//     p = 2^-15, floor 2^-37) and the PV GEMM's c0 = 2^-12 undoes the scale exactly.
 //
 // All kernels are HBM-bound elementwise / row passes over fp32 tensors: 16-byte loads, 8-byte fp16 stores.
 #include "../common.h"
@@ -244,7 +255,7 @@ void launch_gn32_pair(const float* X, f16* Y, int T, int HW, int C, int G, float
 }
 
 // ---------------------------------------------------------------------------------------------------- attention terms
-// qkv fp32 [M, 3C] -> Aq [M, 3C] = [qh | ql | qh], Bk [M, 3C] = [kh | kh | kl]   (QK^T ~ qh kh + ql kh + qh kl)
+// qkv fp32 [M, 3C] -> Aq [M, 3C] = [ql | qh | qh], Bk [M, 3C] = [kh | kl | kh]   (QK^T ~ ql kh + qh kl + qh kh: small terms first)
 __global__ __launch_bounds__(256) void k_qk_terms(const float* qkv, f16* Aq, f16* Bk, long M, int C) {
   const int nv = C / 4;
   const long n = M * nv;
@@ -254,8 +265,8 @@ __global__ __launch_bounds__(256) void k_qk_terms(const float* qkv, f16* Aq, f16
     split4(*(const f32x4*)(qkv + m * 3 * C + c), qh, ql);
     split4(*(const f32x4*)(qkv + m * 3 * C + C + c), kh, kl);
     f16* a = Aq + m * 3 * C + c; f16* b = Bk + m * 3 * C + c;
-    *(h4*)a = qh; *(h4*)(a + C) = ql; *(h4*)(a + 2 * C) = qh;
-    *(h4*)b = kh; *(h4*)(b + C) = kh; *(h4*)(b + 2 * C) = kl;
+    *(h4*)a = ql; *(h4*)(a + C) = qh; *(h4*)(a + 2 * C) = qh;
+    *(h4*)b = kh; *(h4*)(b + C) = kl; *(h4*)(b + 2 * C) = kh;
   }
 }
 void launch_qk_terms(const float* qkv, f16* Aq, f16* Bk, long M, int C, hipStream_t s) {
@@ -264,7 +275,7 @@ void launch_qk_terms(const float* qkv, f16* Aq, f16* Bk, long M, int C, hipStrea
   UG_CHECK(hipGetLastError());
 }
 
-// V of qkv fp32 [B*S, 3C] -> Vt [B][C][3*Spad] = [vh^T | vh^T | vl^T], zero tails   (PV ~ ph vh + pl vh + ph vl)
+// V of qkv fp32 [B*S, 3C] -> Vt [B][C][3*Spad] = [vh^T | vl^T | vh^T], zero tails   (PV ~ pl vh + ph vl + ph vh: small terms first)
 __global__ void k_vt_terms(const float* qkv, f16* Vt, int S, int Spad, int C) {
   __shared__ float tile[32][33];
   const int b = blockIdx.z, s0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
@@ -279,7 +290,7 @@ __global__ void k_vt_terms(const float* qkv, f16* Vt, int S, int Spad, int C) {
       const float x = tile[threadIdx.x][i];
       const f16 h = (f16)x, l = (f16)(x - (float)h);
       f16* d = Vt + ((long)b * C + c) * 3 * Spad + s;
-      d[0] = h; d[Spad] = h; d[2 * Spad] = l;
+      d[0] = h; d[Spad] = l; d[2 * Spad] = h;
     }
   }
 }
@@ -288,8 +299,9 @@ void launch_vt_terms(const float* qkv, f16* Vt, int B, int S, int Spad, int C, h
   UG_CHECK(hipGetLastError());
 }
 
-// row softmax of fp32 scores [rows, ld_in] (first S valid) -> P [rows, 3*Spad] = [ph | pl | ph], zero tails; one wave per row
-__global__ __launch_bounds__(256) void k_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long rows, int S) {
+// row softmax of fp32 scores [rows, ld_in] (first S valid) -> P [rows, 3*Spad] = [pl | ph | ph] of pscale * p, zero tails; one wave per row.
+// pscale: a power of two that lifts the probabilities out of fp16's subnormal range before the split (see the header; the PV GEMM's c0 = 1 / pscale undoes it)
+__global__ __launch_bounds__(256) void k_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long rows, int S, float pscale) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -305,12 +317,14 @@ __global__ __launch_bounds__(256) void k_softmax_pair(const float* in, long ld_i
   const float inv = 1.0f / sum;
   f16* y = out + row * 3 * Spad;
   for (int i = lane; i < Spad; i += 64) {
-    const float pr = (i < S) ? expf(x[i] - mx) * inv : 0.f;
+    const float pr = (i < S) ? expf(x[i] - mx) * inv * pscale : 0.f;   // (a power of two: the same bits as p, exponent shifted)
     const f16 h = (f16)pr, l = (f16)(pr - (float)h);
-    y[i] = h; y[Spad + i] = l; y[2 * Spad + i] = h;
+    y[i] = l; y[Spad + i] = h; y[2 * Spad + i] = h;
   }
 }
-void launch_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long rows, int S, hipStream_t s) {
-  hipLaunchKernelGGL(k_softmax_pair, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, in, ld_in, out, Spad, rows, S);
+void launch_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long rows, int S, float pscale, hipStream_t s) {
+  int ex = 0;
+  UG_REQUIRE(pscale >= 1.f && pscale <= 32768.f && frexpf(pscale, &ex) == 0.5f, "softmax_pair: pscale must be a power of two with pscale * p inside fp16");
+  hipLaunchKernelGGL(k_softmax_pair, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, in, ld_in, out, Spad, rows, S, pscale);
   UG_CHECK(hipGetLastError());
 }
