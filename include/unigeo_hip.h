@@ -267,6 +267,24 @@ int ug_prep_gt(ug_ctx* ctx, const unsigned short* depth_u16 /* [T,Hi,Wi] */, flo
                const float* intrinsics_t33, const float* cam2key_t44, int T, int Hi, int Wi, const int* row_idx /* [Ho] */, int Ho,
                const int* col_idx /* [Wo] */, int Wo, float max_depth, float* cam_normal_out, float* cam_coord_out, float* world_normal_out,
                float* world_coord_out, float* mask_out);
+/* ug_prep_gt with two explicit switches, for loaders whose depth arithmetic or geometry differs from ScanNet++'s (harness/rgbd.py; DESIGN.md
+ * section 17).  Everything ug_prep_gt documents holds, except:
+ *   UG_PREP_DEPTH_F64  the depth stays float64 from the division to the end of the back-projection (bonn.py:123-134), one rounding per component:
+ *                      d64 = double(depth_u16) / double(depth_divisor)
+ *                      x = fl32((u - cx) * d64 / fx), y = fl32((v - cy) * d64 / fy), d = fl32(d64);  cam_coord = (x, -y, -d)
+ *                      bad tests d, the float32 value, as the host tests -cam_coord[2].  A raw 0 gives d = 0: masked, all outputs +0 - what the
+ *                      host's NaN -> masked -> 0 gives.  Without the flag d = fl32(float(depth_u16) / depth_divisor) enters the float64 expressions.
+ *   UG_PREP_ZOOMED     the "zero" rule as an argument instead of a size comparison: with the flag a -0 comes out as +0 (the host's order-0 zoom
+ *                      ran on the targets), without it the sign of a zero is kept - also where (Ho, Wo) differs from (Hi, Wi) because the tables
+ *                      describe a crop, which the host does by slicing.
+ * ug_prep_gt(...) is ug_prep_gt_ex(..., (Ho != Hi || Wo != Wi) ? UG_PREP_ZOOMED : 0).
+ * Errors, in addition: a flag bit other than the two above (the bits are named in ug_last_error; the context stays usable). */
+#define UG_PREP_DEPTH_F64 1   /* depth kept in float64 through the back-projection (Bonn) */
+#define UG_PREP_ZOOMED    2   /* the host's order-0 zoom ran on the targets: -0 comes out as +0 */
+int ug_prep_gt_ex(ug_ctx* ctx, const unsigned short* depth_u16 /* [T,Hi,Wi] */, float depth_divisor, const unsigned char* normals_u8 /* [T,Hi,Wi,3] or NULL */,
+                  const float* intrinsics_t33, const float* cam2key_t44, int T, int Hi, int Wi, const int* row_idx /* [Ho] */, int Ho,
+                  const int* col_idx /* [Wo] */, int Wo, float max_depth, float* cam_normal_out, float* cam_coord_out, float* world_normal_out,
+                  float* world_coord_out, float* mask_out, unsigned flags);
 
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */

@@ -24,7 +24,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
-    "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt",
+    "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -58,6 +58,7 @@ class DepthEvalOptsC(C.Structure):
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_ALIGN_* of include/unigeo_hip.h
+PREP_DEPTH_F64, PREP_ZOOMED = 1, 2                                       # UG_PREP_* of include/unigeo_hip.h
 
 _lib = None
 
@@ -122,7 +123,8 @@ def load_library():
     _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
                         "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
     _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
-                        "ug_prep_gt": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp]})
+                        "ug_prep_gt": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp],
+                        "ug_prep_gt_ex": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp, C.c_uint]})
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -667,11 +669,14 @@ class Engine:
                                                 ci.shape[1], _ptr(out)))
         return out
 
-    def prep_gt(self, depth_u16, normals_u8, intrinsics, cam2key, row_idx, col_idx, depth_divisor=1000.0, max_depth=80.0):
-        """The loader's ground truth at the picked source pixels on the device (``ug_prep_gt``) -> ``(cam_normal, cam_coord, world_normal,
+    def prep_gt(self, depth_u16, normals_u8, intrinsics, cam2key, row_idx, col_idx, depth_divisor=1000.0, max_depth=80.0, depth_f64=False,
+                zoomed=None):
+        """The loader's ground truth at the picked source pixels on the device (``ug_prep_gt_ex``) -> ``(cam_normal, cam_coord, world_normal,
         world_coord, mask)``, float32 ``[T,3,Ho,Wo]`` x 4 and ``[T,Ho,Wo]``.  ``depth_u16`` ``[T,Hi,Wi]``, ``normals_u8`` ``[T,Hi,Wi,3]`` or
         ``None`` (zero normals), ``intrinsics`` ``[T,3,3]``, ``cam2key`` ``[T,4,4]`` (source camera -> key view), ``row_idx`` ``[Ho]`` /
-        ``col_idx`` ``[Wo]`` the source row / column of every output row / column (``harness.scannetpp.resize_pick``)."""
+        ``col_idx`` ``[Wo]`` the source row / column of every output row / column (``harness.scannetpp.resize_pick``).  ``depth_f64`` keeps the
+        depth in float64 through the back-projection (``UG_PREP_DEPTH_F64``); ``zoomed`` says whether the host's order-0 zoom ran on the
+        targets (``UG_PREP_ZOOMED``), ``None`` = it ran iff ``(Ho, Wo) != (Hi, Wi)``, the rule of ``ug_prep_gt``."""
         d = np.asarray(depth_u16)
         if d.dtype != np.uint16 or d.ndim != 3:
             raise ValueError("prep_gt: depth must be uint16 [T,Hi,Wi]")
@@ -688,8 +693,11 @@ class Engine:
         Ho, Wo = ri.size, ci.size
         cn, cc, wn, wc = (np.empty((T, 3, Ho, Wo), np.float32) for _ in range(4))
         mask = np.empty((T, Ho, Wo), np.float32)
-        self._ck(self.lib.ug_prep_gt(self.ctx, _ptr(d), float(depth_divisor), _ptr(n), _ptr(k), _ptr(m), T, Hi, Wi, _ptr(ri), Ho, _ptr(ci), Wo,
-                                     float(max_depth), _ptr(cn), _ptr(cc), _ptr(wn), _ptr(wc), _ptr(mask)))
+        if zoomed is None:
+            zoomed = (Ho, Wo) != (Hi, Wi)
+        flags = (PREP_DEPTH_F64 if depth_f64 else 0) | (PREP_ZOOMED if zoomed else 0)
+        self._ck(self.lib.ug_prep_gt_ex(self.ctx, _ptr(d), float(depth_divisor), _ptr(n), _ptr(k), _ptr(m), T, Hi, Wi, _ptr(ri), Ho, _ptr(ci), Wo,
+                                        float(max_depth), _ptr(cn), _ptr(cc), _ptr(wn), _ptr(wc), _ptr(mask), flags))
         return cn, cc, wn, wc, mask
 
     # ---- ops (parity tests)

@@ -501,11 +501,16 @@ int ug_prep_resize_frames(ug_ctx* x, const unsigned char* frames, int T, int Hi,
   });
 }
 
-int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, const unsigned char* normals, const float* K, const float* M, int T,
-               int Hi, int Wi, const int* row_idx, int Ho, const int* col_idx, int Wo, float max_depth, float* cam_normal, float* cam_coord,
-               float* world_normal, float* world_coord, float* mask) {
+int ug_prep_gt_ex(ug_ctx* x, const unsigned short* depth, float depth_divisor, const unsigned char* normals, const float* K, const float* M, int T,
+                  int Hi, int Wi, const int* row_idx, int Ho, const int* col_idx, int Wo, float max_depth, float* cam_normal, float* cam_coord,
+                  float* world_normal, float* world_coord, float* mask, unsigned flags) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
+    const unsigned unknown = flags & ~(unsigned)(UG_PREP_DEPTH_F64 | UG_PREP_ZOOMED);
+    if (unknown) {
+      char hex[16]; snprintf(hex, sizeof hex, "0x%x", unknown);
+      throw std::runtime_error(std::string("ug_prep_gt_ex: unknown flag bits ") + hex + " (UG_PREP_DEPTH_F64 | UG_PREP_ZOOMED)");
+    }
     UG_REQUIRE(depth && K && M && row_idx && col_idx, "depth, intrinsics, cam2key, row_idx and col_idx must not be NULL");
     UG_REQUIRE(cam_coord && world_coord && mask, "cam_coord, world_coord and mask must not be NULL");
     UG_REQUIRE(!normals || (cam_normal && world_normal), "cam_normal and world_normal must not be NULL when normals are given");
@@ -535,7 +540,8 @@ int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, cons
       const int tc = std::min(Tc, T - t0);
       UG_CHECK(hipMemcpy(dd, depth + src_f * t0, src_f * 2 * tc, hipMemcpyHostToDevice));
       if (normals) { UG_CHECK(hipMemcpy(dn, normals + src_f * 3 * t0, src_f * 3 * tc, hipMemcpyHostToDevice)); }
-      launch_prep_gt(dd, dn, dcam + (size_t)t0 * 20, dri, dci, tc, Hi, Wi, Ho, Wo, depth_divisor, max_depth, o_cn, o_wn, o_cc, o_wc, o_m, c.stream);
+      launch_prep_gt(dd, dn, dcam + (size_t)t0 * 20, dri, dci, tc, Hi, Wi, Ho, Wo, depth_divisor, max_depth, (flags & UG_PREP_DEPTH_F64) != 0,
+                     (flags & UG_PREP_ZOOMED) != 0, o_cn, o_wn, o_cc, o_wc, o_m, c.stream);
       UG_CHECK(hipGetLastError());
       UG_CHECK(hipStreamSynchronize(c.stream));
       const size_t n3 = px_f * 3 * tc * 4, off3 = px_f * 3 * t0;
@@ -546,6 +552,13 @@ int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, cons
       UG_CHECK(hipMemcpy(mask + px_f * t0, o_m, px_f * tc * 4, hipMemcpyDeviceToHost));
     }
   });
+}
+
+int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, const unsigned char* normals, const float* K, const float* M, int T,
+               int Hi, int Wi, const int* row_idx, int Ho, const int* col_idx, int Wo, float max_depth, float* cam_normal, float* cam_coord,
+               float* world_normal, float* world_coord, float* mask) {
+  return ug_prep_gt_ex(x, depth, depth_divisor, normals, K, M, T, Hi, Wi, row_idx, Ho, col_idx, Wo, max_depth, cam_normal, cam_coord, world_normal,
+                       world_coord, mask, (Ho != Hi || Wo != Wi) ? UG_PREP_ZOOMED : 0);
 }
 
 }  // extern "C"

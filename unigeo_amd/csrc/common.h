@@ -297,5 +297,5 @@ void launch_vis_panel(const float* rgb, const float* normals, const float* depth
 void launch_prep_resize(const unsigned char* frames, const int* ridx, const double* rw, int Kr, const int* cidx, const double* cw, int Kc,
                         int T, int Hi, int Wi, int Ho, int Wo, double* mid, float* out, hipStream_t s);
 void launch_prep_gt(const unsigned short* depth, const unsigned char* normals, const double* cam, const int* row_idx, const int* col_idx, int T,
-                    int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, float* cam_normal, float* world_normal, float* cam_coord,
-                    float* world_coord, float* mask, hipStream_t s);
+                    int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, int depth_f64, int zoomed, float* cam_normal, float* world_normal,
+                    float* cam_coord, float* world_coord, float* mask, hipStream_t s);

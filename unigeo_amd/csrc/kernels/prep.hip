@@ -49,6 +49,8 @@ __global__ __launch_bounds__(PB) void k_prep_resize_h(const double* __restrict__
 // Ground truth at the picked pixels (load_clip of harness/scannetpp.py, step for step).  One thread per output pixel (t, oy, ox) reads source
 // pixel (row_idx[oy], col_idx[ox]) of frame t.  cam: 20 doubles per frame = fx, fy, cx, cy, M33 row-major, t3 (+ 4 unused).  Every float32 step
 // of the host is one float32 operation here (__f*_rn: no fusing); the float64 expression (u - cx) * depth / fx has no sum to fuse into.
+// depth_f64 (UG_PREP_DEPTH_F64, harness/rgbd.py's Bonn layout): the depth stays float64 from the division to the end of the back-projection
+// and x, y, z are rounded once each; the mask still tests the float32 z, as the host does on -cam_coord[2].
 struct PrepGtArgs {
   const unsigned short* depth;   // [T,Hi,Wi]
   const unsigned char* normals;  // [T,Hi,Wi,3] or NULL (normals 0)
@@ -62,7 +64,8 @@ struct PrepGtArgs {
   float* mask;                   // [T,Ho,Wo]
   long n;                        // T * Ho * Wo
   int Hi, Wi, Ho, Wo;
-  int resized;                   // (Ho, Wo) != (Hi, Wi): the host's order-0 zoom ran, whose sum 0 + 1 * v turns a -0 into +0
+  int zoomed;                    // UG_PREP_ZOOMED: the host's order-0 zoom ran, whose sum 0 + 1 * v turns a -0 into +0
+  int depth_f64;                 // UG_PREP_DEPTH_F64
   float divisor, max_depth;
 };
 
@@ -75,9 +78,10 @@ __global__ __launch_bounds__(PB) void k_prep_gt(const PrepGtArgs a) {
     const int sy = a.row_idx[oy], sx = a.col_idx[ox];
     const long sp = (t * a.Hi + sy) * a.Wi + sx;
     const double* q = a.cam + t * 20;
-    const float d = __fdiv_rn((float)a.depth[sp], a.divisor);
-    const float x = (float)(((double)sx - q[2]) * (double)d / q[0]);
-    const float y = (float)(((double)sy - q[3]) * (double)d / q[1]);
+    const double dd = a.depth_f64 ? (double)a.depth[sp] / (double)a.divisor : (double)__fdiv_rn((float)a.depth[sp], a.divisor);
+    const float d = (float)dd;
+    const float x = (float)(((double)sx - q[2]) * dd / q[0]);
+    const float y = (float)(((double)sy - q[3]) * dd / q[1]);
     float c[3] = {x, -y, -d};
     float nn[3] = {0.f, 0.f, 0.f};
     if (a.normals) {
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(PB) void k_prep_gt(const PrepGtArgs a) {
       wc[r] = (float)(m[0] * (double)c[0] + m[1] * (double)c[1] + m[2] * (double)c[2] + q[13 + r]);
     }
     const bool bad = x != x || y != y || d != d || d < 1e-3f || d > a.max_depth;
-    if (a.resized)
+    if (a.zoomed)
       for (int j = 0; j < 3; ++j) { nn[j] = __fadd_rn(nn[j], 0.f); wn[j] = __fadd_rn(wn[j], 0.f); c[j] = __fadd_rn(c[j], 0.f); wc[j] = __fadd_rn(wc[j], 0.f); }
     const long o = t * 3 * plane + rem;
     for (int j = 0; j < 3; ++j) {
@@ -116,11 +120,11 @@ void launch_prep_resize(const unsigned char* frames, const int* ridx, const doub
 }
 
 void launch_prep_gt(const unsigned short* depth, const unsigned char* normals, const double* cam, const int* row_idx, const int* col_idx, int T,
-                    int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, float* cam_normal, float* world_normal, float* cam_coord,
-                    float* world_coord, float* mask, hipStream_t s) {
+                    int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, int depth_f64, int zoomed, float* cam_normal, float* world_normal,
+                    float* cam_coord, float* world_coord, float* mask, hipStream_t s) {
   PrepGtArgs a;
   a.depth = depth; a.normals = normals; a.cam = cam; a.row_idx = row_idx; a.col_idx = col_idx;
   a.cam_normal = cam_normal; a.world_normal = world_normal; a.cam_coord = cam_coord; a.world_coord = world_coord; a.mask = mask;
-  a.n = (long)T * Ho * Wo; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.resized = (Ho != Hi || Wo != Wi); a.divisor = divisor; a.max_depth = max_depth;
+  a.n = (long)T * Ho * Wo; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.zoomed = zoomed; a.depth_f64 = depth_f64; a.divisor = divisor; a.max_depth = max_depth;
   hipLaunchKernelGGL(k_prep_gt, dim3(prep_blocks(a.n)), dim3(PB), 0, s, a);
 }

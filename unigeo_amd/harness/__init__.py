@@ -5,10 +5,14 @@ from .metrics import MetricsManager, depth_evaluation, depth_evaluation_in_globa
 from .eval import evaluate, parse_dataset_config, parse_depth_coord, parse_metric_config, import_class_from_module
 from .dataset import SyntheticGeometryDataset, split_clips
 from .scannetpp import ScannetPPDataset, ScannetPPSequence
+from .rgbd import (RGBDClipDataset, RGBDSequence, ScannetV2Dataset, bonnDataset, neuralRGBDDataset, read_tum_trajectory, replicaDataset,
+                   sevenScenesDataset)
 from .distributed import evaluate_sharded
 from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, save_depth_normal_maps
 
 __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_evaluation_in_global_coord",
            "normal_evaluation", "evaluate", "parse_dataset_config", "parse_depth_coord", "parse_metric_config", "import_class_from_module", "SyntheticGeometryDataset",
            "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence",
+           "RGBDClipDataset", "RGBDSequence", "sevenScenesDataset", "bonnDataset", "neuralRGBDDataset", "replicaDataset", "ScannetV2Dataset",
+           "read_tum_trajectory",
            "SPECTRAL_R_LUT", "colorbar_strip", "colorize", "panels_u8", "save_depth_normal_maps"]

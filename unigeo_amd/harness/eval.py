@@ -24,7 +24,7 @@ def parse_dataset_config(config):
            "clip_overlap": config.get("clip_overlap", 0), "input_size": (config["h"], config["w"]),
            "target_size": (config["h"], config["w"])}
     for k in ("split", "split_file", "scenes",       # optional: which scene list the loader walks (default: the split file)
-              "prep"):                               # optional: host | device clip preparation of the ScanNet++ loader
+              "prep"):                               # optional: host | device clip preparation of the ScanNet++ / RGB-D loaders (DESIGN.md sections 16, 17)
         if k in config:
             out[k] = config[k]
     return out
@@ -83,7 +83,9 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     ``ug_eval_depth_global`` on the device path; the row keys stay the same.  It goes with ``depth_alignment: lstsq`` only (``ValueError`` otherwise).
     ``vis_depth: True`` (the reference's key, eval.py:58-62) writes ``save_dir/depth_{seq}/frame_%04d.webp`` after the clip's metrics: rgb | normals |
     coloured depth | colour bar, composed on the GPU from the resident outputs under ``device_metrics=True`` and by the numpy mirror otherwise
-    (DESIGN.md section 15).  Rows and CSV do not change."""
+    (DESIGN.md section 15).  Rows and CSV do not change.
+    ``eval_normal`` on a dataset without ground-truth normals (the RGB-D loaders of ``harness/rgbd.py``) raises ``ValueError`` at the first such clip,
+    before the model runs on it."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
     coord = parse_depth_coord(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
@@ -97,6 +99,9 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     def one_clip(data_idx, mdl):
         data = dataset[data_idx]
         seq = f"{data_idx:03d}_{data['scene_name']}"
+        if "eval_normal" in config and "cam_normal" not in data:
+            raise ValueError(f"eval_normal: clip {seq} of dataset {data.get('_dataset', type(dataset).__name__)!r} has no ground-truth normals "
+                             f"(the sample lacks 'cam_normal'); remove eval_normal from the configuration")
         if verbose:
             print("processing seq:", seq)
         output = mdl.forward(data)

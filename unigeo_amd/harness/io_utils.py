@@ -1,5 +1,6 @@
 """GT preparation - mirrors ``/root/reference/utils/io_utils.py:4-45`` (``prepare_gt_label``): the unified sample
-dict (OpenGL camera coordinates, channel-first arrays) -> stacked torch tensors in OpenCV coordinates."""
+dict (OpenGL camera coordinates, channel-first arrays) -> stacked torch tensors in OpenCV coordinates.  A sample without ``cam_normal``
+(the RGB-D loaders of ``harness/rgbd.py``) gives no ``gt_normals``; the reference's own function raises ``KeyError`` on those datasets."""
 import numpy as np
 
 _GL2CV = np.diag([1.0, -1.0, -1.0, 1.0]).astype(np.float32)
@@ -8,6 +9,7 @@ _GL2CV = np.diag([1.0, -1.0, -1.0, 1.0]).astype(np.float32)
 def prepare_gt_label(data):
     import torch
     n = len(data["images"])
+    has_normals = "cam_normal" in data
     world, masks, poses, depths, rgbs, normals = [], [], [], [], [], []
     for i in range(n):
         cam2world = np.linalg.inv(np.asarray(data["extrinsics"][i]).astype(np.float32))
@@ -17,7 +19,10 @@ def prepare_gt_label(data):
         world.append(pw.transpose(1, 2, 0)); depths.append(pc.transpose(1, 2, 0)[..., -1])
         masks.append(np.asarray(data["mask"][i]).astype(bool))
         rgbs.append(np.asarray(data["images"][i]).transpose(1, 2, 0) / 255.0)
-        normals.append(np.asarray(data["cam_normal"][i]).transpose(1, 2, 0))
+        if has_normals:
+            normals.append(np.asarray(data["cam_normal"][i]).transpose(1, 2, 0))
     st = lambda xs: torch.from_numpy(np.ascontiguousarray(np.stack(xs, 0)))
-    return {"gt_world_pts": st(world), "gt_masks": st(masks), "gt_poses": st(poses), "gt_depths": st(depths),
-            "gt_rgbs": st(rgbs), "gt_normals": st(normals)}
+    out = {"gt_world_pts": st(world), "gt_masks": st(masks), "gt_poses": st(poses), "gt_depths": st(depths), "gt_rgbs": st(rgbs)}
+    if has_normals:
+        out["gt_normals"] = st(normals)
+    return out
