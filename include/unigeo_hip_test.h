@@ -67,6 +67,14 @@ int ug_op_layernorm(ug_ctx* ctx, const float* x, int M, int C, float eps, const 
                     const float* addvec, int rows_per_vec, float* out, float* xout);
 int ug_op_flash_attn(ug_ctx* ctx, const float* qkv /*[B*S,3*H*64]*/, int B, int H, int S, float* out /*[B*S,H*64]*/);
 int ug_op_temporal_attn(ug_ctx* ctx, const float* qkv /*[T*HW,3*H*64]*/, int T, int HW, int H, float* out);
+/* The other launch forms of the d = 64 flash attention (the cross-attention of the StableNormal transformer blocks): Sk keys per batch (0: self-attention,
+ * kv holds B*S rows), kv_shared = 1: one context of Sk rows read by every batch.  q [B*S, ldq]; kv [(kv_shared ? 1 : B)*Sk + guard, ldkv] with K in
+ * columns [0, H*64) and V in [H*64, 2*H*64); out_inout [B*S + guard, ldo].  All three go to the device as given - guard rows, surplus columns and the
+ * caller's contents of out_inout included - and all of out_inout comes back.  ldq, ldkv % 8 == 0, ldo % 4 == 0 (the launcher's rules), else an error. */
+int ug_op_flash_cross_attn(ug_ctx* ctx, const float* q, const float* kv, int B, int H, int S, int Sk, int kv_shared, long ldq, long ldkv, long ldo,
+                           long guard, float* out_inout);
+/* ug_op_temporal_attn over nv videos stacked [nv][T][HW] in one launch (the guided UNet pass): qkv [nv*T*HW,3*H*64], out [nv*T*HW,H*64] */
+int ug_op_temporal_attn_nv(ug_ctx* ctx, const float* qkv, int nv, int T, int HW, int H, float* out);
 int ug_op_attention_generic(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);
 int ug_op_flash_attn_dh(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);   /* fused self-attention, head dim d in {32,48,80,96,112,128}: the CLIP tower's 16 x 80 heads */
 int ug_op_euler_step(ug_ctx* ctx, const float* v, float* latents_inout, long n, float sigma, float sigma_next);

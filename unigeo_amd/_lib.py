@@ -21,7 +21,7 @@ EXPORTS = [
     "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_dc_set_inputs_ex", "ug_dc_get_noise", "ug_op_philox_u32", "ug_op_randn", "ug_op_u8_to_frames", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
     "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
-    "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step",
+    "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
@@ -140,6 +140,8 @@ def load_library():
     lib.ug_op_attention_generic.argtypes = [vp, vp, ip, ip, ip, ip, vp]
     lib.ug_op_flash_attn_dh.argtypes = [vp, vp, ip, ip, ip, ip, vp]
     lib.ug_op_euler_step.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float]
+    _set_argtypes(lib, {"ug_op_flash_cross_attn": [vp, vp, vp, ip, ip, ip, ip, ip, C.c_long, C.c_long, C.c_long, C.c_long, vp],
+                        "ug_op_temporal_attn_nv": [vp, vp, ip, ip, ip, ip, vp]})
     _set_argtypes(lib, {
         "ug_op_split_pair": [vp, vp, C.c_long, ip, vp, vp], "ug_op_gn32_pair": [vp, vp, ip, ip, ip, ip, C.c_float, ip, vp, vp, vp, vp],
         "ug_op_conv_wide": [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, ip, ip, ip, ip, ip, vp], "ug_op_attn_wide": [vp, vp, ip, ip, ip, vp]})
@@ -754,6 +756,24 @@ class Engine:
     def op_temporal_attn(self, qkv, T, HW, H):
         q = _f32(qkv); out = np.empty((T * HW, H * 64), np.float32)
         self._ck(self.lib.ug_op_temporal_attn(self.ctx, _ptr(q), T, HW, H, _ptr(out)))
+        return out
+
+    def op_flash_cross_attn(self, q, kv, out_inout, B, H, S, Sk=0, kv_shared=False, guard=0):
+        """The d = 64 flash attention with its own key count and row strides (the cross-attention launch form).  q [B*S, ldq], kv [(1 if kv_shared
+        else B) * (Sk or S) + guard, ldkv] with K in columns [0, H*64) and V in [H*64, 2*H*64), out_inout [B*S + guard, ldo]: all three are uploaded as
+        they are (guard rows and surplus columns too) and a new array with the device's whole out_inout is returned."""
+        q, kv, out = _f32(q), _f32(kv), np.array(out_inout, dtype=np.float32, order="C")
+        keys = Sk if Sk > 0 else S
+        assert q.ndim == kv.ndim == out.ndim == 2 and q.shape[0] == B * S and out.shape[0] == B * S + guard, (q.shape, kv.shape, out.shape)
+        assert Sk < 0 or kv.shape[0] == (1 if kv_shared else B) * keys + guard, kv.shape
+        self._ck(self.lib.ug_op_flash_cross_attn(self.ctx, _ptr(q), _ptr(kv), B, H, S, Sk, int(bool(kv_shared)), q.shape[1], kv.shape[1], out.shape[1],
+                                                 int(guard), _ptr(out)))
+        return out
+
+    def op_temporal_attn_nv(self, qkv, nv, T, HW, H):
+        q = _f32(qkv); out = np.empty((nv * T * HW, H * 64), np.float32)
+        assert q.shape == (nv * T * HW, 3 * H * 64), q.shape
+        self._ck(self.lib.ug_op_temporal_attn_nv(self.ctx, _ptr(q), nv, T, HW, H, _ptr(out)))
         return out
 
     def op_attention_generic(self, qkv, B, S, H, d):

@@ -473,6 +473,41 @@ int ug_op_temporal_attn(ug_ctx* x, const float* qkv, int T, int HW, int H, float
   });
 }
 
+// the launch forms of launch_flash_attn64 that ug_op_flash_attn cannot reach: Sk != 0 / kv_shared with separate row strides, K and V in one buffer.
+// Everything the caller hands over goes to the device and all of out_inout comes back, so a test can poison what the kernel must not read and
+// plant sentinels where it must not write.
+int ug_op_flash_cross_attn(ug_ctx* x, const float* q, const float* kv, int B, int H, int S, int Sk, int kv_shared, long ldq, long ldkv, long ldo,
+                           long guard, float* out_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const long C = (long)H * 64;
+    UG_REQUIRE(B >= 1 && H >= 1 && S >= 1 && Sk >= 0 && guard >= 0 && q && kv && out_inout, "flash cross-attention shape");
+    UG_REQUIRE(ldq >= C && ldkv >= 2 * C && ldo >= C, "flash cross-attention: rows narrower than the heads");
+    UG_REQUIRE(ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0, "flash cross-attention strides");
+    const long keys = Sk ? Sk : S;
+    const long rows_q = (long)B * S, rows_kv = (kv_shared ? 1 : B) * keys + guard, rows_o = rows_q + guard;
+    f16* dq = up16(c, q, rows_q * ldq); f16* dkv = up16(c, kv, rows_kv * ldkv); f16* o = up16(c, out_inout, rows_o * ldo);
+    FlashP p; p.Q = dq; p.K = dkv; p.V = dkv + C; p.ldq = ldq; p.ldk = p.ldv = ldkv; p.O = o; p.ldo = ldo; p.variant = c.flash_variant;
+    p.B = B; p.H = H; p.S = S; p.scale = 0.125f; p.Sk = Sk; p.kv_shared = kv_shared ? 1 : 0;
+    launch_flash_attn64(p, c.stream);
+    down16(c, o, out_inout, rows_o * ldo);
+  });
+}
+
+// ug_op_temporal_attn over nv videos stacked [nv][T][HW] (TemporalAttnP::nv, grid dimension z: the guided UNet pass)
+int ug_op_temporal_attn_nv(ug_ctx* x, const float* qkv, int nv, int T, int HW, int H, float* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(nv >= 1 && T >= 1 && HW >= 1 && H >= 1, "temporal attention shape");
+    const int C = H * 64; const long M = (long)nv * T * HW;
+    f16* d = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
+    TemporalAttnP p; p.Q = d; p.K = d + C; p.V = d + 2 * C; p.ld = 3 * C; p.O = o; p.ldo = C;
+    p.T = T; p.HW = HW; p.H = H; p.scale = 0.125f; p.nv = nv;
+    launch_temporal_attn64(p, c.stream);
+    down16(c, o, out, M * C);
+  });
+}
+
 int ug_op_attention_generic(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
