@@ -211,6 +211,33 @@ int ug_eval_depth_global(ug_ctx* ctx, const float* pred_depth /* NULL: resident 
                          const float* cam2world_t44, const float* intrinsics_t33, const unsigned char* custom_mask /* or NULL */, int T, int H,
                          int W, const ug_depth_eval_opts* opts, double* out13, float* radius_map_out /* [T*H*W] or NULL */);
 
+/* Point-cloud evaluation: the reference's eval_pcd branch (eval.py:66-83, metrics/eval_pcd.py:10-168 with pcd_alignment.py, metrics/utils.py:14-42
+ * and the Open3D calls it makes; kernels/pcd.hip).
+ * ug_pcd_world_points: the first half of ug_eval_depth_global - fit 1, d = clamp(s_d * pred + t_d, post_clip) in float32, float64 back-projection
+ *   and world transform - with every coordinate rounded once to float32.  out_fit2 = (s_d, t_d); out_pts (host, [T*H*W*3], may be NULL).  The points
+ *   stay resident on the device until the next ug_pcd_world_points; ug_eval_pcd reads them with pred_pts == NULL.  opts as in ug_eval_depth_global.
+ * ug_eval_pcd: pred_pts (NULL: the resident points) / gt_pts float32 [n_pixels,3], mask uint8 [n_pixels] (> 0 keeps the pixel).  Masked
+ *   selection in pixel order; the alignment of Regr3D_t_ScaleShiftInv(norm_mode=False, gt_scale=True) on ALL masked points (exact lower medians;
+ *   the norms behind the scales in float64, rounded once); then the points at positions sample_idx[0 .. n_sample) of the masked sequence (NULL:
+ *   all of them); point-to-point ICP from the identity (nearest neighbour closer than threshold, Umeyama without scaling, stop when fitness and
+ *   inlier rmse both move by less than 1e-6 or after max_iteration updates); normals from the float64 covariance of the min(knn, n) nearest
+ *   points ((0, 0, 1) below 3 points); accuracy / completion of metrics/utils.py.  All pair arithmetic is unfused float64; the nearest target is
+ *   the one with the smallest (dx*dx + dy*dy) + dz*dz, ties to the lowest index.  out32: acc, comp, nc1, nc2, acc_med, comp_med, nc1_med,
+ *   nc2_med, n_points, icp_iterations, icp_fitness, icp_rmse, transformation[16] row-major, pred_scale (clipped), gt_scale, pred_shift_z,
+ *   gt_shift_z.  pred_cloud_out / gt_cloud_out (host, [n_points*3] float32, may be NULL): the aligned, sampled clouds before ICP.  No masked
+ *   pixel: n_points = 0, NaN metrics and scalars, the identity.  Errors (ug_last_error; the context stays usable): NULL opts / gt_pts / mask /
+ *   out32; n_pixels <= 0 or >= 2^31; pred_pts == NULL without resident points of that size; a sample index outside the masked points; knn outside
+ *   1..UG_PCD_MAX_KNN; threshold <= 0; max_iteration < 0; more than 2^40 point pairs in one pass (lower pcd_downsample_num). */
+enum { UG_PCD_MAX_KNN = 32 };
+typedef struct { float threshold; int max_iteration; int knn; } ug_pcd_opts;
+void ug_pcd_opts_default(ug_pcd_opts* o);     /* 0.1, 30, 30 */
+int ug_pcd_world_points(ug_ctx* ctx, const float* pred_depth /* NULL: resident depth */, const float* gt_depth, const float* cam2world_t44,
+                        const float* intrinsics_t33, int T, int H, int W, const ug_depth_eval_opts* opts, float* out_fit2,
+                        float* out_pts /* [T*H*W*3] or NULL */);
+int ug_eval_pcd(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, const float* gt_pts, const unsigned char* mask, long n_pixels,
+                const long* sample_idx /* or NULL */, long n_sample, const ug_pcd_opts* opts, double* out32, float* pred_cloud_out /* or NULL */,
+                float* gt_cloud_out /* or NULL */);
+
 /* Visualisation panels composed on the device: replaces save_depth_normal_maps / colorize / colorize_np (utils/vis_utils.py:38-84,139-199, as
  * eval.py:58-62 calls them under `vis_depth: True`).  One image per frame, uint8 [T,H,Wp,3] row-major,
  *   Wp = (rgb ? W : 0) + W + W + (cbar ? 5 + Wc : 0):   rgb | normals | coloured depth | 5 black columns | colour bar.

@@ -106,6 +106,18 @@ int ug_op_u8_to_frames(ug_ctx* ctx, const unsigned char* frames_tchw, int T, int
  * pixels that is.  NaN clip bounds are off.  count = 0 leaves the medians 0. */
 int ug_op_masked_median(ug_ctx* ctx, const float* pred, const float* gt, long n, float max_depth, float pre_clip_min, float pre_clip_max,
                         float* out_medians /*[2]*/, long* out_count);
+/* The kernels behind ug_eval_pcd one by one (kernels/pcd.hip).
+ *   ug_op_pcd_nn         : nearest target of every query, float64 [n,3] each, the query first moved by T44 (row-major 4x4, may be NULL) as
+ *                          ((r0 x + r1 y) + r2 z) + t -> idx_out [nq], dist_out [nq] = sqrt of the smallest (dx*dx + dy*dy) + dz*dz, ties to the
+ *                          lowest index; unfused float64
+ *   ug_op_pcd_select     : the exact k-th smallest (k from 0) of n float32 (is_f64 = 0) or float64 (is_f64 = 1) values -> *out of that type;
+ *                          -0.0 sorts below +0.0; no NaN
+ *   ug_op_pcd_knn_normals: per point of a float64 cloud [n,3] the min(knn, n) nearest points, itself included, ordered by (squared distance,
+ *                          index) -> nbr_out [n, min(knn, n)] (may be NULL), and the unit eigenvector of the smallest eigenvalue of their float64
+ *                          covariance -> normals_out [n,3]; (0, 0, 1) for n < 3 */
+int ug_op_pcd_nn(ug_ctx* ctx, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out);
+int ug_op_pcd_select(ug_ctx* ctx, const void* values, int is_f64, long n, long k, void* out);
+int ug_op_pcd_knn_normals(ug_ctx* ctx, const double* pts, long n, int knn, int* nbr_out, double* normals_out);
 /* Tuning aids (not on the product path): GEMM / implicit-conv microbenchmark on device-resident random data,
  * and an override of the tile/split-K heuristic (-1 = heuristic). ms_out: [ms per launch, cfg, split, M, K]. */
 /* GroupNorm launch-scheme A/B (mode: launch_groupnorm in kernels/norm.hip); tuning aid, no reference counterpart. */

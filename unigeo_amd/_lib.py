@@ -24,6 +24,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
+    "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
@@ -55,6 +56,10 @@ class CLIPConfigC(C.Structure):
 class DepthEvalOptsC(C.Structure):
     _fields_ = [("alignment", C.c_int), ("max_depth", C.c_float), ("pre_clip_min", C.c_float), ("pre_clip_max", C.c_float),
                 ("post_clip_min", C.c_float), ("post_clip_max", C.c_float)]
+
+
+class PcdOptsC(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("max_iteration", C.c_int), ("knn", C.c_int)]
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_ALIGN_* of include/unigeo_hip.h
@@ -120,6 +125,13 @@ def load_library():
     lib.ug_eval_depth_ex.argtypes = [vp, vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_eval_depth_global.argtypes = [vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
+    lib.ug_pcd_opts_default.restype = None
+    _set_argtypes(lib, {"ug_pcd_opts_default": [C.POINTER(PcdOptsC)],
+                        "ug_pcd_world_points": [vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp],
+                        "ug_eval_pcd": [vp, vp, vp, vp, C.c_long, vp, C.c_long, C.POINTER(PcdOptsC), vp, vp, vp],
+                        "ug_op_pcd_nn": [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp],
+                        "ug_op_pcd_select": [vp, vp, ip, C.c_long, C.c_long, vp],
+                        "ug_op_pcd_knn_normals": [vp, vp, C.c_long, ip, vp, vp]})
     _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
                         "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
     _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
@@ -574,6 +586,79 @@ class Engine:
         res["valid_pixels"] = int(out[8])
         fits = (float(out[9]), float(out[10])), (float(out[11]), float(out[12]))
         return (res, *fits, rmap) if return_radius_map else (res, *fits)
+
+    # ---- point-cloud evaluation on device
+    PCD_KEYS = ["acc", "comp", "nc1", "nc2", "acc_med", "comp_med", "nc1_med", "nc2_med"]
+
+    def pcd_world_points(self, gt_depth, cam2world, intrinsics, pred=None, max_depth=80.0, pre_clip_min=None, pre_clip_max=None,
+                         post_clip_min=None, post_clip_max=None, return_points=True):
+        """World points of the (resident, ``pred=None``) depth (``ug_pcd_world_points``) -> ``(pts float32 [T,H,W,3] or None, (s_d, t_d))``;
+        the points stay on the device for ``eval_pcd(None, ...)``."""
+        g = _f32(gt_depth)
+        if g.ndim != 3:
+            raise ValueError("pcd_world_points: gt_depth must be [T,H,W]")
+        T, H, W = g.shape
+        pose, k = _f32(cam2world).reshape(T, 4, 4), _f32(intrinsics).reshape(T, 3, 3)
+        p = None if pred is None else _f32(pred).reshape(T, H, W)
+        o = DepthEvalOptsC(DEPTH_ALIGNMENTS["lstsq"], float("nan") if max_depth is None else float(max_depth),
+                           *[float("nan") if c is None else float(c) for c in (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)])
+        fit = np.zeros(2, np.float32)
+        pts = np.empty((T, H, W, 3), np.float32) if return_points else None
+        self._ck(self.lib.ug_pcd_world_points(self.ctx, _ptr(p), _ptr(g), _ptr(pose), _ptr(k), T, H, W, C.byref(o), _ptr(fit), _ptr(pts)))
+        return pts, (float(fit[0]), float(fit[1]))
+
+    def eval_pcd(self, pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30,
+                 return_clouds=True):
+        """``pcd_evaluation`` of ``harness/metrics.py`` on the device (``ug_eval_pcd``) -> the same dict.  ``pred_pts=None`` evaluates the
+        points that the last ``pcd_world_points`` left resident.  The sampled positions are drawn here, as the host mirror draws them."""
+        from .harness.metrics import pcd_sample_indices
+        g = _f32(gt_pts).reshape(-1, 3)
+        m = np.ascontiguousarray((np.asarray(masks).reshape(-1) > 0).astype(np.uint8))
+        p = None if pred_pts is None else _f32(pred_pts).reshape(-1, 3)
+        n_mask = int(m.sum())
+        idx = pcd_sample_indices(n_mask, downsample_num, seed)
+        idx = None if idx is None else np.ascontiguousarray(idx.astype(np.int64))
+        ns = n_mask if idx is None else len(idx)
+        o = PcdOptsC(float(threshold), int(max_iteration), int(knn))
+        out = np.zeros(32, np.float64)
+        pc = np.empty((ns, 3), np.float32) if return_clouds else None
+        gc = np.empty((ns, 3), np.float32) if return_clouds else None
+        self._ck(self.lib.ug_eval_pcd(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
+                                      _ptr(out), _ptr(pc), _ptr(gc)))
+        res = dict(zip(self.PCD_KEYS, out[:8].tolist()))
+        res.update(n_points=int(out[8]), icp_iterations=int(out[9]), icp_fitness=float(out[10]), icp_rmse=float(out[11]),
+                   transformation=out[12:28].reshape(4, 4).copy(), pred_scale=float(out[28]), gt_scale=float(out[29]),
+                   pred_shift_z=float(out[30]), gt_shift_z=float(out[31]))
+        if return_clouds:
+            keep = m > 0
+            col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[keep]
+            col = col if idx is None else col[idx]
+            res.update(pred_pcd=(pc, col), gt_pcd=(gc, col.copy()))
+        return res
+
+    def op_pcd_nn(self, query, target, transformation=None):
+        """Nearest target of every query (float64 ``[n,3]``; the query first moved by the 4x4) -> ``(distance float64, index int32)``."""
+        q = np.ascontiguousarray(np.asarray(query, np.float64).reshape(-1, 3)); t = np.ascontiguousarray(np.asarray(target, np.float64).reshape(-1, 3))
+        T = None if transformation is None else np.ascontiguousarray(np.asarray(transformation, np.float64).reshape(4, 4))
+        idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float64)
+        self._ck(self.lib.ug_op_pcd_nn(self.ctx, _ptr(q), len(q), _ptr(t), len(t), _ptr(T), _ptr(idx), _ptr(dist)))
+        return dist, idx
+
+    def op_pcd_select(self, values, k):
+        """The exact k-th smallest (from 0) of a float32 or float64 array."""
+        v = np.ascontiguousarray(np.asarray(values).reshape(-1))
+        if v.dtype not in (np.float32, np.float64):
+            raise ValueError("op_pcd_select: float32 or float64 values")
+        out = np.zeros(1, v.dtype)
+        self._ck(self.lib.ug_op_pcd_select(self.ctx, _ptr(v), int(v.dtype == np.float64), v.size, int(k), _ptr(out)))
+        return out[0]
+
+    def op_pcd_knn_normals(self, pts, knn=30):
+        """KNN lists and covariance normals of a float64 cloud -> ``(neighbours int32 [n, min(knn, n)], normals float64 [n,3])``."""
+        p = np.ascontiguousarray(np.asarray(pts, np.float64).reshape(-1, 3))
+        nbr, nrm = np.empty((len(p), min(knn, len(p))), np.int32), np.empty((len(p), 3), np.float64)
+        self._ck(self.lib.ug_op_pcd_knn_normals(self.ctx, _ptr(p), len(p), int(knn), _ptr(nbr), _ptr(nrm)))
+        return nbr, nrm
 
     def op_masked_median(self, pred, gt, max_depth=80.0, pre_clip_min=None, pre_clip_max=None):
         """The exact masked selection alone -> (lower median of clamp(pred), lower median of gt, count) over the valid ``gt``."""

@@ -260,6 +260,63 @@ int ug_op_masked_median(ug_ctx* x, const float* pred, const float* gt, long n, f
   });
 }
 
+// the kernels of ug_eval_pcd one by one (kernels/pcd.hip)
+int ug_op_pcd_nn(ug_ctx* x, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(query && target && idx_out && dist_out, "query, target, idx_out and dist_out must not be NULL");
+    UG_REQUIRE(nq >= 1 && nt >= 1 && nq < (1L << 31) && nt < (1L << 31), "point counts must be 1 .. 2^31 - 1");
+    UG_REQUIRE((double)nq * (double)nt <= 1099511627776.0, "more than 2^40 point pairs in one nearest-neighbour pass: lower pcd_downsample_num");
+    double* dq = c.ws.get<double>(nq * 3); double* dt = c.ws.get<double>(nt * 3);
+    UG_CHECK(hipMemcpy(dq, query, (size_t)nq * 24, hipMemcpyHostToDevice));
+    UG_CHECK(hipMemcpy(dt, target, (size_t)nt * 24, hipMemcpyHostToDevice));
+    double* dT = nullptr;
+    if (T44) { dT = c.ws.get<double>(16); UG_CHECK(hipMemcpy(dT, T44, 128, hipMemcpyHostToDevice)); }
+    const int ny = pcd_nn_slices(nq, nt);
+    int* idx = c.ws.get<int>(nq); double* dist = c.ws.get<double>(nq);
+    int* pidx = c.ws.get<int>((long)ny * nq); double* pdist = c.ws.get<double>((long)ny * nq);
+    launch_pcd_nn(dq, nq, dt, nt, dT, idx, dist, pidx, pdist, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(idx_out, idx, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    UG_CHECK(hipMemcpy(dist_out, dist, (size_t)nq * 8, hipMemcpyDeviceToHost));
+  });
+}
+int ug_op_pcd_select(ug_ctx* x, const void* values, int is_f64, long n, long k, void* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(values && out, "values and out must not be NULL");
+    UG_REQUIRE(n >= 1 && n < (1L << 31) && k >= 0 && k < n, "n must be 1 .. 2^31 - 1 and k inside it");
+    const size_t bytes = (size_t)n * (is_f64 ? 8 : 4);
+    void* dv = c.ws.alloc(bytes); UG_CHECK(hipMemcpy(dv, values, bytes, hipMemcpyHostToDevice));
+    unsigned* sel = (unsigned*)c.ws.alloc(PCD_SEL_WORDS * 4);
+    unsigned long long* res = c.ws.get<unsigned long long>(1);
+    launch_pcd_select(dv, is_f64, n, 1, 0, (unsigned long long)k, sel, res, 0, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    unsigned long long key;
+    UG_CHECK(hipMemcpy(&key, res, 8, hipMemcpyDeviceToHost));
+    if (is_f64) *(double*)out = pcd_unkey_f64(key); else *(float*)out = pcd_unkey_f32(key);
+  });
+}
+int ug_op_pcd_knn_normals(ug_ctx* x, const double* pts, long n, int knn, int* nbr_out, double* normals_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pts && normals_out, "pts and normals_out must not be NULL");
+    UG_REQUIRE(n >= 1 && n < (1L << 31) && knn >= 1 && knn <= UG_PCD_MAX_KNN, "n must be 1 .. 2^31 - 1 and knn 1 .. UG_PCD_MAX_KNN");
+    UG_REQUIRE((double)n * (double)n <= 1099511627776.0, "more than 2^40 point pairs in one neighbour pass: lower pcd_downsample_num");
+    const long k = n < knn ? n : knn;
+    double* dp = c.ws.get<double>(n * 3); UG_CHECK(hipMemcpy(dp, pts, (size_t)n * 24, hipMemcpyHostToDevice));
+    int* nbr = nbr_out ? c.ws.get<int>(n * k) : nullptr;
+    double* nrm = c.ws.get<double>(n * 3);
+    launch_pcd_knn_normals(dp, n, knn, nbr, nrm, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    if (nbr_out) UG_CHECK(hipMemcpy(nbr_out, nbr, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+    UG_CHECK(hipMemcpy(normals_out, nrm, (size_t)n * 24, hipMemcpyDeviceToHost));
+  });
+}
+
 int ug_op_linear(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, const float* R1,
                  float c0, float c1, int act, int geglu, float* out) {
   UG_TRY(x, {

@@ -286,8 +286,48 @@ void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned 
 // depth evaluation in global coordinates (kernels/metrics.hip); cam: 16 doubles per frame = fx, fy, cx, cy, R row-major, t
 void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s);
+void launch_world_points(const float* pred, const double* cam, long n, int H, int W, float plo, float phi, float sc, float sh, float* pts,
+                         hipStream_t s);
 void launch_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask, long n, float max_depth,
                            float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s);
+// point-cloud evaluation (kernels/pcd.hip).  Clouds are [n,3]; idx / dist are per query.  All launches are stream-ordered and
+// deterministic: fixed-order fp64 reductions, integer atomics only in the selection histograms.
+#define PCD_MAXB 1024         // most blocks of a compaction / reduction launch: `counts` / `part` arrays are sized by it
+#define PCD_SEL_WORDS 264     // select state (unsigned words): 256 histogram words, then prefix (2 words), rank (2 words), padding
+// order-preserving 64-bit key of a float32 (in the upper word) / float64: negative values have all bits flipped, the others only the sign bit
+__host__ __device__ inline unsigned long long pcd_key(double f) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, f);
+  return u ^ ((u >> 63) ? ~0ull : (1ull << 63));
+}
+__host__ __device__ inline unsigned long long pcd_key(float f) {
+  const unsigned u = __builtin_bit_cast(unsigned, f);
+  return (unsigned long long)(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u)) << 32;
+}
+__host__ __device__ inline double pcd_unkey_f64(unsigned long long k) {
+  return __builtin_bit_cast(double, k ^ ((k >> 63) ? (1ull << 63) : ~0ull));
+}
+__host__ __device__ inline float pcd_unkey_f32(unsigned long long k) {
+  const unsigned w = (unsigned)(k >> 32);
+  return __builtin_bit_cast(float, w ^ ((w >> 31) ? 0x80000000u : 0xffffffffu));
+}
+void launch_pcd_compact(const float* pred, const float* gt, const unsigned char* mask, long n, unsigned* counts /*[PCD_MAXB + 1]*/, float* p_out,
+                        float* g_out, hipStream_t s);                 // counts[PCD_MAXB] = how many pixels were kept
+// the k-th smallest (rank words of `res` slot: the caller passes k) of v[i * stride + offset], float32 or float64 -> res[slot] as the order-preserving 64-bit key
+void launch_pcd_select(const void* v, int is_f64, long n, int stride, int offset, unsigned long long k, unsigned* sel, unsigned long long* res,
+                       int slot, hipStream_t s);
+void launch_pcd_shift_z(float* p, float* g, long n, const unsigned long long* res, int slot_p, int slot_g, hipStream_t s);
+void launch_pcd_center_norm(const float* p, long n, const unsigned long long* res, int slot_c, float* norm, hipStream_t s);
+void launch_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32, float* g32, double* p64, double* g64,
+                      hipStream_t s);
+int pcd_nn_slices(long nq, long nt);
+void launch_pcd_nn(const double* q, long nq, const double* t, long nt, const double* T44 /* device, or NULL */, int* idx, double* dist,
+                   int* pidx, double* pdist /* [slices][nq] scratch */, hipStream_t s);
+void launch_pcd_kabsch(const double* q, const double* t, long nq, const double* T44, const int* idx, const double* dist, double threshold,
+                       double* part /*[PCD_MAXB * 17]*/, int* nb, hipStream_t s);
+void launch_pcd_move(const double* q, long n, const double* T44, double* out, hipStream_t s);
+void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr /* [n][min(knn, n)] or NULL */, double* normals, hipStream_t s);
+void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s);
+void launch_pcd_sum(const double* v, long n, double* part /*[PCD_MAXB]*/, int* nb, hipStream_t s);
 // depth / normal visualisation panels (kernels/vis.hip); part: 2 * 1024 floats of scratch, out2 (device) = (vmin, vmax)
 void launch_vis_range(const float* x, long n, float* part, float* out2, hipStream_t s);
 void launch_vis_panel(const float* rgb, const float* normals, const float* depth, const float* lut, const float* cbar, unsigned char* out, int T,

@@ -268,7 +268,26 @@ __global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, cons
 // with the frame's pose, r = |world| rounded once to float32 and written out.  The same pass accumulates the normal-equation sums of the
 // second fit, r against the ground-truth radius over mask1 of the ground-truth DEPTH: n, sum r, sum r^2, sum g_r, sum r * g_r.
 // cam: 16 doubles per frame - fx, fy, cx, cy, R row-major, t - widened from float32 by the host.  The fp64 products and sums stay
-// unfused (__dmul_rn / __dadd_rn): the arithmetic the fixture's generator emulates.
+// unfused: the arithmetic the fixture's generator emulates.
+// One pixel of the chain above: the aligned, post-clipped float32 depth of pixel i -> its world coordinates in fp64 (shared by k_world_radius and
+// k_world_points).  Contraction is switched off for the body: the __fmul_rn / __dmul_rn family are plain operators in this toolchain, and with
+// them s * pred + t came out as ONE fused operation - a float32 depth one ulp away from the host's on a share of the pixels, which the point-cloud
+// metrics see.
+__device__ __forceinline__ void world_point(const float* pred, const double* cam, long i, long hw, int W, float plo, float phi, float s, float t,
+                                            double& wx, double& wy, double& wz) {
+#pragma clang fp contract(off)
+  const long f = i / hw;
+  const long rem = i - f * hw;
+  const int row = (int)(rem / W), col = (int)(rem - (long)row * W);
+  const double* q = cam + f * 16;
+  const float d = s * pred[i] + t;
+  const double z = clipf(d, plo, phi);
+  const double x = ((double)col - q[2]) * z / q[0], y = ((double)row - q[3]) * z / q[1];
+  wx = ((q[4] * x + q[5] * y) + q[6] * z) + q[13];
+  wy = ((q[7] * x + q[8] * y) + q[9] * z) + q[14];
+  wz = ((q[10] * x + q[11] * y) + q[12] * z) + q[15];
+}
+
 __global__ __launch_bounds__(MB) void k_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n,
                                                      int H, int W, float max_depth, float plo, float phi, float s, float t, float* radius,
                                                      double* part) {
@@ -276,15 +295,8 @@ __global__ __launch_bounds__(MB) void k_world_radius(const float* pred, const fl
   double a[5] = {0, 0, 0, 0, 0};
   const long hw = (long)H * W;
   for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
-    const long f = i / hw;
-    const long rem = i - f * hw;
-    const int row = (int)(rem / W), col = (int)(rem - (long)row * W);
-    const double* q = cam + f * 16;
-    const double z = clipf(__fadd_rn(__fmul_rn(s, pred[i]), t), plo, phi);
-    const double x = __dmul_rn((double)col - q[2], z) / q[0], y = __dmul_rn((double)row - q[3], z) / q[1];
-    const double wx = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[4], x), __dmul_rn(q[5], y)), __dmul_rn(q[6], z)), q[13]);
-    const double wy = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[7], x), __dmul_rn(q[8], y)), __dmul_rn(q[9], z)), q[14]);
-    const double wz = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(q[10], x), __dmul_rn(q[11], y)), __dmul_rn(q[12], z)), q[15]);
+    double wx, wy, wz;
+    world_point(pred, cam, i, hw, W, plo, phi, s, t, wx, wy, wz);
     const float rf = (float)sqrt(__dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz)));
     radius[i] = rf;
     if (depth_valid(gt[i], max_depth)) {
@@ -295,6 +307,17 @@ __global__ __launch_bounds__(MB) void k_world_radius(const float* pred, const fl
   for (int k = 0; k < 5; ++k) {
     const double r = block_sum(a[k], sh);
     if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + k] = r;
+  }
+}
+
+// the world points themselves, each coordinate rounded once to float32 (ug_pcd_world_points)
+__global__ __launch_bounds__(MB) void k_world_points(const float* pred, const double* cam, long n, int H, int W, float plo, float phi, float s,
+                                                     float t, float* pts) {
+  const long hw = (long)H * W;
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    double wx, wy, wz;
+    world_point(pred, cam, i, hw, W, plo, phi, s, t, wx, wy, wz);
+    pts[i * 3] = (float)wx; pts[i * 3 + 1] = (float)wy; pts[i * 3 + 2] = (float)wz;
   }
 }
 
@@ -372,6 +395,10 @@ void launch_world_radius(const float* pred, const float* gt, const float* gt_rad
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s) {
   *nb = nblocks(n);
   hipLaunchKernelGGL(k_world_radius, dim3(*nb), dim3(MB), 0, s, pred, gt, gt_radius, cam, n, H, W, max_depth, plo, phi, sc, sh, radius, part);
+}
+void launch_world_points(const float* pred, const double* cam, long n, int H, int W, float plo, float phi, float sc, float sh, float* pts,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(k_world_points, dim3(nblocks(n)), dim3(MB), 0, s, pred, cam, n, H, W, plo, phi, sc, sh, pts);
 }
 void launch_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask, long n, float max_depth,
                            float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s) {

@@ -1,0 +1,410 @@
+// Point-cloud evaluation on the device - what the reference hands to Open3D and a CPU k-d tree:
+//   /root/reference/metrics/eval_pcd.py:10-168 (masked selection, alignment, downsampling, ICP, normals, scores),
+//   metrics/pcd_alignment.py (Regr3D_t_ScaleShiftInv: median shifts and median scales), metrics/utils.py:14-42 (accuracy / completion).
+// Brute-force pair arithmetic in unfused fp64 (fp contract off), the arithmetic of the numpy mirror in harness/metrics.py.  Every kernel is
+// deterministic: reductions are two-stage in a fixed order, target slices are combined in slice order, the only atomics are integer
+// histogram counts.  No float atomics, no cooperative launch, no inline assembly.
+#include "../common.h"
+
+// No contraction anywhere in this file: every product and every sum below rounds on its own, as the numpy mirror's do.  (The __dmul_rn /
+// __dadd_rn intrinsics are plain operators in this toolchain and would fuse; the pragma is what keeps a * b + c two roundings.)
+#pragma clang fp contract(off)
+
+#define PB 256          // threads per block of the streaming kernels
+#define NN_TILE 256     // target points staged in LDS per step
+#define KNN_B 128       // threads per block of the neighbour-list kernel: 128 x 32 x 12 B of lists + the tile = 51 KiB of LDS
+#define KNN_MAX 32      // = UG_PCD_MAX_KNN
+
+typedef unsigned long long u64;
+
+// ------------------------------------------------------------------------------------------------------------- masked compaction
+// Order-preserving: block b owns the contiguous pixels [b * chunk, (b + 1) * chunk); counts per block, one exclusive scan, then every block
+// writes its kept pixels behind its offset, 256 at a time with a block scan of the keep flags.
+__device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned* sc, unsigned* total) {
+  const int tid = threadIdx.x;
+  sc[tid] = v;
+  __syncthreads();
+  for (int o = 1; o < PB; o <<= 1) {
+    const unsigned a = tid >= o ? sc[tid - o] : 0u;
+    __syncthreads();
+    sc[tid] += a;
+    __syncthreads();
+  }
+  const unsigned incl = sc[tid];
+  *total = sc[PB - 1];
+  __syncthreads();
+  return incl - v;
+}
+
+__global__ __launch_bounds__(PB) void k_pcd_count(const unsigned char* mask, long n, long chunk, unsigned* counts) {
+  __shared__ unsigned sc[PB];
+  const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
+  unsigned cnt = 0;
+  for (long i = b0 + threadIdx.x; i < b1; i += PB) cnt += mask[i] > 0;
+  unsigned total;
+  block_scan_excl(cnt, sc, &total);
+  if (threadIdx.x == 0) counts[blockIdx.x] = total;
+}
+
+// one workgroup: counts[0 .. nb) -> exclusive offsets in place, counts[PCD_MAXB] = the total
+__global__ __launch_bounds__(PB) void k_pcd_offsets(unsigned* counts, int nb) {
+  __shared__ unsigned sh[PCD_MAXB];
+  for (int i = threadIdx.x; i < nb; i += PB) sh[i] = counts[i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned acc = 0;
+    for (int b = 0; b < nb; ++b) { const unsigned v = sh[b]; sh[b] = acc; acc += v; }
+    counts[PCD_MAXB] = acc;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nb; i += PB) counts[i] = sh[i];
+}
+
+__global__ __launch_bounds__(PB) void k_pcd_scatter(const float* pred, const float* gt, const unsigned char* mask, long n, long chunk,
+                                                    const unsigned* counts, float* p_out, float* g_out) {
+  __shared__ unsigned sc[PB];
+  const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
+  unsigned long base = counts[blockIdx.x];
+  for (long s0 = b0; s0 < b1; s0 += PB) {      // chunk is a multiple of PB: every thread of the block takes every step
+    const long i = s0 + threadIdx.x;
+    const unsigned keep = i < b1 && mask[i] > 0;
+    unsigned total;
+    const unsigned pos = block_scan_excl(keep, sc, &total);
+    if (keep) {
+      const unsigned long o = (base + pos) * 3;
+      p_out[o] = pred[i * 3]; p_out[o + 1] = pred[i * 3 + 1]; p_out[o + 2] = pred[i * 3 + 2];
+      g_out[o] = gt[i * 3]; g_out[o + 1] = gt[i * 3 + 1]; g_out[o + 2] = gt[i * 3 + 2];
+    }
+    base += total;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- exact k-th smallest
+// Radix select over the order-preserving 64-bit key (common.h: pcd_key), 8 bits per pass from the top; a float32 key fills the upper word, so
+// four passes finish it.  State in device memory (unsigned words): sel[0 .. 256) the histogram of the pass, sel[256 .. 258) the key bits fixed
+// so far, sel[258 .. 260) the rank still to find inside that prefix.  Counts are integers: the result does not depend on workgroup order.
+template <typename T>
+__global__ __launch_bounds__(PB) void k_pcd_sel_hist(const T* v, long n, int stride, int offset, int shift, int first, const unsigned* sel,
+                                                     unsigned* hist) {
+  __shared__ unsigned h[256];
+  const int tid = threadIdx.x;
+  h[tid] = 0;
+  __syncthreads();
+  const u64 prefix = ((u64)sel[257] << 32) | sel[256];
+  for (long i = (long)blockIdx.x * PB + tid; i < n; i += (long)gridDim.x * PB) {
+    const u64 key = pcd_key(v[i * stride + offset]);
+    if (first || ((key ^ prefix) >> (shift + 8)) == 0) atomicAdd(&h[(unsigned)(key >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  if (h[tid]) atomicAdd(&hist[tid], h[tid]);
+}
+
+// one workgroup: the bin that holds the wanted rank, the rank inside it; the histogram is zeroed for the next pass; the last pass stores the key
+__global__ __launch_bounds__(256) void k_pcd_sel_scan(unsigned* sel, int shift, int first, int last, u64 k0, u64* res, int slot) {
+  __shared__ unsigned sc[256];
+  const int tid = threadIdx.x;
+  const unsigned cnt = sel[tid];
+  const u64 k = first ? k0 : (((u64)sel[259] << 32) | sel[258]);
+  const u64 prefix0 = first ? 0ull : (((u64)sel[257] << 32) | sel[256]);
+  unsigned total;
+  const unsigned excl = block_scan_excl(cnt, sc, &total);      // ends with a barrier: every thread has read the rank and the prefix
+  sel[tid] = 0;
+  if (cnt && (u64)excl <= k && k < (u64)excl + cnt) {
+    const u64 prefix = prefix0 | ((u64)tid << shift), rank = k - excl;
+    sel[256] = (unsigned)prefix; sel[257] = (unsigned)(prefix >> 32);
+    sel[258] = (unsigned)rank; sel[259] = (unsigned)(rank >> 32);
+    if (last) res[slot] = prefix;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- alignment
+// p.z -= median(p.z), g.z -= median(g.z): float32, as the reference's in-place tensor updates
+__global__ __launch_bounds__(PB) void k_pcd_shift_z(float* p, float* g, long n, const u64* res, int slot_p, int slot_g) {
+  const float pz = pcd_unkey_f32(res[slot_p]), gz = pcd_unkey_f32(res[slot_g]);
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    p[i * 3 + 2] = p[i * 3 + 2] - pz;
+    g[i * 3 + 2] = g[i * 3 + 2] - gz;
+  }
+}
+// |p - c| with the float32 differences widened: the fp64 products are exact, two sums and one square root round, then once to float32
+__global__ __launch_bounds__(PB) void k_pcd_center_norm(const float* p, long n, const u64* res, int slot_c, float* norm) {
+  const float cx = pcd_unkey_f32(res[slot_c]), cy = pcd_unkey_f32(res[slot_c + 1]), cz = pcd_unkey_f32(res[slot_c + 2]);
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    const float fx = p[i * 3] - cx, fy = p[i * 3 + 1] - cy, fz = p[i * 3 + 2] - cz;      // float32 differences
+    const double dx = fx, dy = fy, dz = fz;
+    norm[i] = (float)__dsqrt_rn((dx * dx + dy * dy) + dz * dz);
+  }
+}
+// gather the sampled points (idx NULL: all), pred *= gt_scale / pred_scale, both z += gt_shift_z; float32 clouds and their fp64 copies
+__global__ __launch_bounds__(PB) void k_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32,
+                                                  float* g32, double* p64, double* g64) {
+  for (long j = (long)blockIdx.x * PB + threadIdx.x; j < ns; j += (long)gridDim.x * PB) {
+    const long i = idx ? idx[j] : j;
+    const float px = p[i * 3] * ratio, py = p[i * 3 + 1] * ratio, pz = p[i * 3 + 2] * ratio + gz;
+    const float gx = g[i * 3], gy = g[i * 3 + 1], gzz = g[i * 3 + 2] + gz;
+    p32[j * 3] = px; p32[j * 3 + 1] = py; p32[j * 3 + 2] = pz;
+    g32[j * 3] = gx; g32[j * 3 + 1] = gy; g32[j * 3 + 2] = gzz;
+    p64[j * 3] = px; p64[j * 3 + 1] = py; p64[j * 3 + 2] = pz;
+    g64[j * 3] = gx; g64[j * 3 + 1] = gy; g64[j * 3 + 2] = gzz;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- nearest neighbour
+// ((r0 x + r1 y) + r2 z) + t per coordinate, T row-major 4x4 in device memory; NULL leaves the point alone
+__device__ __forceinline__ void pcd_move(const double* T, double& x, double& y, double& z) {
+  if (!T) return;
+  const double a = x, b = y, c = z;
+  x = ((T[0] * a + T[1] * b) + T[2] * c) + T[3];
+  y = ((T[4] * a + T[5] * b) + T[6] * c) + T[7];
+  z = ((T[8] * a + T[9] * b) + T[10] * c) + T[11];
+}
+__device__ __forceinline__ double pcd_d2(double x, double y, double z, const double* t) {
+  const double dx = x - t[0], dy = y - t[1], dz = z - t[2];
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// One query per thread; blockIdx.y owns the targets [y * slice, (y + 1) * slice), staged through LDS NN_TILE at a time and read by broadcast.
+// Targets are visited in index order and only a strictly smaller squared distance replaces the best: ties stay with the lowest index.
+__global__ __launch_bounds__(PB) void k_pcd_nn(const double* q, long nq, const double* t, long nt, const double* T44, long slice, int* pidx,
+                                               double* pdist) {
+  __shared__ double tile[NN_TILE * 3];
+  const long i = (long)blockIdx.x * PB + threadIdx.x;
+  const bool live = i < nq;
+  double x = 0, y = 0, z = 0;
+  if (live) { x = q[i * 3]; y = q[i * 3 + 1]; z = q[i * 3 + 2]; pcd_move(T44, x, y, z); }
+  const long t0 = (long)blockIdx.y * slice, t1 = t0 + slice < nt ? t0 + slice : nt;
+  double best = INFINITY;
+  long bi = t0;
+  for (long base = t0; base < t1; base += NN_TILE) {
+    const int cnt = (int)(t1 - base < NN_TILE ? t1 - base : NN_TILE);
+    for (int e = threadIdx.x; e < cnt * 3; e += PB) tile[e] = t[base * 3 + e];
+    __syncthreads();
+    if (live)
+      for (int j = 0; j < cnt; ++j) {
+        const double d2 = pcd_d2(x, y, z, tile + j * 3);
+        if (d2 < best) { best = d2; bi = base + j; }
+      }
+    __syncthreads();
+  }
+  if (live) { pdist[(long)blockIdx.y * nq + i] = best; pidx[(long)blockIdx.y * nq + i] = (int)bi; }
+}
+// the slices in slice order, again only a strictly smaller value wins; the distance is the square root of the winner
+__global__ __launch_bounds__(PB) void k_pcd_nn_combine(const int* pidx, const double* pdist, long nq, int ny, int* idx, double* dist) {
+  const long i = (long)blockIdx.x * PB + threadIdx.x;
+  if (i >= nq) return;
+  double best = pdist[i];
+  int bi = pidx[i];
+  for (int y = 1; y < ny; ++y) {
+    const double d2 = pdist[(long)y * nq + i];
+    if (d2 < best) { best = d2; bi = pidx[(long)y * nq + i]; }
+  }
+  idx[i] = bi; dist[i] = __dsqrt_rn(best);
+}
+
+// ------------------------------------------------------------------------------------------------------------- fixed-order reductions
+__device__ __forceinline__ double pcd_block_sum(double v, double* sh) {
+  const int tid = threadIdx.x;
+  sh[tid] = v;
+  __syncthreads();
+  for (int o = PB / 2; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+// Kabsch sums over the correspondences (dist < threshold): n, sum s (3), sum d (3), sum d s^T (9, row = d), sum dist^2; s = the moved query
+__global__ __launch_bounds__(PB) void k_pcd_kabsch(const double* q, const double* t, long nq, const double* T44, const int* idx, const double* dist,
+                                                   double threshold, double* part) {
+  __shared__ double sh[PB];
+  double a[17];
+  for (int k = 0; k < 17; ++k) a[k] = 0;
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < nq; i += (long)gridDim.x * PB) {
+    const double d = dist[i];
+    if (!(d < threshold)) continue;
+    double s[3] = {q[i * 3], q[i * 3 + 1], q[i * 3 + 2]};
+    pcd_move(T44, s[0], s[1], s[2]);
+    const double* g = t + (long)idx[i] * 3;
+    a[0] += 1.0;
+    for (int r = 0; r < 3; ++r) { a[1 + r] += s[r]; a[4 + r] += g[r]; }
+    for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) a[7 + r * 3 + cc] += g[r] * s[cc];
+    a[16] += d * d;
+  }
+  for (int k = 0; k < 17; ++k) {
+    const double r = pcd_block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 17 + k] = r;
+  }
+}
+__global__ __launch_bounds__(PB) void k_pcd_sum(const double* v, long n, double* part) {
+  __shared__ double sh[PB];
+  double a = 0;
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) a += v[i];
+  const double r = pcd_block_sum(a, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+__global__ __launch_bounds__(PB) void k_pcd_move(const double* q, long n, const double* T44, double* out) {
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
+    pcd_move(T44, x, y, z);
+    out[i * 3] = x; out[i * 3 + 1] = y; out[i * 3 + 2] = z;
+  }
+}
+// |n_t[idx] . n_q| per query
+__global__ __launch_bounds__(PB) void k_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot) {
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    const double* a = nt + (long)idx[i] * 3;
+    const double* b = nq + i * 3;
+    dot[i] = fabs((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------- KNN covariance normals
+// One query per thread.  The running top-k list, sorted by (squared distance, index), lives in LDS in a [k][thread] layout: the threads of
+// a wave touch consecutive words.  Targets arrive in index order, so an equal distance goes behind the entries already there.  Then the mean
+// and the covariance of the k neighbours in fp64 (list order) and a cyclic Jacobi eigen-solve with a fixed number of sweeps.
+__global__ __launch_bounds__(KNN_B) void k_pcd_knn(const double* pts, long n, int k, int* nbr, double* normals) {
+  __shared__ double ld[KNN_MAX][KNN_B];
+  __shared__ int li[KNN_MAX][KNN_B];
+  __shared__ double tile[KNN_B * 3];
+  const int tid = threadIdx.x;
+  const long i = (long)blockIdx.x * KNN_B + tid;
+  const bool live = i < n;
+  double x = 0, y = 0, z = 0;
+  if (live) { x = pts[i * 3]; y = pts[i * 3 + 1]; z = pts[i * 3 + 2]; }
+  int cnt = 0;
+  for (long base = 0; base < n; base += KNN_B) {
+    const int tc = (int)(n - base < KNN_B ? n - base : KNN_B);
+    for (int e = tid; e < tc * 3; e += KNN_B) tile[e] = pts[base * 3 + e];
+    __syncthreads();
+    if (live)
+      for (int j = 0; j < tc; ++j) {
+        const double d2 = pcd_d2(x, y, z, tile + j * 3);
+        if (cnt < k || d2 < ld[cnt - 1][tid]) {
+          int pos = cnt < k ? cnt++ : k - 1;
+          while (pos > 0 && ld[pos - 1][tid] > d2) { ld[pos][tid] = ld[pos - 1][tid]; li[pos][tid] = li[pos - 1][tid]; --pos; }
+          ld[pos][tid] = d2; li[pos][tid] = (int)(base + j);
+        }
+      }
+    __syncthreads();
+  }
+  if (!live) return;
+  if (nbr) for (int j = 0; j < k; ++j) nbr[i * k + j] = li[j][tid];
+  double nx = 0, ny = 0, nz = 1;
+  if (k >= 3) {
+    double m[3] = {0, 0, 0};
+    for (int j = 0; j < k; ++j) { const double* p = pts + (long)li[j][tid] * 3; m[0] += p[0]; m[1] += p[1]; m[2] += p[2]; }
+    m[0] /= k; m[1] /= k; m[2] /= k;
+    double a[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+    for (int j = 0; j < k; ++j) {
+      const double* p = pts + (long)li[j][tid] * 3;
+      const double d[3] = {p[0] - m[0], p[1] - m[1], p[2] - m[2]};
+      for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) a[r][c] += d[r] * d[c];
+    }
+    for (int r = 0; r < 3; ++r) for (int c = r; c < 3; ++c) { a[r][c] /= k; a[c][r] = a[r][c]; }
+    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    for (int sweep = 0; sweep < 12; ++sweep)
+#pragma unroll
+      for (int pq = 0; pq < 3; ++pq) {      // unrolled: p and q are constants, the two matrices stay in registers
+        const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+        for (int r = 0; r < 3; ++r) {        // A <- A J
+          const double arp = a[r][p], arq = a[r][q];
+          a[r][p] = cs * arp - sn * arq; a[r][q] = sn * arp + cs * arq;
+        }
+        for (int r = 0; r < 3; ++r) {        // A <- J^T A,  V <- V J
+          const double apr = a[p][r], aqr = a[q][r];
+          a[p][r] = cs * apr - sn * aqr; a[q][r] = sn * apr + cs * aqr;
+          const double vrp = v[r][p], vrq = v[r][q];
+          v[r][p] = cs * vrp - sn * vrq; v[r][q] = sn * vrp + cs * vrq;
+        }
+      }
+    double em = a[0][0], ex = v[0][0], ey = v[1][0], ez = v[2][0];      // the column of the smallest eigenvalue, without a dynamic index
+    if (a[1][1] < em) { em = a[1][1]; ex = v[0][1]; ey = v[1][1]; ez = v[2][1]; }
+    if (a[2][2] < em) { em = a[2][2]; ex = v[0][2]; ey = v[1][2]; ez = v[2][2]; }
+    const double len = sqrt(ex * ex + ey * ey + ez * ez);
+    if (len > 0) { nx = ex / len; ny = ey / len; nz = ez / len; }
+  }
+  normals[i * 3] = nx; normals[i * 3 + 1] = ny; normals[i * 3 + 2] = nz;
+}
+
+// ------------------------------------------------------------------------------------------------------------- launchers
+static int pcd_blocks(long n) { long b = (n + PB - 1) / PB; return (int)(b > PCD_MAXB ? PCD_MAXB : (b < 1 ? 1 : b)); }
+
+void launch_pcd_compact(const float* pred, const float* gt, const unsigned char* mask, long n, unsigned* counts, float* p_out, float* g_out,
+                        hipStream_t s) {
+  const int nb = pcd_blocks(n);
+  const long chunk = ((n + nb - 1) / nb + PB - 1) / PB * PB;      // a multiple of PB; nb * chunk >= n
+  hipLaunchKernelGGL(k_pcd_count, dim3(nb), dim3(PB), 0, s, mask, n, chunk, counts);
+  hipLaunchKernelGGL(k_pcd_offsets, dim3(1), dim3(PB), 0, s, counts, nb);
+  hipLaunchKernelGGL(k_pcd_scatter, dim3(nb), dim3(PB), 0, s, pred, gt, mask, n, chunk, counts, p_out, g_out);
+}
+
+void launch_pcd_select(const void* v, int is_f64, long n, int stride, int offset, unsigned long long k, unsigned* sel, unsigned long long* res,
+                       int slot, hipStream_t s) {
+  (void)hipMemsetAsync(sel, 0, PCD_SEL_WORDS * sizeof(unsigned), s);
+  const int passes = is_f64 ? 8 : 4, nb = pcd_blocks(n);
+  for (int p = 0; p < passes; ++p) {
+    const int shift = 56 - 8 * p;
+    if (is_f64) hipLaunchKernelGGL(k_pcd_sel_hist<double>, dim3(nb), dim3(PB), 0, s, (const double*)v, n, stride, offset, shift, p == 0, sel, sel);
+    else hipLaunchKernelGGL(k_pcd_sel_hist<float>, dim3(nb), dim3(PB), 0, s, (const float*)v, n, stride, offset, shift, p == 0, sel, sel);
+    hipLaunchKernelGGL(k_pcd_sel_scan, dim3(1), dim3(256), 0, s, sel, shift, p == 0, p == passes - 1, (u64)k, (u64*)res, slot);
+  }
+}
+void launch_pcd_shift_z(float* p, float* g, long n, const unsigned long long* res, int slot_p, int slot_g, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_shift_z, dim3(pcd_blocks(n)), dim3(PB), 0, s, p, g, n, (const u64*)res, slot_p, slot_g);
+}
+void launch_pcd_center_norm(const float* p, long n, const unsigned long long* res, int slot_c, float* norm, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_center_norm, dim3(pcd_blocks(n)), dim3(PB), 0, s, p, n, (const u64*)res, slot_c, norm);
+}
+void launch_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32, float* g32, double* p64, double* g64,
+                      hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_align, dim3(pcd_blocks(ns)), dim3(PB), 0, s, p, g, idx, ns, ratio, gz, p32, g32, p64, g64);
+}
+
+// how the targets are split over blockIdx.y: enough slices that about 2048 workgroups are in flight, whole tiles per slice, at most 64 slices
+static long pcd_nn_slice(long nq, long nt, int* ny) {
+  const long bx = (nq + PB - 1) / PB, tiles = (nt + NN_TILE - 1) / NN_TILE;
+  long want = 2048 / (bx < 1 ? 1 : bx);
+  want = want < 1 ? 1 : (want > 64 ? 64 : want);
+  if (want > tiles) want = tiles;
+  if (want < 1) want = 1;
+  const long slice = (tiles + want - 1) / want * NN_TILE;
+  *ny = (int)((nt + slice - 1) / slice);
+  if (*ny < 1) *ny = 1;
+  return slice;
+}
+int pcd_nn_slices(long nq, long nt) { int ny; pcd_nn_slice(nq, nt, &ny); return ny; }
+
+void launch_pcd_nn(const double* q, long nq, const double* t, long nt, const double* T44, int* idx, double* dist, int* pidx, double* pdist,
+                   hipStream_t s) {
+  int ny;
+  const long slice = pcd_nn_slice(nq, nt, &ny);
+  const int bx = (int)((nq + PB - 1) / PB);
+  hipLaunchKernelGGL(k_pcd_nn, dim3(bx, ny), dim3(PB), 0, s, q, nq, t, nt, T44, slice, pidx, pdist);
+  hipLaunchKernelGGL(k_pcd_nn_combine, dim3(bx), dim3(PB), 0, s, pidx, pdist, nq, ny, idx, dist);
+}
+void launch_pcd_kabsch(const double* q, const double* t, long nq, const double* T44, const int* idx, const double* dist, double threshold,
+                       double* part, int* nb, hipStream_t s) {
+  *nb = pcd_blocks(nq);
+  hipLaunchKernelGGL(k_pcd_kabsch, dim3(*nb), dim3(PB), 0, s, q, t, nq, T44, idx, dist, threshold, part);
+}
+void launch_pcd_move(const double* q, long n, const double* T44, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_move, dim3(pcd_blocks(n)), dim3(PB), 0, s, q, n, T44, out);
+}
+void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr, double* normals, hipStream_t s) {
+  const int k = (int)(n < knn ? n : knn);
+  hipLaunchKernelGGL(k_pcd_knn, dim3((unsigned)((n + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, pts, n, k, nbr, normals);
+}
+void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_normal_dot, dim3(pcd_blocks(n)), dim3(PB), 0, s, nq, nt, idx, n, dot);
+}
+void launch_pcd_sum(const double* v, long n, double* part, int* nb, hipStream_t s) {
+  *nb = pcd_blocks(n);
+  hipLaunchKernelGGL(k_pcd_sum, dim3(*nb), dim3(PB), 0, s, v, n, part);
+}

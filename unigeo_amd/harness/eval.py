@@ -1,9 +1,10 @@
 """The evaluation loop - mirrors ``/root/reference/eval.py:10-99`` and ``configs/config_utils.py:3-35``.
 
 Differences kept deliberately small: the YAML path is an argument instead of being hard-coded (eval.py:11),
-dataset / model classes can be passed as objects, and the point-cloud / camera-pose branches (their inputs are not
-produced by the DepthCrafter / StableNormal plugins) are not reproduced.  ``vis_depth: True`` writes the reference's
-depth / normal panels (eval.py:58-62; ``harness/vis.py``).
+dataset / model classes can be passed as objects, and the camera-pose branch (its inputs are not produced by the
+DepthCrafter / StableNormal plugins) is not reproduced.  ``vis_depth: True`` writes the reference's
+depth / normal panels (eval.py:58-62; ``harness/vis.py``).  ``eval_pcd`` (eval.py:66-83) scores
+the model's world points, or those of its aligned depth, against the ground-truth cloud.
 """
 import importlib
 import os
@@ -11,8 +12,9 @@ import os
 import numpy as np
 
 from .io_utils import prepare_gt_label
-from .vis import save_depth_normal_maps
-from .metrics import DEPTH_ALIGNMENTS, MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation
+from .vis import save_depth_normal_maps, write_ply
+from .metrics import (DEPTH_ALIGNMENTS, PCD_KEYS, MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
+                      pcd_evaluation, world_points_from_depth)
 
 
 def import_class_from_module(module_name, class_name):
@@ -66,6 +68,18 @@ def parse_depth_coord(config):
     return coord
 
 
+def parse_pcd_eval_config(config):
+    """``eval_pcd`` (the reference's key, eval.py:66-83): ``pcd_downsample_num`` (default -1: every masked point), optional ``threshold``
+    (ICP correspondence distance, default 0.1) and ``seed`` (default 0; a clip draws with ``seed + data index``) -> dict, or ``None`` without
+    the key.  ``vis_pcd`` without ``eval_pcd`` is a ``ValueError``."""
+    if "eval_pcd" not in config:
+        if config.get("vis_pcd"):
+            raise ValueError("vis_pcd needs eval_pcd: the point clouds it writes are the ones eval_pcd aligns")
+        return None
+    cfg = config["eval_pcd"] or {}
+    return {"downsample_num": int(cfg.get("pcd_downsample_num", -1)), "threshold": float(cfg.get("threshold", 0.1)), "seed": int(cfg.get("seed", 0))}
+
+
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
              device_metrics=False, models=None):
     """Run the reference's per-clip loop.  With ``world > 1`` this rank only evaluates clips
@@ -85,9 +99,15 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     coloured depth | colour bar, composed on the GPU from the resident outputs under ``device_metrics=True`` and by the numpy mirror otherwise
     (DESIGN.md section 15).  Rows and CSV do not change.
     ``eval_normal`` on a dataset without ground-truth normals (the RGB-D loaders of ``harness/rgbd.py``) raises ``ValueError`` at the first such clip,
-    before the model runs on it."""
+    before the model runs on it.
+    ``eval_pcd`` (eval.py:66-83) adds ``acc / comp / nc1 / nc2`` and their medians: the model's ``pred_world_pts`` when it
+    returns them, else ``world_points_from_depth`` of its depth with ``eval_depth``'s ``max_depth`` and clips (on the resident depth under
+    ``device_metrics=True``), against ``gt_world_pts`` on ``gt_masks`` through ``pcd_evaluation`` / ``ug_eval_pcd``.  ``vis_pcd: True`` writes
+    ``save_dir/pcd_{seq}/pred.ply`` and ``gt.ply`` (the aligned clouds before ICP).  ``vis_pcd`` without ``eval_pcd``, or a clip without
+    ``intrinsics`` when the points have to come from the depth, raises ``ValueError`` before the first clip runs."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
     coord = parse_depth_coord(config)
+    pcd_cfg = parse_pcd_eval_config(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
     if dataset is None:
         dataset = import_class_from_module("unigeo_amd.harness", config["dataset"])(**parse_dataset_config(config))
@@ -102,6 +122,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
         if "eval_normal" in config and "cam_normal" not in data:
             raise ValueError(f"eval_normal: clip {seq} of dataset {data.get('_dataset', type(dataset).__name__)!r} has no ground-truth normals "
                              f"(the sample lacks 'cam_normal'); remove eval_normal from the configuration")
+        if pcd_cfg is not None and "intrinsics" not in data and not getattr(mdl, "predicts_world_points", False):
+            raise ValueError(f"eval_pcd: clip {seq} has no 'intrinsics' to turn the predicted depth into world points")
         if verbose:
             print("processing seq:", seq)
         output = mdl.forward(data)
@@ -129,6 +151,27 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
                 metric.update(eng.eval_normal(gt["gt_normals"].numpy(), gt["gt_masks"].numpy()))
             else:
                 metric.update(normal_evaluation(output["pred_normals"], gt["gt_normals"], custom_mask=gt["gt_masks"]))
+        if pcd_cfg is not None:
+            kw = {"threshold": pcd_cfg["threshold"], "downsample_num": pcd_cfg["downsample_num"], "seed": pcd_cfg["seed"] + data_idx}
+            pts = output.get("pred_world_pts")
+            if hasattr(pts, "detach"):
+                pts = pts.detach().cpu().numpy()
+            if pts is None:
+                K = np.stack([np.asarray(k, dtype=np.float32).reshape(3, 3) for k in data["intrinsics"]], 0)
+                if eng is not None:        # the points are made from the resident depth and stay on the device
+                    eng.pcd_world_points(gt["gt_depths"].numpy(), gt["gt_poses"].numpy(), K, max_depth=max_depth, return_points=False, **clips)
+                else:
+                    pts = world_points_from_depth(output["pred_depths"], gt["gt_depths"], gt["gt_poses"], K, max_depth=max_depth, **clips)[0]
+            if eng is not None:
+                res = eng.eval_pcd(pts, gt["gt_world_pts"].numpy(), gt["gt_masks"].numpy(), gt["gt_rgbs"].numpy(), **kw)
+            else:
+                res = pcd_evaluation(pts, gt["gt_world_pts"], gt["gt_masks"], gt["gt_rgbs"], **kw)
+            metric.update({k: res[k] for k in PCD_KEYS})
+            if config.get("vis_pcd"):
+                pcd_dir = os.path.join(save_dir, f"pcd_{seq}")
+                os.makedirs(pcd_dir, exist_ok=True)
+                write_ply(os.path.join(pcd_dir, "pred.ply"), *res["pred_pcd"])
+                write_ply(os.path.join(pcd_dir, "gt.ply"), *res["gt_pcd"])
         if config.get("vis_depth"):
             vis_dir = os.path.join(save_dir, f"depth_{seq}")
             os.makedirs(vis_dir, exist_ok=True)

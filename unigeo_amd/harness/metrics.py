@@ -6,6 +6,8 @@
   plus its median / L1-scale / metric alignment modes and the pre- and post-alignment clamps.
 * ``depth_evaluation_in_global_coord`` <- ``/root/reference/metrics/eval_depth.py:250-441``: the aligned depth back-projected,
   moved into the world frame, and evaluated as the distance from the world origin.
+* ``world_points_from_depth`` / ``pcd_evaluation`` <- ``/root/reference/metrics/eval_pcd.py:10-168`` with ``pcd_alignment.py``,
+  ``metrics/utils.py:14-42`` and the Open3D calls it makes (point-to-point ICP, KNN normals) restated in numpy.
 * ``normal_evaluation`` <- ``/root/reference/metrics/eval_normal.py:4-72``: angular error in degrees, mean / median /
   rmse / % under 5, 7.5, 11.25, 22.5, 30 degrees.
 * ``MetricsManager``    <- ``/root/reference/metrics/save_utils.py:5-90``: one row per sequence, NaN for missing
@@ -135,6 +137,242 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
     return res, (s_ret, float(t)), emap.reshape(np.shape(_np(ground_truth_depth_original)))
 
 
+def _world_from_depth(pred_depth, gt_depth, cam2world, intrinsics, max_depth, pre_clip_min, pre_clip_max, post_clip_min, post_clip_max):
+    """The first half of ``depth_evaluation_in_global_coord``, shared with ``world_points_from_depth``: mask1, fit 1 on the pre-clipped
+    prediction, ``d = s_d * pred + t_d`` in float32 from the ORIGINAL prediction, the post clips, then the float64 back-projection with integer
+    pixel indices and the world transform -> ``(world float64 [Nf,H,W,3], mask1 [Nf,H,W], (s_d, t_d) float32)``."""
+    f32, f64 = np.float32, np.float64
+    pred = _np(pred_depth).astype(f32)
+    if pred.ndim == 2:
+        pred = pred[None]
+    nf, h, w = pred.shape
+    gt = _np(gt_depth).astype(f32).reshape(pred.shape)
+    poses, K = _np(cam2world).reshape(nf, 4, 4), _np(intrinsics).reshape(nf, 3, 3)
+    mask = (gt > 0) & (gt < max_depth) if max_depth is not None else gt > 0
+    p = pred[mask]
+    if pre_clip_min is not None:
+        p = np.maximum(p, f32(pre_clip_min))
+    if pre_clip_max is not None:
+        p = np.minimum(p, f32(pre_clip_max))
+    s_d, t_d = _lstsq_f32(p, gt[mask], np.float64)
+    d = s_d * pred + t_d
+    if post_clip_min is not None:
+        d = np.maximum(d, f32(post_clip_min))
+    if post_clip_max is not None:
+        d = np.minimum(d, f32(post_clip_max))
+    col, row = np.meshgrid(np.arange(w), np.arange(h), indexing="xy")
+    world = np.empty((nf, h, w, 3), f64)
+    for i in range(nf):
+        z = d[i].astype(f64)
+        x = (col - f64(K[i, 0, 2])) * z / f64(K[i, 0, 0])
+        y = (row - f64(K[i, 1, 2])) * z / f64(K[i, 1, 1])
+        cam = np.stack((x, y, z), axis=-1).reshape(-1, 3)
+        world[i] = (cam @ poses[i][:3, :3].T + poses[i][:3, 3][:, None].T).reshape(h, w, 3)
+    return world, mask, (s_d, t_d)
+
+
+def world_points_from_depth(pred_depth, gt_depth, cam2world, intrinsics, max_depth=80, pre_clip_min=None, pre_clip_max=None,
+                            post_clip_min=None, post_clip_max=None):
+    """World points of a predicted depth -> ``(pts float32 [T,H,W,3], (s_d, t_d))``: the first half of
+    ``depth_evaluation_in_global_coord`` - least-squares fit on mask1, aligned and post-clipped float32 depth of every pixel, float64
+    back-projection and world transform - with each coordinate rounded once to float32."""
+    world, _, (s_d, t_d) = _world_from_depth(pred_depth, gt_depth, cam2world, intrinsics, max_depth, pre_clip_min, pre_clip_max,
+                                             post_clip_min, post_clip_max)
+    return world.astype(np.float32), (float(s_d), float(t_d))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Point-cloud evaluation (DESIGN.md section 18): /root/reference/metrics/eval_pcd.py:10-168 with pcd_alignment.py, metrics/utils.py:14-42
+# and the Open3D calls (registration_icp, estimate_normals) restated in numpy.
+PCD_KEYS = ("acc", "comp", "nc1", "nc2", "acc_med", "comp_med", "nc1_med", "nc2_med")
+
+
+def _lower_median(a):
+    """``torch.nanmedian`` of finite values: element ``(n - 1) // 2`` of the sorted array."""
+    k = (a.shape[0] - 1) // 2
+    return np.partition(a, k, axis=0)[k]
+
+
+def pcd_align(p, g):
+    """``Regr3D_t_ScaleShiftInv(norm_mode=False, gt_scale=True)`` plus ``eval_pcd.py:67-69`` on the masked float32 points ``p`` (prediction)
+    and ``g`` (ground truth), ``[n,3]`` -> ``(p', g', (pred_scale, gt_scale, pred_shift_z, gt_shift_z))``, everything float32.  The norms
+    behind the two scales are taken in float64 from the float32 differences and rounded once."""
+    f32 = np.float32
+    p, g = np.array(p, f32), np.array(g, f32)
+    pz, gz = _lower_median(p[:, 2]), _lower_median(g[:, 2])
+    p[:, 2] -= pz
+    g[:, 2] -= gz
+
+    def scale(x):
+        diff = (x - _lower_median(x)).astype(np.float64)
+        return _lower_median(np.sqrt((diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2]).astype(f32))
+    gs, ps = scale(g), np.clip(scale(p), f32(1e-3), f32(1e3))
+    p *= f32(gs) / f32(ps)
+    p[:, 2] += gz
+    g[:, 2] += gz
+    return p, g, (ps, gs, pz, gz)
+
+
+def _d2(q, t):
+    dx, dy, dz = q[:, None, 0] - t[None, :, 0], q[:, None, 1] - t[None, :, 1], q[:, None, 2] - t[None, :, 2]
+    return (dx * dx + dy * dy) + dz * dz
+
+
+def nn_brute(q, t, chunk=1 << 22):
+    """Nearest target of every query, float64 ``[n,3]`` each -> ``(distance float64, index)``: the smallest
+    ``(dx*dx + dy*dy) + dz*dz``, ties to the lowest index; the distance is its square root."""
+    q, t = np.asarray(q, np.float64), np.asarray(t, np.float64)
+    idx, dist = np.empty(len(q), np.int64), np.empty(len(q), np.float64)
+    step = max(1, chunk // max(1, len(t)))
+    for a in range(0, len(q), step):
+        d2 = _d2(q[a:a + step], t)
+        i = np.argmin(d2, axis=1)
+        idx[a:a + step], dist[a:a + step] = i, np.sqrt(d2[np.arange(len(i)), i])
+    return dist, idx
+
+
+def _nn(q, t):
+    try:
+        from scipy.spatial import cKDTree
+    except ImportError:
+        return nn_brute(q, t)
+    return cKDTree(t).query(q)
+
+
+def knn_brute(pts, k, chunk=1 << 22):
+    """The ``min(k, n)`` nearest points of every point in its own cloud, itself included, ordered by (squared distance, index) ->
+    ``[n, min(k, n)]`` indices."""
+    pts = np.asarray(pts, np.float64)
+    n = len(pts)
+    k = min(k, n)
+    out = np.empty((n, k), np.int64)
+    step = max(1, chunk // max(1, n))
+    for a in range(0, n, step):
+        d2 = _d2(pts[a:a + step], pts)
+        if k < n:          # keep only what can be among the k nearest, then sort that stably; a tie at the k-th distance sorts the whole row
+            kth = np.partition(d2, k - 1, axis=1)[:, k - 1]
+            keep = d2 <= kth[:, None]
+            if (keep.sum(1) == k).all():
+                cols = np.nonzero(keep)[1].reshape(-1, k)
+                o = np.argsort(np.take_along_axis(d2, cols, 1), axis=1, kind="stable")
+                out[a:a + step] = np.take_along_axis(cols, o, 1)
+                continue
+        out[a:a + step] = np.argsort(d2, axis=1, kind="stable")[:, :k]
+    return out
+
+
+def knn_normals(pts, knn=30):
+    """Open3D's ``estimate_normals()`` with its default KNN search: the unit eigenvector of the smallest eigenvalue of the float64 covariance
+    of the ``min(knn, n)`` nearest points about their mean; ``(0, 0, 1)`` with fewer than 3 points.  The sign is free."""
+    pts = np.asarray(pts, np.float64)
+    n = len(pts)
+    if min(n, knn) < 3:
+        return np.tile(np.array([0.0, 0.0, 1.0]), (n, 1))
+    nb = pts[knn_brute(pts, knn)]
+    c = nb - nb.mean(1, keepdims=True)
+    cov = np.einsum("nki,nkj->nij", c, c) / nb.shape[1]
+    return np.linalg.eigh(cov)[1][:, :, 0]
+
+
+def _move(T, p):
+    """``((r0 x + r1 y) + r2 z) + t`` per coordinate, float64."""
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return np.stack([((T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z) + T[r, 3] for r in range(3)], 1)
+
+
+def umeyama_rigid(src, dst):
+    """Least-squares rigid ``dst ~ R src + t`` (Umeyama without scaling) -> 4x4; the identity for no point."""
+    U4 = np.eye(4)
+    if len(src) == 0:
+        return U4
+    ms, md = src.mean(0), dst.mean(0)
+    H = (dst - md).T @ (src - ms) / len(src)
+    U, _, Vt = np.linalg.svd(H)
+    S = np.diag([1.0, 1.0, 1.0 if np.linalg.det(U) * np.linalg.det(Vt) >= 0 else -1.0])
+    R = U @ S @ Vt
+    U4[:3, :3], U4[:3, 3] = R, md - R @ ms
+    return U4
+
+
+def icp_point_to_point(src, dst, threshold, max_iteration=30, nn=_nn):
+    """Open3D's ``registration_icp`` with ``TransformationEstimationPointToPoint``, identity start, relative fitness / rmse 1e-6 ->
+    ``(T, iterations, fitness, inlier_rmse, history)``; ``history`` lists ``(fitness, rmse)`` of every evaluation."""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+
+    def evaluate(T):
+        moved = _move(T, src)
+        if len(src) == 0 or len(dst) == 0:
+            return 0.0, 0.0, moved[:0], dst[:0]
+        d, i = nn(moved, dst)
+        ok = d < threshold
+        nc = int(ok.sum())
+        return nc / len(src), (math.sqrt(float((d[ok] * d[ok]).sum()) / nc) if nc else 0.0), moved[ok], dst[i[ok]]
+    T = np.eye(4)
+    fit, rmse, s, d = evaluate(T)
+    hist, it = [(fit, rmse)], 0
+    for it in range(1, max_iteration + 1):
+        T = umeyama_rigid(s, d) @ T
+        prev = (fit, rmse)
+        fit, rmse, s, d = evaluate(T)
+        hist.append((fit, rmse))
+        if abs(prev[0] - fit) < 1e-6 and abs(prev[1] - rmse) < 1e-6:
+            break
+    return T, it, fit, rmse, hist
+
+
+def pcd_scores(gt_pts, pred_pts, gt_normals, pred_normals, nn=_nn):
+    """``accuracy`` and ``completion`` of ``metrics/utils.py:14-42`` -> the eight reference keys."""
+    d1, i1 = nn(pred_pts, gt_pts)
+    d2, i2 = nn(gt_pts, pred_pts)
+    n1 = np.abs(np.sum(gt_normals[i1] * pred_normals, axis=-1))
+    n2 = np.abs(np.sum(gt_normals * pred_normals[i2], axis=-1))
+    return {"acc": float(np.mean(d1)), "comp": float(np.mean(d2)), "nc1": float(np.mean(n1)), "nc2": float(np.mean(n2)),
+            "acc_med": float(np.median(d1)), "comp_med": float(np.median(d2)), "nc1_med": float(np.median(n1)), "nc2_med": float(np.median(n2))}
+
+
+def pcd_metrics_from_clouds(p, g, threshold=0.1, knn=30, max_iteration=30, nn=_nn):
+    """ICP, normals and scores of two aligned float32 clouds ``[n,3]`` -> the eight keys plus the ICP record; NaN scores for no point."""
+    p64, g64 = np.asarray(p, np.float32).astype(np.float64), np.asarray(g, np.float32).astype(np.float64)
+    if len(p64) == 0:
+        res = {k: math.nan for k in PCD_KEYS}
+        res.update(icp_iterations=0, icp_fitness=0.0, icp_rmse=0.0, transformation=np.eye(4))
+        return res
+    T, it, fit, rmse, hist = icp_point_to_point(p64, g64, threshold, max_iteration, nn)
+    moved = _move(T, p64)
+    res = pcd_scores(g64, moved, knn_normals(g64, knn), knn_normals(moved, knn), nn)
+    res.update(icp_iterations=it, icp_fitness=fit, icp_rmse=rmse, transformation=T, icp_history=hist)
+    return res
+
+
+def pcd_sample_indices(n, downsample_num, seed):
+    """The sampled positions among the ``n`` masked points: ``default_rng(seed).choice`` without replacement when
+    ``0 < downsample_num < n``, else ``None`` (every point)."""
+    if 0 < downsample_num < n:
+        return np.random.default_rng(seed).choice(n, downsample_num, replace=False)
+    return None
+
+
+def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30):
+    """``pcd_evaluation`` of the reference (``metrics/eval_pcd.py:10-168``) -> dict: masked selection in pixel order,
+    ``pcd_align``, seeded downsampling (the reference draws from the unseeded global generator and raises when ``downsample_num`` exceeds the
+    point count; here that uses every point), point-to-point ICP from the identity, KNN normals, ``accuracy`` / ``completion``.
+    ``pred_pcd`` / ``gt_pcd`` are ``(points float32 [n,3], colours float32 [n,3])`` taken before ICP (zeros without ``rgbs``)."""
+    m = _np(masks).reshape(-1) > 0
+    p = _np(pred_pts).astype(np.float32).reshape(-1, 3)[m]
+    g = _np(gt_pts).astype(np.float32).reshape(-1, 3)[m]
+    col = np.zeros((len(p), 3), np.float32) if rgbs is None else _np(rgbs).astype(np.float32).reshape(-1, 3)[m]
+    scal = (math.nan,) * 4
+    if len(p):
+        p, g, scal = pcd_align(p, g)
+    idx = pcd_sample_indices(len(p), downsample_num, seed)
+    if idx is not None:
+        p, g, col = p[idx], g[idx], col[idx]
+    res = pcd_metrics_from_clouds(p, g, threshold, knn, max_iteration)
+    res.update(n_points=len(p), pred_scale=float(scal[0]), gt_scale=float(scal[1]), pred_shift_z=float(scal[2]), gt_shift_z=float(scal[3]),
+               pred_pcd=(p, col), gt_pcd=(g, col.copy()))
+    return res
+
+
 def depth_evaluation_in_global_coord(predicted_depth_original, ground_truth_depth_original, ground_truth_radius, cam2world, intrinsics,
                                      max_depth=80, custom_mask=None, post_clip_min=None, post_clip_max=None, pre_clip_min=None,
                                      pre_clip_max=None, align_with_lstsq=False, align_with_lad=False, align_with_lad2=False,
@@ -164,38 +402,17 @@ def depth_evaluation_in_global_coord(predicted_depth_original, ground_truth_dept
                                   "reference) are not restated")
     if not align_with_lstsq:
         raise ValueError("depth_evaluation_in_global_coord needs align_with_lstsq=True (the reference asserts it)")
-    f32, f64 = np.float32, np.float64
-    pred = _np(predicted_depth_original).astype(f32)
-    if pred.ndim == 2:
-        pred = pred[None]
-    nf, h, w = pred.shape
-    gt = _np(ground_truth_depth_original).astype(f32).reshape(pred.shape)
-    gr = _np(ground_truth_radius).astype(f32).reshape(pred.shape)
-    poses, K = _np(cam2world).reshape(nf, 4, 4), _np(intrinsics).reshape(nf, 3, 3)
-    mask = (gt > 0) & (gt < max_depth) if max_depth is not None else gt > 0
-    p = pred[mask]
-    if pre_clip_min is not None:
-        p = np.maximum(p, f32(pre_clip_min))
-    if pre_clip_max is not None:
-        p = np.minimum(p, f32(pre_clip_max))
-    s_d, t_d = _lstsq_f32(p, gt[mask], np.float64)
-    d = s_d * pred + t_d
-    if post_clip_min is not None:
-        d = np.maximum(d, f32(post_clip_min))
-    if post_clip_max is not None:
-        d = np.minimum(d, f32(post_clip_max))
-    col, row = np.meshgrid(np.arange(w), np.arange(h), indexing="xy")
-    r = np.empty(pred.shape, f32)
+    f32 = np.float32
+    world, mask, (s_d, t_d) = _world_from_depth(predicted_depth_original, ground_truth_depth_original, cam2world, intrinsics, max_depth,
+                                                pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)
+    nf, h, w = mask.shape
+    gr = _np(ground_truth_radius).astype(f32).reshape(mask.shape)
+    r = np.empty(mask.shape, f32)
     for i in range(nf):
-        z = d[i].astype(f64)
-        x = (col - f64(K[i, 0, 2])) * z / f64(K[i, 0, 0])
-        y = (row - f64(K[i, 1, 2])) * z / f64(K[i, 1, 1])
-        cam = np.stack((x, y, z), axis=-1).reshape(-1, 3)
-        world = cam @ poses[i][:3, :3].T + poses[i][:3, 3][:, None].T
-        r[i] = np.linalg.norm(world, axis=-1).reshape(h, w)
+        r[i] = np.linalg.norm(world[i].reshape(-1, 3), axis=-1).reshape(h, w)
     s_r, t_r = _lstsq_f32(r[mask], gr[mask], np.float64)
     radius_map = s_r * r + t_r
-    sel = mask if custom_mask is None else mask & _np(custom_mask).astype(bool).reshape(pred.shape)
+    sel = mask if custom_mask is None else mask & _np(custom_mask).astype(bool).reshape(mask.shape)
     res = _metric_values(radius_map[sel], gr[sel])
     if return_fits:
         return res, radius_map, (float(s_r), float(t_r)), (float(s_d), float(t_d))

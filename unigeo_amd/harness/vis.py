@@ -195,3 +195,30 @@ def save_depth_normal_maps(depth_maps, normal_maps, path, rgbs=None, engine=None
     for i, im in enumerate(panels):
         write(os.path.join(path, f"frame_{i:04d}"), im)
     return panels
+
+
+def write_ply(path, points, colors=None):
+    """A point cloud as binary little-endian PLY: float32 x y z and uint8 red green blue per vertex (``vis_pcd``).
+    ``colors`` float in [0, 1] (``u8 = trunc(c * 255)`` after clipping) or ``None`` for white."""
+    pts = np.asarray(points, np.float32).reshape(-1, 3)
+    col = np.full((len(pts), 3), 255, np.uint8) if colors is None else (np.clip(np.asarray(colors, np.float32).reshape(-1, 3), 0.0, 1.0) * np.float32(255)).astype(np.uint8)
+    rec = np.empty(len(pts), np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)]))
+    rec["xyz"], rec["rgb"] = pts, col
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n" % len(pts))
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_ply(path):
+    """What ``write_ply`` wrote -> ``(points float32 [n,3], colours uint8 [n,3])``."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii").split("\n")
+    if head[0] != "ply" or head[1] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    n = int(next(l for l in head if l.startswith("element vertex")).split()[2])
+    rec = np.frombuffer(raw, np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3)]), count=n, offset=end)
+    return rec["xyz"].copy(), rec["rgb"].copy()
