@@ -237,6 +237,16 @@ int ug_pcd_world_points(ug_ctx* ctx, const float* pred_depth /* NULL: resident d
 int ug_eval_pcd(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, const float* gt_pts, const unsigned char* mask, long n_pixels,
                 const long* sample_idx /* or NULL */, long n_sample, const ug_pcd_opts* opts, double* out32, float* pred_cloud_out /* or NULL */,
                 float* gt_cloud_out /* or NULL */);
+/* ug_eval_pcd_fps: ug_eval_pcd with farthest-point sampling in place of the index list (the reference's disabled branch, metrics/eval_pcd.py:84-93,
+ *   172-193).  After the alignment of ALL masked points, each aligned float32 cloud is sampled on its own: m[j] = +inf for a
+ *   point with three finite coordinates, else -1; step i picks s = argmax m (ties to the lowest index, so step 0 is the first finite point), then
+ *   m[j] = d if d < m[j] with d = (dx*dx + dy*dy) + dz*dz in unfused float32.  The n_sample picked points of each cloud, in pick order, go on to
+ *   the ICP, the normals and the scores.  n_sample <= 0 or n_sample >= the masked count: every point, no sampling, ug_eval_pcd with no index list.
+ *   out32 as ug_eval_pcd (n_points = the sampled count); pred_idx_out / gt_idx_out (host, [n_points], may be NULL): the picked positions in the
+ *   masked sequence (0 .. n_points - 1 without sampling).  Errors as ug_eval_pcd; the 2^40 pair cap counts the sampled sizes. */
+int ug_eval_pcd_fps(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, const float* gt_pts, const unsigned char* mask, long n_pixels,
+                    long n_sample, const ug_pcd_opts* opts, double* out32, float* pred_cloud_out /* or NULL */, float* gt_cloud_out /* or NULL */,
+                    long* pred_idx_out /* or NULL */, long* gt_idx_out /* or NULL */);
 
 /* Visualisation panels composed on the device: replaces save_depth_normal_maps / colorize / colorize_np (utils/vis_utils.py:38-84,139-199, as
  * eval.py:58-62 calls them under `vis_depth: True`).  One image per frame, uint8 [T,H,Wp,3] row-major,

@@ -114,10 +114,14 @@ int ug_op_masked_median(ug_ctx* ctx, const float* pred, const float* gt, long n,
  *                          -0.0 sorts below +0.0; no NaN
  *   ug_op_pcd_knn_normals: per point of a float64 cloud [n,3] the min(knn, n) nearest points, itself included, ordered by (squared distance,
  *                          index) -> nbr_out [n, min(knn, n)] (may be NULL), and the unit eigenvector of the smallest eigenvalue of their float64
- *                          covariance -> normals_out [n,3]; (0, 0, 1) for n < 3 */
+ *                          covariance -> normals_out [n,3]; (0, 0, 1) for n < 3
+ *   ug_op_pcd_fps        : farthest-point sampling of a float32 cloud [n,3] alone -> idx_out [k] in pick order and
+ *                          sel_dist_out [k] = the squared distance to the points picked before (+inf for the first; -1 for a non-finite point, picked
+ *                          only when no finite one exists); 1 <= k <= n < 2^31, else an error that leaves the context usable */
 int ug_op_pcd_nn(ug_ctx* ctx, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out);
 int ug_op_pcd_select(ug_ctx* ctx, const void* values, int is_f64, long n, long k, void* out);
 int ug_op_pcd_knn_normals(ug_ctx* ctx, const double* pts, long n, int knn, int* nbr_out, double* normals_out);
+int ug_op_pcd_fps(ug_ctx* ctx, const float* pts, long n, long k, long* idx_out, float* sel_dist_out);
 /* Tuning aids (not on the product path): GEMM / implicit-conv microbenchmark on device-resident random data,
  * and an override of the tile/split-K heuristic (-1 = heuristic). ms_out: [ms per launch, cfg, split, M, K]. */
 /* GroupNorm launch-scheme A/B (mode: launch_groupnorm in kernels/norm.hip); tuning aid, no reference counterpart. */

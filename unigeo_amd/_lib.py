@@ -24,7 +24,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
-    "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals",
+    "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
@@ -132,6 +132,8 @@ def load_library():
                         "ug_op_pcd_nn": [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp],
                         "ug_op_pcd_select": [vp, vp, ip, C.c_long, C.c_long, vp],
                         "ug_op_pcd_knn_normals": [vp, vp, C.c_long, ip, vp, vp]})
+    _set_argtypes(lib, {"ug_eval_pcd_fps": [vp, vp, vp, vp, C.c_long, C.c_long, C.POINTER(PcdOptsC), vp, vp, vp, vp, vp],
+                        "ug_op_pcd_fps": [vp, vp, C.c_long, C.c_long, vp, vp]})
     _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
                         "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
     _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
@@ -608,14 +610,32 @@ class Engine:
         return pts, (float(fit[0]), float(fit[1]))
 
     def eval_pcd(self, pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30,
-                 return_clouds=True):
+                 return_clouds=True, sampling="random"):
         """``pcd_evaluation`` of ``harness/metrics.py`` on the device (``ug_eval_pcd``) -> the same dict.  ``pred_pts=None`` evaluates the
-        points that the last ``pcd_world_points`` left resident.  The sampled positions are drawn here, as the host mirror draws them."""
+        points that the last ``pcd_world_points`` left resident.  The sampled positions are drawn here, as the host mirror draws them;
+        ``sampling="fps"`` picks them on the device instead (``ug_eval_pcd_fps``) and adds ``pred_idx`` / ``gt_idx``."""
         from .harness.metrics import pcd_sample_indices
+        if sampling not in ("random", "fps"):
+            raise ValueError(f"eval_pcd: sampling must be 'random' or 'fps', not {sampling!r}")
         g = _f32(gt_pts).reshape(-1, 3)
         m = np.ascontiguousarray((np.asarray(masks).reshape(-1) > 0).astype(np.uint8))
         p = None if pred_pts is None else _f32(pred_pts).reshape(-1, 3)
         n_mask = int(m.sum())
+        if sampling == "fps":
+            ns = downsample_num if 0 < downsample_num < n_mask else n_mask
+            o = PcdOptsC(float(threshold), int(max_iteration), int(knn))
+            out = np.zeros(32, np.float64)
+            pc = np.empty((ns, 3), np.float32) if return_clouds else None
+            gc = np.empty((ns, 3), np.float32) if return_clouds else None
+            ip, ig = np.empty(ns, np.int64), np.empty(ns, np.int64)
+            self._ck(self.lib.ug_eval_pcd_fps(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, int(downsample_num), C.byref(o), _ptr(out), _ptr(pc),
+                                              _ptr(gc), _ptr(ip), _ptr(ig)))
+            res = self._pcd_result(out)
+            res.update(pred_idx=ip, gt_idx=ig)
+            if return_clouds:
+                col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[m > 0]
+                res.update(pred_pcd=(pc, col[ip]), gt_pcd=(gc, col[ig]))
+            return res
         idx = pcd_sample_indices(n_mask, downsample_num, seed)
         idx = None if idx is None else np.ascontiguousarray(idx.astype(np.int64))
         ns = n_mask if idx is None else len(idx)
@@ -625,16 +645,29 @@ class Engine:
         gc = np.empty((ns, 3), np.float32) if return_clouds else None
         self._ck(self.lib.ug_eval_pcd(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
                                       _ptr(out), _ptr(pc), _ptr(gc)))
-        res = dict(zip(self.PCD_KEYS, out[:8].tolist()))
-        res.update(n_points=int(out[8]), icp_iterations=int(out[9]), icp_fitness=float(out[10]), icp_rmse=float(out[11]),
-                   transformation=out[12:28].reshape(4, 4).copy(), pred_scale=float(out[28]), gt_scale=float(out[29]),
-                   pred_shift_z=float(out[30]), gt_shift_z=float(out[31]))
+        res = self._pcd_result(out)
         if return_clouds:
             keep = m > 0
             col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[keep]
             col = col if idx is None else col[idx]
             res.update(pred_pcd=(pc, col), gt_pcd=(gc, col.copy()))
         return res
+
+    def _pcd_result(self, out):
+        res = dict(zip(self.PCD_KEYS, out[:8].tolist()))
+        res.update(n_points=int(out[8]), icp_iterations=int(out[9]), icp_fitness=float(out[10]), icp_rmse=float(out[11]),
+                   transformation=out[12:28].reshape(4, 4).copy(), pred_scale=float(out[28]), gt_scale=float(out[29]),
+                   pred_shift_z=float(out[30]), gt_shift_z=float(out[31]))
+        return res
+
+    def op_pcd_fps(self, pts, k):
+        """Farthest-point sampling of a float32 cloud ``[n,3]`` alone (``pcd_fps_indices`` of ``harness/metrics.py``) ->
+        ``(idx int64 [k], sel_dist float32 [k])``."""
+        p = _f32(pts).reshape(-1, 3)
+        k = int(k)
+        idx, sel = np.empty(max(k, 0), np.int64), np.empty(max(k, 0), np.float32)
+        self._ck(self.lib.ug_op_pcd_fps(self.ctx, _ptr(p), len(p), k, _ptr(idx), _ptr(sel)))
+        return idx, sel
 
     def op_pcd_nn(self, query, target, transformation=None):
         """Nearest target of every query (float64 ``[n,3]``; the query first moved by the 4x4) -> ``(distance float64, index int32)``."""

@@ -298,6 +298,142 @@ static void pcd_mean_median(Ctx& c, const double* v, long n, unsigned* sel, unsi
   med = (pcd_unkey_f64(k[0]) + pcd_unkey_f64(k[1])) / 2.0;
 }
 
+// ug_eval_pcd and ug_eval_pcd_fps: one pipeline.  `fps` replaces the index list by farthest-point sampling of each aligned cloud.
+static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, const unsigned char* mask, long n, const long* sample_idx, long n_sample,
+                         bool fps, const ug_pcd_opts* o, double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out,
+                         long* gt_idx_out) {
+  UG_REQUIRE(o && gt_pts && mask && out, "options, gt_pts, mask and out32 must not be NULL");
+  UG_REQUIRE(n > 0 && n < (1L << 31), "n_pixels must be positive and below 2^31");
+  UG_REQUIRE(o->knn >= 1 && o->knn <= UG_PCD_MAX_KNN, "knn must be 1..UG_PCD_MAX_KNN");
+  UG_REQUIRE(o->threshold > 0.f && o->max_iteration >= 0, "threshold must be positive and max_iteration not negative");
+  UG_REQUIRE(pred_pts || (c.d_pcd_pts && c.pcd_pixels == n), "no resident world points of that size (ug_pcd_world_points first)");
+  UG_REQUIRE(!sample_idx || n_sample > 0, "n_sample must be positive when sample_idx is given");
+  const float* dp = c.d_pcd_pts;
+  if (pred_pts) { float* d = c.ws.get<float>(n * 3); UG_CHECK(hipMemcpy(d, pred_pts, (size_t)n * 12, hipMemcpyHostToDevice)); dp = d; }
+  float* dg = c.ws.get<float>(n * 3); UG_CHECK(hipMemcpy(dg, gt_pts, (size_t)n * 12, hipMemcpyHostToDevice));
+  unsigned char* dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(dm, mask, n, hipMemcpyHostToDevice));
+  unsigned* counts = (unsigned*)c.ws.alloc((PCD_MAXB + 1) * 4);
+  float* P = c.ws.get<float>(n * 3); float* G = c.ws.get<float>(n * 3);
+  launch_pcd_compact(dp, dg, dm, n, counts, P, G, c.stream);
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  unsigned m32 = 0;
+  UG_CHECK(hipMemcpy(&m32, counts + PCD_MAXB, 4, hipMemcpyDeviceToHost));
+  const long m = m32;
+  for (int k = 0; k < 32; ++k) out[k] = NAN;
+  out[8] = 0; out[9] = 0; out[10] = 0; out[11] = 0;
+  double Tm[16];
+  for (int i = 0; i < 16; ++i) Tm[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  memcpy(out + 12, Tm, sizeof(Tm));
+  if (m == 0) return;      // empty mask: NaN metrics, like the mean over an empty selection
+  const bool sample = fps && n_sample > 0 && n_sample < m;      // otherwise farthest-point sampling takes every point: no sampling at all
+  const long ns = (sample_idx || sample) ? n_sample : m;
+  if (sample_idx) for (long j = 0; j < ns; ++j) UG_REQUIRE(sample_idx[j] >= 0 && sample_idx[j] < m, "a sample index lies outside the masked points");
+  UG_REQUIRE((double)ns * (double)ns <= 1099511627776.0,
+             "more than 2^40 point pairs in one nearest-neighbour pass: lower pcd_downsample_num");
+
+  // alignment: median shifts along z, then per cloud the median centre and the median distance from it (all exact selections)
+  unsigned* sel = (unsigned*)c.ws.alloc(PCD_SEL_WORDS * 4);
+  unsigned long long* res = c.ws.get<unsigned long long>(16);
+  const unsigned long long kmed = (unsigned long long)((m - 1) / 2);
+  launch_pcd_select(P, 0, m, 3, 2, kmed, sel, res, 0, c.stream);
+  launch_pcd_select(G, 0, m, 3, 2, kmed, sel, res, 1, c.stream);
+  launch_pcd_shift_z(P, G, m, res, 0, 1, c.stream);
+  float* norm = c.ws.get<float>(m);
+  for (int a = 0; a < 2; ++a) {
+    const float* X = a ? G : P;
+    for (int k = 0; k < 3; ++k) launch_pcd_select(X, 0, m, 3, k, kmed, sel, res, 2 + a * 3 + k, c.stream);
+    launch_pcd_center_norm(X, m, res, 2 + a * 3, norm, c.stream);
+    launch_pcd_select(norm, 0, m, 1, 0, kmed, sel, res, 8 + a, c.stream);
+  }
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  unsigned long long hres[10];
+  UG_CHECK(hipMemcpy(hres, res, sizeof(hres), hipMemcpyDeviceToHost));
+  const float pz = pcd_unkey_f32(hres[0]), gz = pcd_unkey_f32(hres[1]), gs = pcd_unkey_f32(hres[9]);
+  const float ps = std::min(std::max(pcd_unkey_f32(hres[8]), 1e-3f), 1e3f);
+  const float ratio = gs / ps;
+  out[28] = ps; out[29] = gs; out[30] = pz; out[31] = gz; out[8] = (double)ns;
+
+  long* didx = nullptr;
+  if (sample_idx) { didx = c.ws.get<long>(ns); UG_CHECK(hipMemcpy(didx, sample_idx, (size_t)ns * sizeof(long), hipMemcpyHostToDevice)); }
+  float* p32 = c.ws.get<float>(ns * 3); float* g32 = c.ws.get<float>(ns * 3);
+  double* p64 = c.ws.get<double>(ns * 3); double* g64 = c.ws.get<double>(ns * 3);
+  long* fidx[2] = {nullptr, nullptr};
+  if (sample) {      // align every masked point in place (each thread reads its own point before it writes it), then pick from each cloud on its own
+    launch_pcd_align(P, G, nullptr, m, ratio, gz, P, G, nullptr, nullptr, c.stream);
+    float* fm = c.ws.get<float>(m); float* fpm = c.ws.get<float>(2 * PCD_MAXB); int* fpi = c.ws.get<int>(2 * PCD_MAXB);
+    float* fsel = c.ws.get<float>(ns);
+    for (int a = 0; a < 2; ++a) {
+      fidx[a] = c.ws.get<long>(ns);
+      launch_pcd_fps(a ? G : P, m, ns, fm, fpm, fpi, fidx[a], fsel, c.stream);
+      launch_pcd_gather(a ? G : P, fidx[a], ns, a ? g32 : p32, a ? g64 : p64, c.stream);
+    }
+  } else launch_pcd_align(P, G, didx, ns, ratio, gz, p32, g32, p64, g64, c.stream);
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  long* const idx_out[2] = {pred_idx_out, gt_idx_out};
+  for (int a = 0; a < 2; ++a) {
+    if (!idx_out[a]) continue;
+    if (sample) UG_CHECK(hipMemcpy(idx_out[a], fidx[a], (size_t)ns * sizeof(long), hipMemcpyDeviceToHost));
+    else for (long j = 0; j < ns; ++j) idx_out[a][j] = sample_idx ? sample_idx[j] : j;
+  }
+  if (pred_cloud_out) UG_CHECK(hipMemcpy(pred_cloud_out, p32, (size_t)ns * 12, hipMemcpyDeviceToHost));
+  if (gt_cloud_out) UG_CHECK(hipMemcpy(gt_cloud_out, g32, (size_t)ns * 12, hipMemcpyDeviceToHost));
+
+  // point-to-point ICP from the identity: the pair search and the Kabsch sums on the device, the 3x3 SVD here
+  const int ny = pcd_nn_slices(ns, ns);
+  int* idx = c.ws.get<int>(ns); double* dist = c.ws.get<double>(ns);
+  int* pidx = c.ws.get<int>((long)ny * ns); double* pdist = c.ws.get<double>((long)ny * ns);
+  double* dT = c.ws.get<double>(16);
+  double* part = c.ws.get<double>(PCD_MAXB * 17);
+  double sums[17];
+  const double thr = (double)o->threshold;
+  auto evaluate = [&](double& fit, double& rmse) {      // the stream is idle whenever dT is rewritten: every evaluation ends with a fetch
+    UG_CHECK(hipMemcpy(dT, Tm, sizeof(Tm), hipMemcpyHostToDevice));
+    int nb = 0;
+    launch_pcd_nn(p64, ns, g64, ns, dT, idx, dist, pidx, pdist, c.stream);
+    launch_pcd_kabsch(p64, g64, ns, dT, idx, dist, thr, part, &nb, c.stream);
+    UG_CHECK(hipGetLastError());
+    fetch_partial_sums(c, part, nb, sums);
+    fit = sums[0] / (double)ns;
+    rmse = sums[0] > 0 ? sqrt(sums[16] / sums[0]) : 0.0;
+  };
+  double fit = 0, rmse = 0;
+  evaluate(fit, rmse);
+  int it = 0;
+  while (it < o->max_iteration) {
+    double U[16], Tn[16];
+    pcd_host::umeyama_from_sums(sums, U);
+    pcd_host::mul44(U, Tm, Tn);
+    memcpy(Tm, Tn, sizeof(Tm));
+    const double pf = fit, pr = rmse;
+    evaluate(fit, rmse);
+    ++it;
+    if (fabs(pf - fit) < 1e-6 && fabs(pr - rmse) < 1e-6) break;
+  }
+  out[9] = it; out[10] = fit; out[11] = rmse;
+  memcpy(out + 12, Tm, sizeof(Tm));
+
+  // the moved prediction, normals of both clouds, nearest neighbours both ways, scores
+  double* moved = c.ws.get<double>(ns * 3);
+  double* nP = c.ws.get<double>(ns * 3); double* nG = c.ws.get<double>(ns * 3);
+  int* idx2 = c.ws.get<int>(ns); double* dist2 = c.ws.get<double>(ns);
+  double* dot1 = c.ws.get<double>(ns); double* dot2 = c.ws.get<double>(ns);
+  launch_pcd_move(p64, ns, dT, moved, c.stream);      // dT holds the final transformation: the last evaluation uploaded it
+  launch_pcd_knn_normals(moved, ns, o->knn, nullptr, nP, c.stream);
+  launch_pcd_knn_normals(g64, ns, o->knn, nullptr, nG, c.stream);
+  launch_pcd_nn(moved, ns, g64, ns, nullptr, idx, dist, pidx, pdist, c.stream);       // accuracy: prediction -> ground truth
+  launch_pcd_normal_dot(nP, nG, idx, ns, dot1, c.stream);
+  launch_pcd_nn(g64, ns, moved, ns, nullptr, idx2, dist2, pidx, pdist, c.stream);     // completion: ground truth -> prediction
+  launch_pcd_normal_dot(nG, nP, idx2, ns, dot2, c.stream);
+  UG_CHECK(hipGetLastError());
+  pcd_mean_median(c, dist, ns, sel, res, part, out[0], out[4]);
+  pcd_mean_median(c, dist2, ns, sel, res, part, out[1], out[5]);
+  pcd_mean_median(c, dot1, ns, sel, res, part, out[2], out[6]);
+  pcd_mean_median(c, dot2, ns, sel, res, part, out[3], out[7]);
+}
+
 // ---------------------------------------------------------------- clip preparation helpers (ug_prep_*)
 static const size_t PREP_CHUNK_BYTES = (size_t)96 << 20;      // device bytes one chunk of frames may take: the workspace does not grow with T
 static int prep_chunk_frames(int T, size_t per_frame) {
@@ -448,119 +584,15 @@ int ug_eval_pcd(ug_ctx* x, const float* pred_pts, const float* gt_pts, const uns
                 const ug_pcd_opts* o, double* out, float* pred_cloud_out, float* gt_cloud_out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
-    UG_REQUIRE(o && gt_pts && mask && out, "options, gt_pts, mask and out32 must not be NULL");
-    UG_REQUIRE(n > 0 && n < (1L << 31), "n_pixels must be positive and below 2^31");
-    UG_REQUIRE(o->knn >= 1 && o->knn <= UG_PCD_MAX_KNN, "knn must be 1..UG_PCD_MAX_KNN");
-    UG_REQUIRE(o->threshold > 0.f && o->max_iteration >= 0, "threshold must be positive and max_iteration not negative");
-    UG_REQUIRE(pred_pts || (c.d_pcd_pts && c.pcd_pixels == n), "no resident world points of that size (ug_pcd_world_points first)");
-    UG_REQUIRE(!sample_idx || n_sample > 0, "n_sample must be positive when sample_idx is given");
-    const float* dp = c.d_pcd_pts;
-    if (pred_pts) { float* d = c.ws.get<float>(n * 3); UG_CHECK(hipMemcpy(d, pred_pts, (size_t)n * 12, hipMemcpyHostToDevice)); dp = d; }
-    float* dg = c.ws.get<float>(n * 3); UG_CHECK(hipMemcpy(dg, gt_pts, (size_t)n * 12, hipMemcpyHostToDevice));
-    unsigned char* dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(dm, mask, n, hipMemcpyHostToDevice));
-    unsigned* counts = (unsigned*)c.ws.alloc((PCD_MAXB + 1) * 4);
-    float* P = c.ws.get<float>(n * 3); float* G = c.ws.get<float>(n * 3);
-    launch_pcd_compact(dp, dg, dm, n, counts, P, G, c.stream);
-    UG_CHECK(hipGetLastError());
-    UG_CHECK(hipStreamSynchronize(c.stream));
-    unsigned m32 = 0;
-    UG_CHECK(hipMemcpy(&m32, counts + PCD_MAXB, 4, hipMemcpyDeviceToHost));
-    const long m = m32;
-    for (int k = 0; k < 32; ++k) out[k] = NAN;
-    out[8] = 0; out[9] = 0; out[10] = 0; out[11] = 0;
-    double Tm[16];
-    for (int i = 0; i < 16; ++i) Tm[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    memcpy(out + 12, Tm, sizeof(Tm));
-    if (m == 0) return 0;      // empty mask: NaN metrics, like the mean over an empty selection
-    const long ns = sample_idx ? n_sample : m;
-    if (sample_idx) for (long j = 0; j < ns; ++j) UG_REQUIRE(sample_idx[j] >= 0 && sample_idx[j] < m, "a sample index lies outside the masked points");
-    UG_REQUIRE((double)ns * (double)ns <= 1099511627776.0,
-               "more than 2^40 point pairs in one nearest-neighbour pass: lower pcd_downsample_num");
+    eval_pcd_run(c, pred_pts, gt_pts, mask, n, sample_idx, n_sample, false, o, out, pred_cloud_out, gt_cloud_out, nullptr, nullptr);
+  });
+}
 
-    // alignment: median shifts along z, then per cloud the median centre and the median distance from it (all exact selections)
-    unsigned* sel = (unsigned*)c.ws.alloc(PCD_SEL_WORDS * 4);
-    unsigned long long* res = c.ws.get<unsigned long long>(16);
-    const unsigned long long kmed = (unsigned long long)((m - 1) / 2);
-    launch_pcd_select(P, 0, m, 3, 2, kmed, sel, res, 0, c.stream);
-    launch_pcd_select(G, 0, m, 3, 2, kmed, sel, res, 1, c.stream);
-    launch_pcd_shift_z(P, G, m, res, 0, 1, c.stream);
-    float* norm = c.ws.get<float>(m);
-    for (int a = 0; a < 2; ++a) {
-      const float* X = a ? G : P;
-      for (int k = 0; k < 3; ++k) launch_pcd_select(X, 0, m, 3, k, kmed, sel, res, 2 + a * 3 + k, c.stream);
-      launch_pcd_center_norm(X, m, res, 2 + a * 3, norm, c.stream);
-      launch_pcd_select(norm, 0, m, 1, 0, kmed, sel, res, 8 + a, c.stream);
-    }
-    UG_CHECK(hipGetLastError());
-    UG_CHECK(hipStreamSynchronize(c.stream));
-    unsigned long long hres[10];
-    UG_CHECK(hipMemcpy(hres, res, sizeof(hres), hipMemcpyDeviceToHost));
-    const float pz = pcd_unkey_f32(hres[0]), gz = pcd_unkey_f32(hres[1]), gs = pcd_unkey_f32(hres[9]);
-    const float ps = std::min(std::max(pcd_unkey_f32(hres[8]), 1e-3f), 1e3f);
-    const float ratio = gs / ps;
-    out[28] = ps; out[29] = gs; out[30] = pz; out[31] = gz; out[8] = (double)ns;
-
-    long* didx = nullptr;
-    if (sample_idx) { didx = c.ws.get<long>(ns); UG_CHECK(hipMemcpy(didx, sample_idx, (size_t)ns * sizeof(long), hipMemcpyHostToDevice)); }
-    float* p32 = c.ws.get<float>(ns * 3); float* g32 = c.ws.get<float>(ns * 3);
-    double* p64 = c.ws.get<double>(ns * 3); double* g64 = c.ws.get<double>(ns * 3);
-    launch_pcd_align(P, G, didx, ns, ratio, gz, p32, g32, p64, g64, c.stream);
-    UG_CHECK(hipGetLastError());
-    UG_CHECK(hipStreamSynchronize(c.stream));
-    if (pred_cloud_out) UG_CHECK(hipMemcpy(pred_cloud_out, p32, (size_t)ns * 12, hipMemcpyDeviceToHost));
-    if (gt_cloud_out) UG_CHECK(hipMemcpy(gt_cloud_out, g32, (size_t)ns * 12, hipMemcpyDeviceToHost));
-
-    // point-to-point ICP from the identity: the pair search and the Kabsch sums on the device, the 3x3 SVD here
-    const int ny = pcd_nn_slices(ns, ns);
-    int* idx = c.ws.get<int>(ns); double* dist = c.ws.get<double>(ns);
-    int* pidx = c.ws.get<int>((long)ny * ns); double* pdist = c.ws.get<double>((long)ny * ns);
-    double* dT = c.ws.get<double>(16);
-    double* part = c.ws.get<double>(PCD_MAXB * 17);
-    double sums[17];
-    const double thr = (double)o->threshold;
-    auto evaluate = [&](double& fit, double& rmse) {      // the stream is idle whenever dT is rewritten: every evaluation ends with a fetch
-      UG_CHECK(hipMemcpy(dT, Tm, sizeof(Tm), hipMemcpyHostToDevice));
-      int nb = 0;
-      launch_pcd_nn(p64, ns, g64, ns, dT, idx, dist, pidx, pdist, c.stream);
-      launch_pcd_kabsch(p64, g64, ns, dT, idx, dist, thr, part, &nb, c.stream);
-      UG_CHECK(hipGetLastError());
-      fetch_partial_sums(c, part, nb, sums);
-      fit = sums[0] / (double)ns;
-      rmse = sums[0] > 0 ? sqrt(sums[16] / sums[0]) : 0.0;
-    };
-    double fit = 0, rmse = 0;
-    evaluate(fit, rmse);
-    int it = 0;
-    while (it < o->max_iteration) {
-      double U[16], Tn[16];
-      pcd_host::umeyama_from_sums(sums, U);
-      pcd_host::mul44(U, Tm, Tn);
-      memcpy(Tm, Tn, sizeof(Tm));
-      const double pf = fit, pr = rmse;
-      evaluate(fit, rmse);
-      ++it;
-      if (fabs(pf - fit) < 1e-6 && fabs(pr - rmse) < 1e-6) break;
-    }
-    out[9] = it; out[10] = fit; out[11] = rmse;
-    memcpy(out + 12, Tm, sizeof(Tm));
-
-    // the moved prediction, normals of both clouds, nearest neighbours both ways, scores
-    double* moved = c.ws.get<double>(ns * 3);
-    double* nP = c.ws.get<double>(ns * 3); double* nG = c.ws.get<double>(ns * 3);
-    int* idx2 = c.ws.get<int>(ns); double* dist2 = c.ws.get<double>(ns);
-    double* dot1 = c.ws.get<double>(ns); double* dot2 = c.ws.get<double>(ns);
-    launch_pcd_move(p64, ns, dT, moved, c.stream);      // dT holds the final transformation: the last evaluation uploaded it
-    launch_pcd_knn_normals(moved, ns, o->knn, nullptr, nP, c.stream);
-    launch_pcd_knn_normals(g64, ns, o->knn, nullptr, nG, c.stream);
-    launch_pcd_nn(moved, ns, g64, ns, nullptr, idx, dist, pidx, pdist, c.stream);       // accuracy: prediction -> ground truth
-    launch_pcd_normal_dot(nP, nG, idx, ns, dot1, c.stream);
-    launch_pcd_nn(g64, ns, moved, ns, nullptr, idx2, dist2, pidx, pdist, c.stream);     // completion: ground truth -> prediction
-    launch_pcd_normal_dot(nG, nP, idx2, ns, dot2, c.stream);
-    UG_CHECK(hipGetLastError());
-    pcd_mean_median(c, dist, ns, sel, res, part, out[0], out[4]);
-    pcd_mean_median(c, dist2, ns, sel, res, part, out[1], out[5]);
-    pcd_mean_median(c, dot1, ns, sel, res, part, out[2], out[6]);
-    pcd_mean_median(c, dot2, ns, sel, res, part, out[3], out[7]);
+int ug_eval_pcd_fps(ug_ctx* x, const float* pred_pts, const float* gt_pts, const unsigned char* mask, long n, long n_sample, const ug_pcd_opts* o,
+                    double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out, long* gt_idx_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    eval_pcd_run(c, pred_pts, gt_pts, mask, n, nullptr, n_sample, true, o, out, pred_cloud_out, gt_cloud_out, pred_idx_out, gt_idx_out);
   });
 }
 

@@ -316,6 +316,23 @@ int ug_op_pcd_knn_normals(ug_ctx* x, const double* pts, long n, int knn, int* nb
     UG_CHECK(hipMemcpy(normals_out, nrm, (size_t)n * 24, hipMemcpyDeviceToHost));
   });
 }
+// farthest-point sampling alone
+int ug_op_pcd_fps(ug_ctx* x, const float* pts, long n, long k, long* idx_out, float* sel_dist_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pts && idx_out && sel_dist_out, "pts, idx_out and sel_dist_out must not be NULL");
+    UG_REQUIRE(n >= 1 && n < (1L << 31), "n must be 1 .. 2^31 - 1");
+    UG_REQUIRE(k >= 1 && k <= n, "k must be 1 .. n");
+    float* dp = c.ws.get<float>(n * 3); UG_CHECK(hipMemcpy(dp, pts, (size_t)n * 12, hipMemcpyHostToDevice));
+    float* m = c.ws.get<float>(n); float* pm = c.ws.get<float>(2 * PCD_MAXB); int* pi = c.ws.get<int>(2 * PCD_MAXB);
+    long* idx = c.ws.get<long>(k); float* sel = c.ws.get<float>(k);
+    launch_pcd_fps(dp, n, k, m, pm, pi, idx, sel, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(idx_out, idx, (size_t)k * sizeof(long), hipMemcpyDeviceToHost));
+    UG_CHECK(hipMemcpy(sel_dist_out, sel, (size_t)k * 4, hipMemcpyDeviceToHost));
+  });
+}
 
 int ug_op_linear(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, const float* R1,
                  float c0, float c1, int act, int geglu, float* out) {

@@ -328,6 +328,11 @@ void launch_pcd_move(const double* q, long n, const double* T44, double* out, hi
 void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr /* [n][min(knn, n)] or NULL */, double* normals, hipStream_t s);
 void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s);
 void launch_pcd_sum(const double* v, long n, double* part /*[PCD_MAXB]*/, int* nb, hipStream_t s);
+// farthest-point sampling: k picks of a float32 cloud [n,3], 1 <= k <= n < 2^31, in k + 1 stream-ordered launches.
+// Scratch: m [n] the running smallest squared distance, pm / pi [2 * PCD_MAXB] the per-workgroup (best m, lowest index) of the even and odd launches.
+void launch_pcd_fps(const float* p, long n, long k, float* m, float* pm, int* pi, long* idx /*[k]*/, float* sel_dist /*[k]*/, hipStream_t s);
+// out32[j] = src[idx[j]] and its float64 copy (either output may be NULL)
+void launch_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64, hipStream_t s);
 // depth / normal visualisation panels (kernels/vis.hip); part: 2 * 1024 floats of scratch, out2 (device) = (vmin, vmax)
 void launch_vis_range(const float* x, long n, float* part, float* out2, hipStream_t s);
 void launch_vis_panel(const float* rgb, const float* normals, const float* depth, const float* lut, const float* cbar, unsigned char* out, int T,

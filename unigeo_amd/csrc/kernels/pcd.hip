@@ -1,6 +1,7 @@
 // Point-cloud evaluation on the device - what the reference hands to Open3D and a CPU k-d tree:
 //   /root/reference/metrics/eval_pcd.py:10-168 (masked selection, alignment, downsampling, ICP, normals, scores),
-//   metrics/pcd_alignment.py (Regr3D_t_ScaleShiftInv: median shifts and median scales), metrics/utils.py:14-42 (accuracy / completion).
+//   metrics/pcd_alignment.py (Regr3D_t_ScaleShiftInv: median shifts and median scales), metrics/utils.py:14-42 (accuracy / completion),
+//   and the farthest-point sampling of its disabled branch (eval_pcd.py:84-93,172-193), in unfused fp32.
 // Brute-force pair arithmetic in unfused fp64 (fp contract off), the arithmetic of the numpy mirror in harness/metrics.py.  Every kernel is
 // deterministic: reductions are two-stage in a fixed order, target slices are combined in slice order, the only atomics are integer
 // histogram counts.  No float atomics, no cooperative launch, no inline assembly.
@@ -135,7 +136,8 @@ __global__ __launch_bounds__(PB) void k_pcd_center_norm(const float* p, long n, 
     norm[i] = (float)__dsqrt_rn((dx * dx + dy * dy) + dz * dz);
   }
 }
-// gather the sampled points (idx NULL: all), pred *= gt_scale / pred_scale, both z += gt_shift_z; float32 clouds and their fp64 copies
+// gather the sampled points (idx NULL: all), pred *= gt_scale / pred_scale, both z += gt_shift_z; float32 clouds and their fp64 copies (p64 and
+// g64 both NULL: none)
 __global__ __launch_bounds__(PB) void k_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32,
                                                   float* g32, double* p64, double* g64) {
   for (long j = (long)blockIdx.x * PB + threadIdx.x; j < ns; j += (long)gridDim.x * PB) {
@@ -144,6 +146,7 @@ __global__ __launch_bounds__(PB) void k_pcd_align(const float* p, const float* g
     const float gx = g[i * 3], gy = g[i * 3 + 1], gzz = g[i * 3 + 2] + gz;
     p32[j * 3] = px; p32[j * 3 + 1] = py; p32[j * 3 + 2] = pz;
     g32[j * 3] = gx; g32[j * 3 + 1] = gy; g32[j * 3 + 2] = gzz;
+    if (!p64) continue;      // farthest-point sampling aligns every masked point and widens only what it picks
     p64[j * 3] = px; p64[j * 3 + 1] = py; p64[j * 3 + 2] = pz;
     g64[j * 3] = gx; g64[j * 3 + 1] = gy; g64[j * 3 + 2] = gzz;
   }
@@ -333,6 +336,78 @@ __global__ __launch_bounds__(KNN_B) void k_pcd_knn(const double* pts, long n, in
   normals[i * 3] = nx; normals[i * 3 + 1] = ny; normals[i * 3 + 2] = nz;
 }
 
+// ------------------------------------------------------------------------------------------------------------- farthest-point sampling
+// DESIGN.md section 19, the arithmetic of pcd_fps_indices in harness/metrics.py.  m[j] is the smallest squared distance of point j to the points
+// picked so far (+inf before the first pick, -1 for a non-finite point); every pick is the largest m, ties to the lowest index.  One launch per
+// pick: launch L (L >= 1) first reduces the (best m, lowest index) pairs that the workgroups of launch L - 1 left - every workgroup on its own, in
+// the same order, so all agree on the pick s - then lowers m by the distance to p[s] over its grid-stride share and leaves its own pair.  Launch 0
+// only initialises m.  The pairs are double-buffered by launch parity: launch L reads slot (L - 1) & 1 and writes slot L & 1, and the stream
+// orders the launches, so no workgroup reads a word that a workgroup of its own launch writes.
+__device__ __forceinline__ void fps_better(float& bm, int& bi, float m, int i) {
+  if (m > bm || (m == bm && i < bi)) { bm = m; bi = i; }
+}
+__device__ __forceinline__ void fps_block_best(float& bm, int& bi, float* sm, int* si) {
+  const int tid = threadIdx.x;
+  sm[tid] = bm; si[tid] = bi;
+  __syncthreads();
+  for (int o = PB / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      float m = sm[tid]; int i = si[tid];
+      fps_better(m, i, sm[tid + o], si[tid + o]);
+      sm[tid] = m; si[tid] = i;
+    }
+    __syncthreads();
+  }
+  bm = sm[0]; bi = si[0];
+  __syncthreads();
+}
+#define FPS_NONE_M (-2.f)          // below every m (m >= -1): a thread or slot without a point never wins
+#define FPS_NONE_I 0x7fffffff
+
+__global__ __launch_bounds__(PB) void k_pcd_fps(const float* p, long n, float* m, long launch, int nprev, int last, float* pm, int* pi, long* idx,
+                                                float* sel_dist) {
+  __shared__ float sm[PB];
+  __shared__ int si[PB];
+  const int tid = threadIdx.x;
+  const float* pm_in = pm + ((launch & 1) ^ 1) * PCD_MAXB; const int* pi_in = pi + ((launch & 1) ^ 1) * PCD_MAXB;
+  float* pm_out = pm + (launch & 1) * PCD_MAXB; int* pi_out = pi + (launch & 1) * PCD_MAXB;
+  float bm = FPS_NONE_M; int bi = FPS_NONE_I;
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  if (launch > 0) {
+    for (int b = tid; b < nprev; b += PB) fps_better(bm, bi, pm_in[b], pi_in[b]);
+    fps_block_best(bm, bi, sm, si);
+    if (blockIdx.x == 0 && tid == 0) { idx[launch - 1] = bi; sel_dist[launch - 1] = bm; }
+    if (last) return;
+    sx = p[(long)bi * 3]; sy = p[(long)bi * 3 + 1]; sz = p[(long)bi * 3 + 2];
+    bm = FPS_NONE_M; bi = FPS_NONE_I;
+  }
+  for (long j = (long)blockIdx.x * PB + tid; j < n; j += (long)gridDim.x * PB) {      // ascending j: a strictly larger m keeps the lowest index
+    const float x = p[j * 3], y = p[j * 3 + 1], z = p[j * 3 + 2];
+    float mj;
+    if (launch == 0) {
+      mj = (isfinite(x) && isfinite(y) && isfinite(z)) ? INFINITY : -1.f;
+      m[j] = mj;
+    } else {
+      mj = m[j];
+      const float dx = x - sx, dy = y - sy, dz = z - sz;
+      const float d = (dx * dx + dy * dy) + dz * dz;
+      if (d < mj) { mj = d; m[j] = d; }      // a NaN d (a non-finite point) leaves m alone
+    }
+    if (mj > bm) { bm = mj; bi = (int)j; }
+  }
+  fps_block_best(bm, bi, sm, si);
+  if (tid == 0) { pm_out[blockIdx.x] = bm; pi_out[blockIdx.x] = bi; }
+}
+
+__global__ __launch_bounds__(PB) void k_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64) {
+  for (long j = (long)blockIdx.x * PB + threadIdx.x; j < ns; j += (long)gridDim.x * PB) {
+    const long i = idx[j];
+    const float x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+    if (out32) { out32[j * 3] = x; out32[j * 3 + 1] = y; out32[j * 3 + 2] = z; }
+    if (out64) { out64[j * 3] = x; out64[j * 3 + 1] = y; out64[j * 3 + 2] = z; }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------- launchers
 static int pcd_blocks(long n) { long b = (n + PB - 1) / PB; return (int)(b > PCD_MAXB ? PCD_MAXB : (b < 1 ? 1 : b)); }
 
@@ -403,6 +478,17 @@ void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr, double
 }
 void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s) {
   hipLaunchKernelGGL(k_pcd_normal_dot, dim3(pcd_blocks(n)), dim3(PB), 0, s, nq, nt, idx, n, dot);
+}
+// k picks in k + 1 plain launches: launch 0 initialises m, launch L writes pick L - 1; the last one has nothing left to update and is one workgroup
+void launch_pcd_fps(const float* p, long n, long k, float* m, float* pm, int* pi, long* idx, float* sel_dist, hipStream_t s) {
+  const int nb = pcd_blocks(n);
+  for (long L = 0; L <= k; ++L) {
+    const int last = L == k;
+    hipLaunchKernelGGL(k_pcd_fps, dim3(last ? 1 : nb), dim3(PB), 0, s, p, n, m, L, nb, last, pm, pi, idx, sel_dist);
+  }
+}
+void launch_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_gather, dim3(pcd_blocks(ns)), dim3(PB), 0, s, src, idx, ns, out32, out64);
 }
 void launch_pcd_sum(const double* v, long n, double* part, int* nb, hipStream_t s) {
   *nb = pcd_blocks(n);

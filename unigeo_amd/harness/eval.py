@@ -71,13 +71,18 @@ def parse_depth_coord(config):
 def parse_pcd_eval_config(config):
     """``eval_pcd`` (the reference's key, eval.py:66-83): ``pcd_downsample_num`` (default -1: every masked point), optional ``threshold``
     (ICP correspondence distance, default 0.1) and ``seed`` (default 0; a clip draws with ``seed + data index``) -> dict, or ``None`` without
-    the key.  ``vis_pcd`` without ``eval_pcd`` is a ``ValueError``."""
+    the key.  ``sampling`` is ``random`` (default: the seeded draw) or ``fps`` (farthest-point sampling; ``seed`` is not
+    used); anything else, and ``vis_pcd`` without ``eval_pcd``, is a ``ValueError``."""
     if "eval_pcd" not in config:
         if config.get("vis_pcd"):
             raise ValueError("vis_pcd needs eval_pcd: the point clouds it writes are the ones eval_pcd aligns")
         return None
     cfg = config["eval_pcd"] or {}
-    return {"downsample_num": int(cfg.get("pcd_downsample_num", -1)), "threshold": float(cfg.get("threshold", 0.1)), "seed": int(cfg.get("seed", 0))}
+    sampling = cfg.get("sampling", "random")
+    if sampling not in ("random", "fps"):
+        raise ValueError(f"eval_pcd.sampling must be 'random' or 'fps', not {sampling!r}")
+    return {"downsample_num": int(cfg.get("pcd_downsample_num", -1)), "threshold": float(cfg.get("threshold", 0.1)), "seed": int(cfg.get("seed", 0)),
+            "sampling": sampling}
 
 
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
@@ -102,7 +107,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     before the model runs on it.
     ``eval_pcd`` (eval.py:66-83) adds ``acc / comp / nc1 / nc2`` and their medians: the model's ``pred_world_pts`` when it
     returns them, else ``world_points_from_depth`` of its depth with ``eval_depth``'s ``max_depth`` and clips (on the resident depth under
-    ``device_metrics=True``), against ``gt_world_pts`` on ``gt_masks`` through ``pcd_evaluation`` / ``ug_eval_pcd``.  ``vis_pcd: True`` writes
+    ``device_metrics=True``), against ``gt_world_pts`` on ``gt_masks`` through ``pcd_evaluation`` / ``ug_eval_pcd``
+    (``sampling: fps``: farthest-point sampling of each cloud, ``ug_eval_pcd_fps``).  ``vis_pcd: True`` writes
     ``save_dir/pcd_{seq}/pred.ply`` and ``gt.ply`` (the aligned clouds before ICP).  ``vis_pcd`` without ``eval_pcd``, or a clip without
     ``intrinsics`` when the points have to come from the depth, raises ``ValueError`` before the first clip runs."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
@@ -152,7 +158,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
             else:
                 metric.update(normal_evaluation(output["pred_normals"], gt["gt_normals"], custom_mask=gt["gt_masks"]))
         if pcd_cfg is not None:
-            kw = {"threshold": pcd_cfg["threshold"], "downsample_num": pcd_cfg["downsample_num"], "seed": pcd_cfg["seed"] + data_idx}
+            kw = {"threshold": pcd_cfg["threshold"], "downsample_num": pcd_cfg["downsample_num"], "seed": pcd_cfg["seed"] + data_idx,
+                  "sampling": pcd_cfg["sampling"]}
             pts = output.get("pred_world_pts")
             if hasattr(pts, "detach"):
                 pts = pts.detach().cpu().numpy()

@@ -352,11 +352,51 @@ def pcd_sample_indices(n, downsample_num, seed):
     return None
 
 
-def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30):
+def pcd_fps_indices(pts, k):
+    """Farthest-point sampling of a float32 cloud ``[n,3]`` -> ``(idx int64 [k], sel_dist float32 [k])``, the statement
+    that ``k_pcd_fps`` follows operation by operation.  ``m[j]`` starts at ``+inf`` for a point with three finite coordinates, else ``-1``.
+    Step ``i``: ``s = argmax m`` (ties to the lowest index), ``idx[i] = s``, ``sel_dist[i] = m[s]``, then ``m[j] = d if d < m[j]`` with
+    ``d = (dx*dx + dy*dy) + dz*dz``, every operation one float32 rounding, never fused; a NaN ``d`` leaves ``m[j]`` alone, so a non-finite
+    point is never picked while a finite one remains.  Step 0 picks the first finite point.
+
+    UNPINNED: this restates ``pytorch3d.ops.sample_farthest_points`` (``random_start_point=False``: start at index 0; each next point the
+    argmax of the running minimum squared distance, first maximum on ties) from its documented behaviour; pytorch3d is not installed here, so
+    neither the start index nor the tie rule has been compared against it."""
+    f32 = np.float32
+    p = np.ascontiguousarray(np.asarray(pts, f32).reshape(-1, 3))
+    n, k = len(p), int(k)
+    if not 0 < k <= n:
+        raise ValueError(f"pcd_fps_indices: k must be 1 .. n ({k} of {n})")
+    x, y, z = p[:, 0].copy(), p[:, 1].copy(), p[:, 2].copy()
+    m = np.where(np.isfinite(x) & np.isfinite(y) & np.isfinite(z), f32(np.inf), f32(-1)).astype(f32)
+    idx, sel = np.empty(k, np.int64), np.empty(k, f32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for i in range(k):
+            s = int(np.argmax(m))          # the first of equal maxima
+            idx[i], sel[i] = s, m[s]
+            dx, dy, dz = x - x[s], y - y[s], z - z[s]
+            d = (dx * dx + dy * dy) + dz * dz
+            np.copyto(m, d, where=d < m)
+    return idx, sel
+
+
+def pcd_sample_indices_fps(p, g, downsample_num):
+    """Farthest-point sampling of each aligned cloud on its own, as the reference's disabled branch (``metrics/eval_pcd.py:92-93``) ->
+    ``(idx_pred, idx_gt)`` when ``0 < downsample_num < n``, else ``None`` (every point)."""
+    if 0 < downsample_num < len(p):
+        return pcd_fps_indices(p, downsample_num)[0], pcd_fps_indices(g, downsample_num)[0]
+    return None
+
+
+def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30, sampling="random"):
     """``pcd_evaluation`` of the reference (``metrics/eval_pcd.py:10-168``) -> dict: masked selection in pixel order,
     ``pcd_align``, seeded downsampling (the reference draws from the unseeded global generator and raises when ``downsample_num`` exceeds the
     point count; here that uses every point), point-to-point ICP from the identity, KNN normals, ``accuracy`` / ``completion``.
-    ``pred_pcd`` / ``gt_pcd`` are ``(points float32 [n,3], colours float32 [n,3])`` taken before ICP (zeros without ``rgbs``)."""
+    ``pred_pcd`` / ``gt_pcd`` are ``(points float32 [n,3], colours float32 [n,3])`` taken before ICP (zeros without ``rgbs``).
+    ``sampling="fps"`` ignores ``seed``, samples each aligned cloud with ``pcd_fps_indices`` and adds ``pred_idx`` /
+    ``gt_idx``, the picked positions among the masked points; each cloud then carries the colours of its own points."""
+    if sampling not in ("random", "fps"):
+        raise ValueError(f"pcd_evaluation: sampling must be 'random' or 'fps', not {sampling!r}")
     m = _np(masks).reshape(-1) > 0
     p = _np(pred_pts).astype(np.float32).reshape(-1, 3)[m]
     g = _np(gt_pts).astype(np.float32).reshape(-1, 3)[m]
@@ -364,6 +404,14 @@ def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample
     scal = (math.nan,) * 4
     if len(p):
         p, g, scal = pcd_align(p, g)
+    if sampling == "fps":
+        pair = pcd_sample_indices_fps(p, g, downsample_num)
+        ip, ig = pair if pair is not None else (np.arange(len(p), dtype=np.int64),) * 2
+        p, g, cp, cg = (p, g, col, col.copy()) if pair is None else (p[ip], g[ig], col[ip], col[ig])
+        res = pcd_metrics_from_clouds(p, g, threshold, knn, max_iteration)
+        res.update(n_points=len(p), pred_scale=float(scal[0]), gt_scale=float(scal[1]), pred_shift_z=float(scal[2]), gt_shift_z=float(scal[3]),
+                   pred_pcd=(p, cp), gt_pcd=(g, cg), pred_idx=ip, gt_idx=ig)
+        return res
     idx = pcd_sample_indices(len(p), downsample_num, seed)
     if idx is not None:
         p, g, col = p[idx], g[idx], col[idx]
