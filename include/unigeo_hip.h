@@ -247,6 +247,23 @@ int ug_eval_pcd(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, 
 int ug_eval_pcd_fps(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, const float* gt_pts, const unsigned char* mask, long n_pixels,
                     long n_sample, const ug_pcd_opts* opts, double* out32, float* pred_cloud_out /* or NULL */, float* gt_cloud_out /* or NULL */,
                     long* pred_idx_out /* or NULL */, long* gt_idx_out /* or NULL */);
+/* ug_eval_pcd_ex: both calls above behind one flag word, plus the choice of the search.
+ *   UG_PCD_FPS        : farthest-point sampling as ug_eval_pcd_fps (sample_idx must then be NULL); without it sample_idx / n_sample as ug_eval_pcd.
+ *   UG_PCD_SEARCH_GRID: every nearest-neighbour pass (ICP, accuracy, completion) and both KNN passes go through a uniform grid over the target
+ *                       cloud - one grid over the ground truth and one over the moved prediction, each built once.  The search is exact: a query
+ *                       that the grid cannot settle within a few rings of cells is finished by the brute-force kernels, so every output is
+ *                       bit-equal to the call without the flag.  The 2^40 pair cap then counts only those leftover queries times the target
+ *                       size, which is what lets an unsampled clip (pcd_downsample_num = -1) run.
+ *   ug_eval_pcd(...) is ug_eval_pcd_ex(..., 0, ...), ug_eval_pcd_fps(...) is ug_eval_pcd_ex(..., NULL, n_sample, ..., UG_PCD_FPS, ...).
+ *   search_stats (host, [8], may be NULL; zeros without the grid flag): queries settled by a grid and leftover queries, both summed over all
+ *   passes; cells and fullest cell of the ground-truth grid; cells and fullest cell of the moved-prediction grid; peak workspace bytes; 0.
+ *   Errors as above, and a flag bit other than the two named here (the context stays usable). */
+#define UG_PCD_FPS         1
+#define UG_PCD_SEARCH_GRID 2
+int ug_eval_pcd_ex(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, const float* gt_pts, const unsigned char* mask, long n_pixels,
+                   const long* sample_idx /* or NULL */, long n_sample, const ug_pcd_opts* opts, int flags, double* out32,
+                   float* pred_cloud_out /* or NULL */, float* gt_cloud_out /* or NULL */, long* pred_idx_out /* or NULL */,
+                   long* gt_idx_out /* or NULL */, long* search_stats /* [8] or NULL */);
 
 /* Visualisation panels composed on the device: replaces save_depth_normal_maps / colorize / colorize_np (utils/vis_utils.py:38-84,139-199, as
  * eval.py:58-62 calls them under `vis_depth: True`).  One image per frame, uint8 [T,H,Wp,3] row-major,

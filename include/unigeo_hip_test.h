@@ -122,6 +122,13 @@ int ug_op_pcd_nn(ug_ctx* ctx, const double* query, long nq, const double* target
 int ug_op_pcd_select(ug_ctx* ctx, const void* values, int is_f64, long n, long k, void* out);
 int ug_op_pcd_knn_normals(ug_ctx* ctx, const double* pts, long n, int knn, int* nbr_out, double* normals_out);
 int ug_op_pcd_fps(ug_ctx* ctx, const float* pts, long n, long k, long* idx_out, float* sel_dist_out);
+/* The same two searches through a uniform grid over the target cloud: arguments and outputs as ug_op_pcd_nn /
+ * ug_op_pcd_knn_normals, and the same bytes.  Queries the grid cannot settle within PCD_GRID_RINGS rings of cells (far from every target, a
+ * non-finite query, an empty grid) are finished by the brute-force kernels; the 2^40 pair cap counts those leftovers times the target size.
+ * stats (host, [4], may be NULL): queries settled by the grid, leftover queries, cells of the grid, points in its fullest cell. */
+int ug_op_pcd_nn_grid(ug_ctx* ctx, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out,
+                      long* stats /* [4] or NULL */);
+int ug_op_pcd_knn_normals_grid(ug_ctx* ctx, const double* pts, long n, int knn, int* nbr_out, double* normals_out, long* stats /* [4] or NULL */);
 /* Tuning aids (not on the product path): GEMM / implicit-conv microbenchmark on device-resident random data,
  * and an override of the tile/split-K heuristic (-1 = heuristic). ms_out: [ms per launch, cfg, split, M, K]. */
 /* GroupNorm launch-scheme A/B (mode: launch_groupnorm in kernels/norm.hip); tuning aid, no reference counterpart. */

@@ -25,6 +25,7 @@ EXPORTS = [
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
+    "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
@@ -134,6 +135,9 @@ def load_library():
                         "ug_op_pcd_knn_normals": [vp, vp, C.c_long, ip, vp, vp]})
     _set_argtypes(lib, {"ug_eval_pcd_fps": [vp, vp, vp, vp, C.c_long, C.c_long, C.POINTER(PcdOptsC), vp, vp, vp, vp, vp],
                         "ug_op_pcd_fps": [vp, vp, C.c_long, C.c_long, vp, vp]})
+    _set_argtypes(lib, {"ug_eval_pcd_ex": [vp, vp, vp, vp, C.c_long, vp, C.c_long, C.POINTER(PcdOptsC), ip, vp, vp, vp, vp, vp, vp],
+                        "ug_op_pcd_nn_grid": [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp, vp],
+                        "ug_op_pcd_knn_normals_grid": [vp, vp, C.c_long, ip, vp, vp, vp]})
     _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
                         "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
     _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
@@ -610,13 +614,19 @@ class Engine:
         return pts, (float(fit[0]), float(fit[1]))
 
     def eval_pcd(self, pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30,
-                 return_clouds=True, sampling="random"):
+                 return_clouds=True, sampling="random", search="brute"):
         """``pcd_evaluation`` of ``harness/metrics.py`` on the device (``ug_eval_pcd``) -> the same dict.  ``pred_pts=None`` evaluates the
         points that the last ``pcd_world_points`` left resident.  The sampled positions are drawn here, as the host mirror draws them;
-        ``sampling="fps"`` picks them on the device instead (``ug_eval_pcd_fps``) and adds ``pred_idx`` / ``gt_idx``."""
+        ``sampling="fps"`` picks them on the device instead (``ug_eval_pcd_fps``) and adds ``pred_idx`` / ``gt_idx``.
+        ``search="grid"`` (``ug_eval_pcd_ex`` with ``UG_PCD_SEARCH_GRID``) finds the same neighbours through a uniform
+        grid - every entry of the dict is bit-equal - and adds ``search_stats``."""
         from .harness.metrics import pcd_sample_indices
         if sampling not in ("random", "fps"):
             raise ValueError(f"eval_pcd: sampling must be 'random' or 'fps', not {sampling!r}")
+        if search not in ("brute", "grid"):
+            raise ValueError(f"eval_pcd: search must be 'brute' or 'grid', not {search!r}")
+        grid = search == "grid"
+        stats = np.zeros(8, np.int64)
         g = _f32(gt_pts).reshape(-1, 3)
         m = np.ascontiguousarray((np.asarray(masks).reshape(-1) > 0).astype(np.uint8))
         p = None if pred_pts is None else _f32(pred_pts).reshape(-1, 3)
@@ -628,9 +638,13 @@ class Engine:
             pc = np.empty((ns, 3), np.float32) if return_clouds else None
             gc = np.empty((ns, 3), np.float32) if return_clouds else None
             ip, ig = np.empty(ns, np.int64), np.empty(ns, np.int64)
-            self._ck(self.lib.ug_eval_pcd_fps(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, int(downsample_num), C.byref(o), _ptr(out), _ptr(pc),
-                                              _ptr(gc), _ptr(ip), _ptr(ig)))
-            res = self._pcd_result(out)
+            if grid:
+                self._ck(self.lib.ug_eval_pcd_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, None, int(downsample_num), C.byref(o),
+                                                 self.PCD_FPS | self.PCD_SEARCH_GRID, _ptr(out), _ptr(pc), _ptr(gc), _ptr(ip), _ptr(ig), _ptr(stats)))
+            else:
+                self._ck(self.lib.ug_eval_pcd_fps(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, int(downsample_num), C.byref(o), _ptr(out), _ptr(pc),
+                                                  _ptr(gc), _ptr(ip), _ptr(ig)))
+            res = self._pcd_result(out, stats if grid else None)
             res.update(pred_idx=ip, gt_idx=ig)
             if return_clouds:
                 col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[m > 0]
@@ -643,9 +657,13 @@ class Engine:
         out = np.zeros(32, np.float64)
         pc = np.empty((ns, 3), np.float32) if return_clouds else None
         gc = np.empty((ns, 3), np.float32) if return_clouds else None
-        self._ck(self.lib.ug_eval_pcd(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
-                                      _ptr(out), _ptr(pc), _ptr(gc)))
-        res = self._pcd_result(out)
+        if grid:
+            self._ck(self.lib.ug_eval_pcd_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
+                                             self.PCD_SEARCH_GRID, _ptr(out), _ptr(pc), _ptr(gc), None, None, _ptr(stats)))
+        else:
+            self._ck(self.lib.ug_eval_pcd(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
+                                          _ptr(out), _ptr(pc), _ptr(gc)))
+        res = self._pcd_result(out, stats if grid else None)
         if return_clouds:
             keep = m > 0
             col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[keep]
@@ -653,8 +671,13 @@ class Engine:
             res.update(pred_pcd=(pc, col), gt_pcd=(gc, col.copy()))
         return res
 
-    def _pcd_result(self, out):
+    PCD_FPS, PCD_SEARCH_GRID = 1, 2      # UG_PCD_FPS, UG_PCD_SEARCH_GRID
+    SEARCH_STAT_KEYS = ["settled", "leftover", "gt_cells", "gt_max_cell", "pred_cells", "pred_max_cell", "workspace_peak_bytes"]
+
+    def _pcd_result(self, out, stats=None):
         res = dict(zip(self.PCD_KEYS, out[:8].tolist()))
+        if stats is not None:
+            res["search_stats"] = dict(zip(self.SEARCH_STAT_KEYS, (int(v) for v in stats[:7])))
         res.update(n_points=int(out[8]), icp_iterations=int(out[9]), icp_fitness=float(out[10]), icp_rmse=float(out[11]),
                    transformation=out[12:28].reshape(4, 4).copy(), pred_scale=float(out[28]), gt_scale=float(out[29]),
                    pred_shift_z=float(out[30]), gt_shift_z=float(out[31]))
@@ -676,6 +699,24 @@ class Engine:
         idx, dist = np.empty(len(q), np.int32), np.empty(len(q), np.float64)
         self._ck(self.lib.ug_op_pcd_nn(self.ctx, _ptr(q), len(q), _ptr(t), len(t), _ptr(T), _ptr(idx), _ptr(dist)))
         return dist, idx
+
+    GRID_STAT_KEYS = ["settled", "leftover", "cells", "max_cell"]
+
+    def op_pcd_nn_grid(self, query, target, transformation=None):
+        """``op_pcd_nn`` through the uniform grid -> ``(distance, index, stats)``: the same bytes, and how many
+        queries the grid settled / left to the brute-force kernels, its cells and the points in its fullest cell."""
+        q = np.ascontiguousarray(np.asarray(query, np.float64).reshape(-1, 3)); t = np.ascontiguousarray(np.asarray(target, np.float64).reshape(-1, 3))
+        T = None if transformation is None else np.ascontiguousarray(np.asarray(transformation, np.float64).reshape(4, 4))
+        idx, dist, st = np.empty(len(q), np.int32), np.empty(len(q), np.float64), np.zeros(4, np.int64)
+        self._ck(self.lib.ug_op_pcd_nn_grid(self.ctx, _ptr(q), len(q), _ptr(t), len(t), _ptr(T), _ptr(idx), _ptr(dist), _ptr(st)))
+        return dist, idx, dict(zip(self.GRID_STAT_KEYS, (int(v) for v in st)))
+
+    def op_pcd_knn_normals_grid(self, pts, knn=30):
+        """``op_pcd_knn_normals`` through the uniform grid -> ``(neighbours, normals, stats)``: the same bytes."""
+        p = np.ascontiguousarray(np.asarray(pts, np.float64).reshape(-1, 3))
+        nbr, nrm, st = np.empty((len(p), min(knn, len(p))), np.int32), np.empty((len(p), 3), np.float64), np.zeros(4, np.int64)
+        self._ck(self.lib.ug_op_pcd_knn_normals_grid(self.ctx, _ptr(p), len(p), int(knn), _ptr(nbr), _ptr(nrm), _ptr(st)))
+        return nbr, nrm, dict(zip(self.GRID_STAT_KEYS, (int(v) for v in st)))
 
     def op_pcd_select(self, values, k):
         """The exact k-th smallest (from 0) of a float32 or float64 array."""

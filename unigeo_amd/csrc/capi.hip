@@ -298,10 +298,13 @@ static void pcd_mean_median(Ctx& c, const double* v, long n, unsigned* sel, unsi
   med = (pcd_unkey_f64(k[0]) + pcd_unkey_f64(k[1])) / 2.0;
 }
 
-// ug_eval_pcd and ug_eval_pcd_fps: one pipeline.  `fps` replaces the index list by farthest-point sampling of each aligned cloud.
+// ug_eval_pcd, ug_eval_pcd_fps and ug_eval_pcd_ex: one pipeline.  `fps` replaces the index list by farthest-point sampling of each aligned cloud
+// (DESIGN.md section 19); `grid` sends every search through a uniform grid over its target cloud and issues no other
+// launch differently.
 static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, const unsigned char* mask, long n, const long* sample_idx, long n_sample,
-                         bool fps, const ug_pcd_opts* o, double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out,
-                         long* gt_idx_out) {
+                         bool fps, bool grid, const ug_pcd_opts* o, double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out,
+                         long* gt_idx_out, long* search_stats) {
+  if (search_stats) for (int k = 0; k < 8; ++k) search_stats[k] = 0;
   UG_REQUIRE(o && gt_pts && mask && out, "options, gt_pts, mask and out32 must not be NULL");
   UG_REQUIRE(n > 0 && n < (1L << 31), "n_pixels must be positive and below 2^31");
   UG_REQUIRE(o->knn >= 1 && o->knn <= UG_PCD_MAX_KNN, "knn must be 1..UG_PCD_MAX_KNN");
@@ -329,7 +332,7 @@ static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, con
   const bool sample = fps && n_sample > 0 && n_sample < m;      // otherwise farthest-point sampling takes every point: no sampling at all
   const long ns = (sample_idx || sample) ? n_sample : m;
   if (sample_idx) for (long j = 0; j < ns; ++j) UG_REQUIRE(sample_idx[j] >= 0 && sample_idx[j] < m, "a sample index lies outside the masked points");
-  UG_REQUIRE((double)ns * (double)ns <= 1099511627776.0,
+  UG_REQUIRE(grid || (double)ns * (double)ns <= 1099511627776.0,      // with the grid the cap counts the leftover queries of every pass
              "more than 2^40 point pairs in one nearest-neighbour pass: lower pcd_downsample_num");
 
   // alignment: median shifts along z, then per cloud the median centre and the median distance from it (all exact selections)
@@ -384,7 +387,16 @@ static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, con
   // point-to-point ICP from the identity: the pair search and the Kabsch sums on the device, the 3x3 SVD here
   const int ny = pcd_nn_slices(ns, ns);
   int* idx = c.ws.get<int>(ns); double* dist = c.ws.get<double>(ns);
-  int* pidx = c.ws.get<int>((long)ny * ns); double* pdist = c.ws.get<double>((long)ny * ns);
+  int* pidx = nullptr; double* pdist = nullptr;
+  if (!grid) { pidx = c.ws.get<int>((long)ny * ns); pdist = c.ws.get<double>((long)ny * ns); }
+  PcdGrid gridG{}, gridP{};      // over g64, built once for the ICP, the accuracy pass and its own KNN; over the moved prediction, built after the ICP
+  PcdSearchStats st;
+  long cellmax[2] = {0, 0};
+  int* left = nullptr; unsigned* n_left = nullptr;
+  if (grid) {
+    left = c.ws.get<int>(ns); n_left = c.ws.get<unsigned>(1);
+    gridG = pcd_grid_build(c, g64, ns, &cellmax[0]);
+  }
   double* dT = c.ws.get<double>(16);
   double* part = c.ws.get<double>(PCD_MAXB * 17);
   double sums[17];
@@ -392,7 +404,8 @@ static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, con
   auto evaluate = [&](double& fit, double& rmse) {      // the stream is idle whenever dT is rewritten: every evaluation ends with a fetch
     UG_CHECK(hipMemcpy(dT, Tm, sizeof(Tm), hipMemcpyHostToDevice));
     int nb = 0;
-    launch_pcd_nn(p64, ns, g64, ns, dT, idx, dist, pidx, pdist, c.stream);
+    if (grid) pcd_nn_search_grid(c, p64, ns, dT, gridG, idx, dist, left, n_left, st);
+    else launch_pcd_nn(p64, ns, g64, ns, dT, idx, dist, pidx, pdist, c.stream);
     launch_pcd_kabsch(p64, g64, ns, dT, idx, dist, thr, part, &nb, c.stream);
     UG_CHECK(hipGetLastError());
     fetch_partial_sums(c, part, nb, sums);
@@ -421,17 +434,32 @@ static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, con
   int* idx2 = c.ws.get<int>(ns); double* dist2 = c.ws.get<double>(ns);
   double* dot1 = c.ws.get<double>(ns); double* dot2 = c.ws.get<double>(ns);
   launch_pcd_move(p64, ns, dT, moved, c.stream);      // dT holds the final transformation: the last evaluation uploaded it
-  launch_pcd_knn_normals(moved, ns, o->knn, nullptr, nP, c.stream);
-  launch_pcd_knn_normals(g64, ns, o->knn, nullptr, nG, c.stream);
-  launch_pcd_nn(moved, ns, g64, ns, nullptr, idx, dist, pidx, pdist, c.stream);       // accuracy: prediction -> ground truth
-  launch_pcd_normal_dot(nP, nG, idx, ns, dot1, c.stream);
-  launch_pcd_nn(g64, ns, moved, ns, nullptr, idx2, dist2, pidx, pdist, c.stream);     // completion: ground truth -> prediction
-  launch_pcd_normal_dot(nG, nP, idx2, ns, dot2, c.stream);
+  if (grid) {
+    gridP = pcd_grid_build(c, moved, ns, &cellmax[1]);
+    pcd_knn_search_grid(c, gridP, o->knn, nullptr, nP, left, n_left, st);
+    pcd_knn_search_grid(c, gridG, o->knn, nullptr, nG, left, n_left, st);
+    pcd_nn_search_grid(c, moved, ns, nullptr, gridG, idx, dist, left, n_left, st);      // accuracy: prediction -> ground truth
+    launch_pcd_normal_dot(nP, nG, idx, ns, dot1, c.stream);
+    pcd_nn_search_grid(c, g64, ns, nullptr, gridP, idx2, dist2, left, n_left, st);      // completion: ground truth -> prediction
+    launch_pcd_normal_dot(nG, nP, idx2, ns, dot2, c.stream);
+  } else {
+    launch_pcd_knn_normals(moved, ns, o->knn, nullptr, nP, c.stream);
+    launch_pcd_knn_normals(g64, ns, o->knn, nullptr, nG, c.stream);
+    launch_pcd_nn(moved, ns, g64, ns, nullptr, idx, dist, pidx, pdist, c.stream);       // accuracy: prediction -> ground truth
+    launch_pcd_normal_dot(nP, nG, idx, ns, dot1, c.stream);
+    launch_pcd_nn(g64, ns, moved, ns, nullptr, idx2, dist2, pidx, pdist, c.stream);     // completion: ground truth -> prediction
+    launch_pcd_normal_dot(nG, nP, idx2, ns, dot2, c.stream);
+  }
   UG_CHECK(hipGetLastError());
   pcd_mean_median(c, dist, ns, sel, res, part, out[0], out[4]);
   pcd_mean_median(c, dist2, ns, sel, res, part, out[1], out[5]);
   pcd_mean_median(c, dot1, ns, sel, res, part, out[2], out[6]);
   pcd_mean_median(c, dot2, ns, sel, res, part, out[3], out[7]);
+  if (grid && search_stats) {
+    search_stats[0] = st.settled; search_stats[1] = st.left;
+    search_stats[2] = gridG.cells; search_stats[3] = cellmax[0]; search_stats[4] = gridP.cells; search_stats[5] = cellmax[1];
+    search_stats[6] = (long)c.ws.peak();
+  }
 }
 
 // ---------------------------------------------------------------- clip preparation helpers (ug_prep_*)
@@ -584,7 +612,7 @@ int ug_eval_pcd(ug_ctx* x, const float* pred_pts, const float* gt_pts, const uns
                 const ug_pcd_opts* o, double* out, float* pred_cloud_out, float* gt_cloud_out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
-    eval_pcd_run(c, pred_pts, gt_pts, mask, n, sample_idx, n_sample, false, o, out, pred_cloud_out, gt_cloud_out, nullptr, nullptr);
+    eval_pcd_run(c, pred_pts, gt_pts, mask, n, sample_idx, n_sample, false, false, o, out, pred_cloud_out, gt_cloud_out, nullptr, nullptr, nullptr);
   });
 }
 
@@ -592,7 +620,23 @@ int ug_eval_pcd_fps(ug_ctx* x, const float* pred_pts, const float* gt_pts, const
                     double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out, long* gt_idx_out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
-    eval_pcd_run(c, pred_pts, gt_pts, mask, n, nullptr, n_sample, true, o, out, pred_cloud_out, gt_cloud_out, pred_idx_out, gt_idx_out);
+    eval_pcd_run(c, pred_pts, gt_pts, mask, n, nullptr, n_sample, true, false, o, out, pred_cloud_out, gt_cloud_out, pred_idx_out, gt_idx_out, nullptr);
+  });
+}
+int ug_eval_pcd_ex(ug_ctx* x, const float* pred_pts, const float* gt_pts, const unsigned char* mask, long n, const long* sample_idx, long n_sample,
+                   const ug_pcd_opts* o, int flags, double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out, long* gt_idx_out,
+                   long* search_stats) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const unsigned unknown = (unsigned)flags & ~(unsigned)(UG_PCD_FPS | UG_PCD_SEARCH_GRID);
+    if (unknown) {
+      char hex[16]; snprintf(hex, sizeof hex, "0x%x", unknown);
+      throw std::runtime_error(std::string("ug_eval_pcd_ex: unknown flag bits ") + hex + " (UG_PCD_FPS | UG_PCD_SEARCH_GRID)");
+    }
+    const bool fps = (flags & UG_PCD_FPS) != 0;
+    UG_REQUIRE(!fps || !sample_idx, "UG_PCD_FPS picks the points itself: sample_idx must be NULL");
+    eval_pcd_run(c, pred_pts, gt_pts, mask, n, sample_idx, n_sample, fps, (flags & UG_PCD_SEARCH_GRID) != 0, o, out, pred_cloud_out, gt_cloud_out,
+                 pred_idx_out, gt_idx_out, search_stats);
   });
 }
 

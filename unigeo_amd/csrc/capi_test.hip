@@ -316,6 +316,50 @@ int ug_op_pcd_knn_normals(ug_ctx* x, const double* pts, long n, int knn, int* nb
     UG_CHECK(hipMemcpy(normals_out, nrm, (size_t)n * 24, hipMemcpyDeviceToHost));
   });
 }
+// the two searches through the uniform grid
+int ug_op_pcd_nn_grid(ug_ctx* x, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out,
+                      long* stats) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(query && target && idx_out && dist_out, "query, target, idx_out and dist_out must not be NULL");
+    UG_REQUIRE(nq >= 1 && nt >= 1 && nq < (1L << 31) && nt < (1L << 31), "point counts must be 1 .. 2^31 - 1");
+    double* dq = c.ws.get<double>(nq * 3); double* dt = c.ws.get<double>(nt * 3);
+    UG_CHECK(hipMemcpy(dq, query, (size_t)nq * 24, hipMemcpyHostToDevice));
+    UG_CHECK(hipMemcpy(dt, target, (size_t)nt * 24, hipMemcpyHostToDevice));
+    double* dT = nullptr;
+    if (T44) { dT = c.ws.get<double>(16); UG_CHECK(hipMemcpy(dT, T44, 128, hipMemcpyHostToDevice)); }
+    int* idx = c.ws.get<int>(nq); double* dist = c.ws.get<double>(nq);
+    int* left = c.ws.get<int>(nq); unsigned* n_left = c.ws.get<unsigned>(1);
+    long cellmax = 0;
+    PcdSearchStats st;
+    const PcdGrid g = pcd_grid_build(c, dt, nt, &cellmax);
+    pcd_nn_search_grid(c, dq, nq, dT, g, idx, dist, left, n_left, st);
+    UG_CHECK(hipMemcpy(idx_out, idx, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    UG_CHECK(hipMemcpy(dist_out, dist, (size_t)nq * 8, hipMemcpyDeviceToHost));
+    if (stats) { stats[0] = st.settled; stats[1] = st.left; stats[2] = g.cells; stats[3] = cellmax; }
+  });
+}
+int ug_op_pcd_knn_normals_grid(ug_ctx* x, const double* pts, long n, int knn, int* nbr_out, double* normals_out, long* stats) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pts && normals_out, "pts and normals_out must not be NULL");
+    UG_REQUIRE(n >= 1 && n < (1L << 31) && knn >= 1 && knn <= UG_PCD_MAX_KNN, "n must be 1 .. 2^31 - 1 and knn 1 .. UG_PCD_MAX_KNN");
+    const long k = n < knn ? n : knn;
+    double* dp = c.ws.get<double>(n * 3); UG_CHECK(hipMemcpy(dp, pts, (size_t)n * 24, hipMemcpyHostToDevice));
+    int* nbr = nbr_out ? c.ws.get<int>(n * k) : nullptr;
+    double* nrm = c.ws.get<double>(n * 3);
+    int* left = c.ws.get<int>(n); unsigned* n_left = c.ws.get<unsigned>(1);
+    long cellmax = 0;
+    PcdSearchStats st;
+    const PcdGrid g = pcd_grid_build(c, dp, n, &cellmax);
+    pcd_knn_search_grid(c, g, knn, nbr, nrm, left, n_left, st);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    if (nbr_out) UG_CHECK(hipMemcpy(nbr_out, nbr, (size_t)n * k * 4, hipMemcpyDeviceToHost));
+    UG_CHECK(hipMemcpy(normals_out, nrm, (size_t)n * 24, hipMemcpyDeviceToHost));
+    if (stats) { stats[0] = st.settled; stats[1] = st.left; stats[2] = g.cells; stats[3] = cellmax; }
+  });
+}
 // farthest-point sampling alone
 int ug_op_pcd_fps(ug_ctx* x, const float* pts, long n, long k, long* idx_out, float* sel_dist_out) {
   UG_TRY(x, {

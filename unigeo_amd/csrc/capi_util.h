@@ -81,6 +81,76 @@ static inline DepthEvalBufs depth_eval_upload(Ctx& c, const float* pred, const f
   if (cmask) { b.dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(b.dm, cmask, n, hipMemcpyHostToDevice)); }
   return b;
 }
+// ------------------------------------------------------------------ exact grid search: what ug_eval_pcd_ex (product) and ug_op_pcd_*_grid (test) share
+struct PcdSearchStats { long settled = 0, left = 0; };
+static inline unsigned pcd_fetch_u32(Ctx& c, const unsigned* d) {
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  unsigned v = 0;
+  UG_CHECK(hipMemcpy(&v, d, 4, hipMemcpyDeviceToHost));
+  return v;
+}
+// The grid over t [n,3] (device).  sorted / orig / start stay on the workspace stack until the caller's Scope ends; the sort's scratch is released here.
+static inline PcdGrid pcd_grid_build(Ctx& c, const double* t, long n, long* max_cell) {
+  PcdGrid g{};
+  double* part = c.ws.get<double>(PCD_MAXB * 7); double* box = c.ws.get<double>(8);
+  launch_pcd_grid_bbox(t, n, part, box, c.stream);
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  double hb[8];
+  UG_CHECK(hipMemcpy(hb, box, sizeof(hb), hipMemcpyDeviceToHost));
+  pcd_grid_shape(hb, n, &g);
+  g.pts = t;
+  unsigned* start = c.ws.get<unsigned>(g.cells + 1);
+  double* sorted = c.ws.get<double>(n * 3); int* orig = c.ws.get<int>(n);
+  g.start = start; g.sorted = sorted; g.orig = orig;
+  const size_t mk = c.ws.mark();
+  unsigned* counts = c.ws.get<unsigned>(g.cells); unsigned* bsum = c.ws.get<unsigned>(PCD_MAXB + 2); int* cell = c.ws.get<int>(n);
+  launch_pcd_grid_build(t, n, g, counts, start, bsum, cell, sorted, orig, c.stream);
+  *max_cell = (long)pcd_fetch_u32(c, bsum + PCD_MAXB + 1);
+  c.ws.release(mk);
+  return g;
+}
+// launch_pcd_nn through the grid; left [nq] ints and n_left (one word) are device scratch.  Leaves the stream idle.
+static inline void pcd_nn_search_grid(Ctx& c, const double* q, long nq, const double* T44, const PcdGrid& g, int* idx, double* dist, int* left,
+                                      unsigned* n_left, PcdSearchStats& st) {
+  launch_pcd_nn_grid(q, nq, T44, g, idx, dist, left, n_left, c.stream);
+  const long nl = (long)pcd_fetch_u32(c, n_left);
+  UG_REQUIRE(nl >= 0 && nl <= nq, "leftover count out of range");
+  st.settled += nq - nl; st.left += nl;
+  if (nl == 0) return;
+  UG_REQUIRE((double)nl * (double)g.n <= 1099511627776.0,
+             "more than 2^40 point pairs in one nearest-neighbour pass over the queries the grid left: lower pcd_downsample_num");
+  const size_t mk = c.ws.mark();
+  const int ny = pcd_nn_slices(nl, g.n);
+  double* ql = c.ws.get<double>(nl * 3); int* il = c.ws.get<int>(nl); double* dl = c.ws.get<double>(nl);
+  int* pidx = c.ws.get<int>((long)ny * nl); double* pdist = c.ws.get<double>((long)ny * nl);
+  launch_pcd_gather64(q, left, nl, ql, c.stream);
+  launch_pcd_nn(ql, nl, g.pts, g.n, T44, il, dl, pidx, pdist, c.stream);
+  launch_pcd_nn_scatter(left, nl, il, dl, idx, dist, c.stream);
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  c.ws.release(mk);
+}
+// launch_pcd_knn_normals of the cloud the grid was built over.  A cloud with a non-finite point goes to the brute-force kernel whole: such a point
+// can enter its lists, which no cell holds.
+static inline void pcd_knn_search_grid(Ctx& c, const PcdGrid& g, int knn, int* nbr, double* normals, int* left, unsigned* n_left, PcdSearchStats& st) {
+  const char* cap = "more than 2^40 point pairs in one neighbour pass over the points the grid left: lower pcd_downsample_num";
+  if (g.n_in < g.n) {
+    UG_REQUIRE((double)g.n * (double)g.n <= 1099511627776.0, cap);
+    launch_pcd_knn_normals(g.pts, g.n, knn, nbr, normals, c.stream);
+    st.left += g.n;
+    return;
+  }
+  launch_pcd_knn_grid(g, knn, nbr, normals, left, n_left, c.stream);
+  const long nl = (long)pcd_fetch_u32(c, n_left);
+  UG_REQUIRE(nl >= 0 && nl <= g.n, "leftover count out of range");
+  st.settled += g.n - nl; st.left += nl;
+  if (nl == 0) return;
+  UG_REQUIRE((double)nl * (double)g.n <= 1099511627776.0, cap);
+  launch_pcd_knn_normals_list(g.pts, g.n, knn, left, nl, nbr, normals, c.stream);
+}
+
 // the result words of launch_masked_median, once the stream is idle: how many pixels were selected, the lower medians of prediction and ground truth
 static inline void read_masked_median(Ctx& c, const unsigned* sel, unsigned& count, float& mp, float& mg) {
   UG_CHECK(hipStreamSynchronize(c.stream));

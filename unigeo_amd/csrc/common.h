@@ -333,6 +333,36 @@ void launch_pcd_sum(const double* v, long n, double* part /*[PCD_MAXB]*/, int* n
 void launch_pcd_fps(const float* p, long n, long k, float* m, float* pm, int* pi, long* idx /*[k]*/, float* sel_dist /*[k]*/, hipStream_t s);
 // out32[j] = src[idx[j]] and its float64 copy (either output may be NULL)
 void launch_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64, hipStream_t s);
+// exact search through a uniform grid (kernels/pcd.hip): the same results as launch_pcd_nn / launch_pcd_knn_normals.
+#define PCD_GRID_RINGS 3                 // rings of cells a query walks before it is left to the brute-force kernels
+#define PCD_GRID_MAX_CELLS (1L << 24)    // cap on Gx * Gy * Gz
+#define PCD_GRID_OCC 4.0                 // points per cell that the rule for h aims at
+#define PCD_GRID_EPS 9.5367431640625e-07 // 2^-20: slack of the ring bound, far above the rounding of the cell arithmetic (2^24 cells * 2^-51)
+struct PcdGrid {                         // shape from the host (pcd_grid_shape), arrays on the device
+  double mn[3], h, inv_h;
+  int G[3];
+  long cells, n, n_in;                   // n points went in, n_in of them finite and in a cell
+  const double* pts;                     // the cloud as given [n,3]
+  const double* sorted;                  // [n_in,3] cell by cell
+  const int* orig;                       // [n_in] the index in pts
+  const unsigned* start;                 // [cells + 1] first sorted position of every cell
+};
+// box (device, 8 doubles): min xyz, max xyz of the finite points, then their count; part [PCD_MAXB * 7] scratch
+void launch_pcd_grid_bbox(const double* t, long n, double* part, double* box, hipStream_t s);
+// host: cell edge and cells per axis from the box (the rule of DESIGN.md section 20); fills mn, h, inv_h, G, cells, n, n_in
+void pcd_grid_shape(const double* box, long n, PcdGrid* g);
+// counting sort into the cells: counts [cells] (zeroed here), start [cells + 1], bsum [PCD_MAXB + 2] (bsum[PCD_MAXB + 1] = the fullest cell),
+// cell [n] scratch, sorted [n,3] / orig [n] outputs
+void launch_pcd_grid_build(const double* t, long n, const PcdGrid& g, unsigned* counts, unsigned* start, unsigned* bsum, int* cell, double* sorted,
+                           int* orig, hipStream_t s);
+// settled queries get idx / dist; the others are appended to left [nq] and counted in *n_left (device, zeroed here)
+void launch_pcd_nn_grid(const double* q, long nq, const double* T44, const PcdGrid& g, int* idx, double* dist, int* left, unsigned* n_left,
+                        hipStream_t s);
+void launch_pcd_knn_grid(const PcdGrid& g, int knn, int* nbr /* or NULL */, double* normals, int* left, unsigned* n_left, hipStream_t s);
+// launch_pcd_knn_normals for the nl queries list[0 .. nl) only; rows of the other points are not written
+void launch_pcd_knn_normals_list(const double* pts, long n, int knn, const int* list, long nl, int* nbr, double* normals, hipStream_t s);
+void launch_pcd_gather64(const double* src, const int* list, long nl, double* out, hipStream_t s);                          // out[i] = src[list[i]]
+void launch_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist, hipStream_t s);
 // depth / normal visualisation panels (kernels/vis.hip); part: 2 * 1024 floats of scratch, out2 (device) = (vmin, vmax)
 void launch_vis_range(const float* x, long n, float* part, float* out2, hipStream_t s);
 void launch_vis_panel(const float* rgb, const float* normals, const float* depth, const float* lut, const float* cbar, unsigned char* out, int T,

@@ -4,8 +4,10 @@
 //   and the farthest-point sampling of its disabled branch (eval_pcd.py:84-93,172-193), in unfused fp32.
 // Brute-force pair arithmetic in unfused fp64 (fp contract off), the arithmetic of the numpy mirror in harness/metrics.py.  Every kernel is
 // deterministic: reductions are two-stage in a fixed order, target slices are combined in slice order, the only atomics are integer
-// histogram counts.  No float atomics, no cooperative launch, no inline assembly.
+// histogram counts.  No float atomics, no cooperative launch, no inline assembly.  The exact search through a uniform grid (DESIGN.md
+// section 20) finds the same neighbours without visiting every pair; its atomics are integer counts and list lengths.
 #include "../common.h"
+#include "../pcd_host.h"
 
 // No contraction anywhere in this file: every product and every sum below rounds on its own, as the numpy mirror's do.  (The __dmul_rn /
 // __dadd_rn intrinsics are plain operators in this toolchain and would fuse; the pragma is what keeps a * b + c two roundings.)
@@ -264,36 +266,9 @@ __global__ __launch_bounds__(PB) void k_pcd_normal_dot(const double* nq, const d
 }
 
 // ------------------------------------------------------------------------------------------------------------- KNN covariance normals
-// One query per thread.  The running top-k list, sorted by (squared distance, index), lives in LDS in a [k][thread] layout: the threads of
-// a wave touch consecutive words.  Targets arrive in index order, so an equal distance goes behind the entries already there.  Then the mean
-// and the covariance of the k neighbours in fp64 (list order) and a cyclic Jacobi eigen-solve with a fixed number of sweeps.
-__global__ __launch_bounds__(KNN_B) void k_pcd_knn(const double* pts, long n, int k, int* nbr, double* normals) {
-  __shared__ double ld[KNN_MAX][KNN_B];
-  __shared__ int li[KNN_MAX][KNN_B];
-  __shared__ double tile[KNN_B * 3];
-  const int tid = threadIdx.x;
-  const long i = (long)blockIdx.x * KNN_B + tid;
-  const bool live = i < n;
-  double x = 0, y = 0, z = 0;
-  if (live) { x = pts[i * 3]; y = pts[i * 3 + 1]; z = pts[i * 3 + 2]; }
-  int cnt = 0;
-  for (long base = 0; base < n; base += KNN_B) {
-    const int tc = (int)(n - base < KNN_B ? n - base : KNN_B);
-    for (int e = tid; e < tc * 3; e += KNN_B) tile[e] = pts[base * 3 + e];
-    __syncthreads();
-    if (live)
-      for (int j = 0; j < tc; ++j) {
-        const double d2 = pcd_d2(x, y, z, tile + j * 3);
-        if (cnt < k || d2 < ld[cnt - 1][tid]) {
-          int pos = cnt < k ? cnt++ : k - 1;
-          while (pos > 0 && ld[pos - 1][tid] > d2) { ld[pos][tid] = ld[pos - 1][tid]; li[pos][tid] = li[pos - 1][tid]; --pos; }
-          ld[pos][tid] = d2; li[pos][tid] = (int)(base + j);
-        }
-      }
-    __syncthreads();
-  }
-  if (!live) return;
-  if (nbr) for (int j = 0; j < k; ++j) nbr[i * k + j] = li[j][tid];
+// The mean and the covariance of the k listed neighbours in fp64 (list order) and the cyclic Jacobi eigen-solve with a fixed number of sweeps:
+// the one copy that k_pcd_knn and k_pcd_knn_grid share, so equal lists give bit-equal normals.
+__device__ __forceinline__ void pcd_list_normal(const double* pts, const int (*li)[KNN_B], int tid, int k, double* out) {
   double nx = 0, ny = 0, nz = 1;
   if (k >= 3) {
     double m[3] = {0, 0, 0};
@@ -333,7 +308,41 @@ __global__ __launch_bounds__(KNN_B) void k_pcd_knn(const double* pts, long n, in
     const double len = sqrt(ex * ex + ey * ey + ez * ez);
     if (len > 0) { nx = ex / len; ny = ey / len; nz = ez / len; }
   }
-  normals[i * 3] = nx; normals[i * 3 + 1] = ny; normals[i * 3 + 2] = nz;
+  out[0] = nx; out[1] = ny; out[2] = nz;
+}
+
+// One query per thread.  The running top-k list, sorted by (squared distance, index), lives in LDS in a [k][thread] layout: the threads of
+// a wave touch consecutive words.  Targets arrive in index order, so an equal distance goes behind the entries already there.  Then the normal
+// from the list.  `list` (or NULL with nl = n) names the points to serve: the leftovers of k_pcd_knn_grid.
+__global__ __launch_bounds__(KNN_B) void k_pcd_knn(const double* pts, long n, int k, const int* list, long nl, int* nbr, double* normals) {
+  __shared__ double ld[KNN_MAX][KNN_B];
+  __shared__ int li[KNN_MAX][KNN_B];
+  __shared__ double tile[KNN_B * 3];
+  const int tid = threadIdx.x;
+  const long slot = (long)blockIdx.x * KNN_B + tid;      // without a list (NULL, nl = n) slot is the point itself
+  const bool live = slot < nl;
+  const long i = live && list ? list[slot] : slot;
+  double x = 0, y = 0, z = 0;
+  if (live) { x = pts[i * 3]; y = pts[i * 3 + 1]; z = pts[i * 3 + 2]; }
+  int cnt = 0;
+  for (long base = 0; base < n; base += KNN_B) {
+    const int tc = (int)(n - base < KNN_B ? n - base : KNN_B);
+    for (int e = tid; e < tc * 3; e += KNN_B) tile[e] = pts[base * 3 + e];
+    __syncthreads();
+    if (live)
+      for (int j = 0; j < tc; ++j) {
+        const double d2 = pcd_d2(x, y, z, tile + j * 3);
+        if (cnt < k || d2 < ld[cnt - 1][tid]) {
+          int pos = cnt < k ? cnt++ : k - 1;
+          while (pos > 0 && ld[pos - 1][tid] > d2) { ld[pos][tid] = ld[pos - 1][tid]; li[pos][tid] = li[pos - 1][tid]; --pos; }
+          ld[pos][tid] = d2; li[pos][tid] = (int)(base + j);
+        }
+      }
+    __syncthreads();
+  }
+  if (!live) return;
+  if (nbr) for (int j = 0; j < k; ++j) nbr[i * k + j] = li[j][tid];
+  pcd_list_normal(pts, li, tid, k, normals + i * 3);
 }
 
 // ------------------------------------------------------------------------------------------------------------- farthest-point sampling
@@ -408,6 +417,220 @@ __global__ __launch_bounds__(PB) void k_pcd_gather(const float* src, const long*
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------- exact search through a uniform grid
+// DESIGN.md section 20.  A counting sort of the finite targets into cubic cells of edge h, then every query walks the cells around its own, ring
+// by ring, with the arithmetic of k_pcd_nn / k_pcd_knn on every candidate.  After ring r every target not yet seen lies more than r * h away
+// along some axis, so a best squared distance below ((r * h)(1 - eps))^2 is final.  What PCD_GRID_RINGS rings do not settle is appended to a
+// leftover list for the brute-force kernels.  The only atomics are integer counts; the order of the points inside a cell and of the leftover list
+// varies between calls, the outputs do not: every comparison is on (squared distance, original index).
+struct GridDev { double mn[3], h, inv_h; int G[3]; const double* sorted; const int* orig; const unsigned* start; };
+static GridDev grid_dev(const PcdGrid& g) {
+  GridDev d;
+  for (int a = 0; a < 3; ++a) { d.mn[a] = g.mn[a]; d.G[a] = g.G[a]; }
+  d.h = g.h; d.inv_h = g.inv_h; d.sorted = g.sorted; d.orig = g.orig; d.start = g.start;
+  return d;
+}
+__device__ __forceinline__ bool pcd_finite3(double x, double y, double z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+// the clamp keeps every cell index in range, whatever the coordinate: a query outside the box lands in a border cell
+__device__ __forceinline__ int pcd_cell_axis(double x, double mn, double inv_h, int G) {
+  const double f = floor((x - mn) * inv_h);
+  return !(f >= 0.0) ? 0 : (f > (double)(G - 1) ? G - 1 : (int)f);
+}
+
+template <int OP> __device__ __forceinline__ double pcd_block_reduce(double v, double* sh) {      // OP 0: sum, 1: min, 2: max; fixed order
+  const int tid = threadIdx.x;
+  sh[tid] = v;
+  __syncthreads();
+  for (int o = PB / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      const double a = sh[tid], b = sh[tid + o];
+      sh[tid] = OP == 0 ? a + b : (OP == 1 ? (b < a ? b : a) : (b > a ? b : a));
+    }
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+// stage 1 (final = 0): per workgroup min xyz, max xyz and the count of the finite points of t -> out[b * 7 ..]; stage 2 (final = 1, one workgroup):
+// the same over the nb rows of stage 1 -> out[0 .. 7)
+__global__ __launch_bounds__(PB) void k_pcd_grid_bbox(const double* in, long n, int final, double* out) {
+  __shared__ double sh[PB];
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, cnt = 0;
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    if (final) {
+      for (int a = 0; a < 3; ++a) { const double l = in[i * 7 + a], h = in[i * 7 + 3 + a]; lo[a] = l < lo[a] ? l : lo[a]; hi[a] = h > hi[a] ? h : hi[a]; }
+      cnt += in[i * 7 + 6];
+    } else {
+      const double p[3] = {in[i * 3], in[i * 3 + 1], in[i * 3 + 2]};
+      if (!pcd_finite3(p[0], p[1], p[2])) continue;
+      for (int a = 0; a < 3; ++a) { lo[a] = p[a] < lo[a] ? p[a] : lo[a]; hi[a] = p[a] > hi[a] ? p[a] : hi[a]; }
+      cnt += 1.0;
+    }
+  }
+  double r[7];
+  for (int a = 0; a < 3; ++a) { r[a] = pcd_block_reduce<1>(lo[a], sh); r[3 + a] = pcd_block_reduce<2>(hi[a], sh); }
+  r[6] = pcd_block_reduce<0>(cnt, sh);
+  if (threadIdx.x == 0) for (int k = 0; k < 7; ++k) out[(long)blockIdx.x * 7 + k] = r[k];
+}
+
+// cell of every target (-1: a non-finite coordinate, in no cell) and the integer count per cell
+__global__ __launch_bounds__(PB) void k_pcd_grid_count(const double* t, long n, GridDev g, unsigned* counts, int* cell) {
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    const double x = t[i * 3], y = t[i * 3 + 1], z = t[i * 3 + 2];
+    int c = -1;
+    if (pcd_finite3(x, y, z)) {
+      const int cx = pcd_cell_axis(x, g.mn[0], g.inv_h, g.G[0]), cy = pcd_cell_axis(y, g.mn[1], g.inv_h, g.G[1]),
+                cz = pcd_cell_axis(z, g.mn[2], g.inv_h, g.G[2]);
+      c = (cz * g.G[1] + cy) * g.G[0] + cx;
+      atomicAdd(&counts[c], 1u);
+    }
+    cell[i] = c;
+  }
+}
+// exclusive scan of the counts, as the masked compaction does it: workgroup b owns the cells [b * chunk, (b + 1) * chunk)
+__global__ __launch_bounds__(PB) void k_pcd_grid_scan_sums(const unsigned* counts, long cells, long chunk, unsigned* bsum) {
+  __shared__ unsigned sc[PB];
+  const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < cells ? b0 + chunk : cells;
+  unsigned cnt = 0, mx = 0;
+  for (long i = b0 + threadIdx.x; i < b1; i += PB) { const unsigned v = counts[i]; cnt += v; mx = v > mx ? v : mx; }
+  unsigned total;
+  block_scan_excl(cnt, sc, &total);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+  if (mx) atomicMax(&bsum[PCD_MAXB + 1], mx);      // the fullest cell: an integer maximum, the same in any order
+}
+__global__ __launch_bounds__(PB) void k_pcd_grid_scan_cells(const unsigned* counts, long cells, long chunk, const unsigned* bsum, unsigned* start) {
+  __shared__ unsigned sc[PB];
+  const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < cells ? b0 + chunk : cells;
+  unsigned base = bsum[blockIdx.x];
+  for (long s0 = b0; s0 < b1; s0 += PB) {      // chunk is a multiple of PB: every thread of the block takes every step
+    const long i = s0 + threadIdx.x;
+    const unsigned v = i < b1 ? counts[i] : 0u;
+    unsigned total;
+    const unsigned pos = block_scan_excl(v, sc, &total);
+    if (i < b1) start[i] = base + pos;
+    base += total;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) start[cells] = bsum[PCD_MAXB];
+}
+// the sorted points and their original indices; counts runs down to zero, so position start + count - 1 is taken exactly once
+__global__ __launch_bounds__(PB) void k_pcd_grid_scatter(const double* t, long n, const int* cell, const unsigned* start, unsigned* counts,
+                                                         double* sorted, int* orig) {
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+    const int c = cell[i];
+    if (c < 0) continue;
+    const unsigned long pos = (unsigned long)start[c] + (atomicSub(&counts[c], 1u) - 1u);
+    sorted[pos * 3] = t[i * 3]; sorted[pos * 3 + 1] = t[i * 3 + 1]; sorted[pos * 3 + 2] = t[i * 3 + 2];
+    orig[pos] = (int)i;
+  }
+}
+
+// Ring r around cell (cx, cy, cz), clipped to the grid: visit(a, b) for every run [a, b) of sorted positions.  Cells are stored x fastest, so a
+// row of the two z faces and the two y faces is one run; the rows in between contribute their two end cells.
+template <class F> __device__ __forceinline__ void pcd_ring(const GridDev& g, int cx, int cy, int cz, int r, F&& visit) {
+  const int x0 = cx - r > 0 ? cx - r : 0, x1 = cx + r < g.G[0] - 1 ? cx + r : g.G[0] - 1;
+  const int y0 = cy - r > 0 ? cy - r : 0, y1 = cy + r < g.G[1] - 1 ? cy + r : g.G[1] - 1;
+  const int z0 = cz - r > 0 ? cz - r : 0, z1 = cz + r < g.G[2] - 1 ? cz + r : g.G[2] - 1;
+  for (int zz = z0; zz <= z1; ++zz)
+    for (int yy = y0; yy <= y1; ++yy) {
+      const long row = ((long)zz * g.G[1] + yy) * g.G[0];
+      if (zz - cz == r || cz - zz == r || yy - cy == r || cy - yy == r) visit(g.start[row + x0], g.start[row + x1 + 1]);
+      else {
+        if (cx - r >= 0) visit(g.start[row + cx - r], g.start[row + cx - r + 1]);
+        if (cx + r <= g.G[0] - 1) visit(g.start[row + cx + r], g.start[row + cx + r + 1]);
+      }
+    }
+}
+__device__ __forceinline__ bool pcd_ring_covers(const GridDev& g, int cx, int cy, int cz, int r) {      // rings 0 .. r hold every cell
+  return cx - r <= 0 && cx + r >= g.G[0] - 1 && cy - r <= 0 && cy + r >= g.G[1] - 1 && cz - r <= 0 && cz + r >= g.G[2] - 1;
+}
+__device__ __forceinline__ double pcd_ring_bound2(const GridDev& g, int r) {
+  const double b = ((double)r * g.h) * (1.0 - PCD_GRID_EPS);
+  return b * b;
+}
+
+// One query per thread, moved by T44 as k_pcd_nn moves it.  The winner is the lexicographic minimum of (squared distance, original index): cells
+// are not visited in index order.  A query is settled when a target was found and either the ring bound or the whole grid is behind it.
+__global__ __launch_bounds__(PB) void k_pcd_nn_grid(const double* q, long nq, const double* T44, GridDev g, long n_in, int* idx, double* dist,
+                                                    int* left, unsigned* n_left) {
+  const long i = (long)blockIdx.x * PB + threadIdx.x;
+  if (i >= nq) return;
+  double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
+  pcd_move(T44, x, y, z);
+  double best = INFINITY;
+  int bi = -1;
+  bool settled = false;
+  if (n_in > 0 && pcd_finite3(x, y, z)) {
+    const int cx = pcd_cell_axis(x, g.mn[0], g.inv_h, g.G[0]), cy = pcd_cell_axis(y, g.mn[1], g.inv_h, g.G[1]),
+              cz = pcd_cell_axis(z, g.mn[2], g.inv_h, g.G[2]);
+    for (int r = 0; r <= PCD_GRID_RINGS && !settled; ++r) {
+      pcd_ring(g, cx, cy, cz, r, [&](unsigned a, unsigned b) {
+        for (unsigned p = a; p < b; ++p) {
+          const double d2 = pcd_d2(x, y, z, g.sorted + (unsigned long)p * 3);
+          const int j = g.orig[p];
+          if (d2 < best || (d2 == best && j < bi)) { best = d2; bi = j; }
+        }
+      });
+      const bool all = pcd_ring_covers(g, cx, cy, cz, r);
+      settled = bi >= 0 && (all || best < pcd_ring_bound2(g, r));
+      if (all) break;
+    }
+  }
+  if (settled) { idx[i] = bi; dist[i] = __dsqrt_rn(best); }
+  else left[atomicAdd(n_left, 1u)] = (int)i;
+}
+
+// KNN of the cloud the grid was built over (every point finite), one point per thread, lists in LDS as k_pcd_knn holds them.  Insertion is by
+// (squared distance, original index).  Settled when the list is full (k = min(knn, n)) and its last entry is below the ring bound, or the whole
+// grid has been seen.
+__global__ __launch_bounds__(KNN_B) void k_pcd_knn_grid(const double* pts, long n, int k, GridDev g, int* nbr, double* normals, int* left,
+                                                        unsigned* n_left) {
+  __shared__ double ld[KNN_MAX][KNN_B];
+  __shared__ int li[KNN_MAX][KNN_B];
+  const int tid = threadIdx.x;
+  const long i = (long)blockIdx.x * KNN_B + tid;
+  if (i >= n) return;      // no barrier below
+  const double x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  const int cx = pcd_cell_axis(x, g.mn[0], g.inv_h, g.G[0]), cy = pcd_cell_axis(y, g.mn[1], g.inv_h, g.G[1]),
+            cz = pcd_cell_axis(z, g.mn[2], g.inv_h, g.G[2]);
+  int cnt = 0;
+  bool settled = false;
+  for (int r = 0; r <= PCD_GRID_RINGS && !settled; ++r) {
+    pcd_ring(g, cx, cy, cz, r, [&](unsigned a, unsigned b) {
+      for (unsigned p = a; p < b; ++p) {
+        const double d2 = pcd_d2(x, y, z, g.sorted + (unsigned long)p * 3);
+        const int j = g.orig[p];
+        if (cnt < k || d2 < ld[cnt - 1][tid] || (d2 == ld[cnt - 1][tid] && j < li[cnt - 1][tid])) {
+          int pos = cnt < k ? cnt++ : k - 1;
+          while (pos > 0 && (ld[pos - 1][tid] > d2 || (ld[pos - 1][tid] == d2 && li[pos - 1][tid] > j))) {
+            ld[pos][tid] = ld[pos - 1][tid]; li[pos][tid] = li[pos - 1][tid]; --pos;
+          }
+          ld[pos][tid] = d2; li[pos][tid] = j;
+        }
+      }
+    });
+    const bool all = pcd_ring_covers(g, cx, cy, cz, r);
+    settled = cnt == k && (all || ld[k - 1][tid] < pcd_ring_bound2(g, r));
+    if (all) break;
+  }
+  if (!settled) { left[atomicAdd(n_left, 1u)] = (int)i; return; }
+  if (nbr) for (int j = 0; j < k; ++j) nbr[i * k + j] = li[j][tid];
+  pcd_list_normal(pts, li, tid, k, normals + i * 3);
+}
+
+__global__ __launch_bounds__(PB) void k_pcd_gather64(const double* src, const int* list, long nl, double* out) {
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < nl; i += (long)gridDim.x * PB) {
+    const long j = list[i];
+    out[i * 3] = src[j * 3]; out[i * 3 + 1] = src[j * 3 + 1]; out[i * 3 + 2] = src[j * 3 + 2];
+  }
+}
+__global__ __launch_bounds__(PB) void k_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist) {
+  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < nl; i += (long)gridDim.x * PB) {
+    const long j = list[i];
+    idx[j] = idx_l[i]; dist[j] = dist_l[i];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------- launchers
 static int pcd_blocks(long n) { long b = (n + PB - 1) / PB; return (int)(b > PCD_MAXB ? PCD_MAXB : (b < 1 ? 1 : b)); }
 
@@ -474,7 +697,7 @@ void launch_pcd_move(const double* q, long n, const double* T44, double* out, hi
 }
 void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr, double* normals, hipStream_t s) {
   const int k = (int)(n < knn ? n : knn);
-  hipLaunchKernelGGL(k_pcd_knn, dim3((unsigned)((n + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, pts, n, k, nbr, normals);
+  hipLaunchKernelGGL(k_pcd_knn, dim3((unsigned)((n + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, pts, n, k, (const int*)nullptr, n, nbr, normals);
 }
 void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s) {
   hipLaunchKernelGGL(k_pcd_normal_dot, dim3(pcd_blocks(n)), dim3(PB), 0, s, nq, nt, idx, n, dot);
@@ -493,4 +716,53 @@ void launch_pcd_gather(const float* src, const long* idx, long ns, float* out32,
 void launch_pcd_sum(const double* v, long n, double* part, int* nb, hipStream_t s) {
   *nb = pcd_blocks(n);
   hipLaunchKernelGGL(k_pcd_sum, dim3(*nb), dim3(PB), 0, s, v, n, part);
+}
+
+// ------------------------------------------------------------------------------------------------------------- grid launchers
+void launch_pcd_grid_bbox(const double* t, long n, double* part, double* box, hipStream_t s) {
+  const int nb = pcd_blocks(n);
+  hipLaunchKernelGGL(k_pcd_grid_bbox, dim3(nb), dim3(PB), 0, s, t, n, 0, part);
+  hipLaunchKernelGGL(k_pcd_grid_bbox, dim3(1), dim3(PB), 0, s, (const double*)part, (long)nb, 1, box);
+}
+
+// host: the rule for h lives in pcd_host.h (plain C++, tested under sanitizers on the host)
+void pcd_grid_shape(const double* box, long n, PcdGrid* g) {
+  g->n = n; g->n_in = (long)box[6];
+  pcd_host::grid_shape(box, g->n_in, PCD_GRID_OCC, PCD_GRID_MAX_CELLS, g->mn, &g->h, g->G, &g->cells);
+  g->inv_h = 1.0 / g->h;
+}
+
+void launch_pcd_grid_build(const double* t, long n, const PcdGrid& g, unsigned* counts, unsigned* start, unsigned* bsum, int* cell, double* sorted,
+                           int* orig, hipStream_t s) {
+  const GridDev d = grid_dev(g);
+  (void)hipMemsetAsync(counts, 0, (size_t)g.cells * sizeof(unsigned), s);
+  (void)hipMemsetAsync(bsum, 0, (PCD_MAXB + 2) * sizeof(unsigned), s);
+  hipLaunchKernelGGL(k_pcd_grid_count, dim3(pcd_blocks(n)), dim3(PB), 0, s, t, n, d, counts, cell);
+  const int nb = pcd_blocks(g.cells);
+  const long chunk = ((g.cells + nb - 1) / nb + PB - 1) / PB * PB;      // a multiple of PB; nb * chunk >= cells
+  hipLaunchKernelGGL(k_pcd_grid_scan_sums, dim3(nb), dim3(PB), 0, s, (const unsigned*)counts, g.cells, chunk, bsum);
+  hipLaunchKernelGGL(k_pcd_offsets, dim3(1), dim3(PB), 0, s, bsum, nb);
+  hipLaunchKernelGGL(k_pcd_grid_scan_cells, dim3(nb), dim3(PB), 0, s, (const unsigned*)counts, g.cells, chunk, (const unsigned*)bsum, start);
+  hipLaunchKernelGGL(k_pcd_grid_scatter, dim3(pcd_blocks(n)), dim3(PB), 0, s, t, n, (const int*)cell, (const unsigned*)start, counts, sorted, orig);
+}
+void launch_pcd_nn_grid(const double* q, long nq, const double* T44, const PcdGrid& g, int* idx, double* dist, int* left, unsigned* n_left,
+                        hipStream_t s) {
+  (void)hipMemsetAsync(n_left, 0, sizeof(unsigned), s);
+  hipLaunchKernelGGL(k_pcd_nn_grid, dim3((unsigned)((nq + PB - 1) / PB)), dim3(PB), 0, s, q, nq, T44, grid_dev(g), g.n_in, idx, dist, left, n_left);
+}
+void launch_pcd_knn_grid(const PcdGrid& g, int knn, int* nbr, double* normals, int* left, unsigned* n_left, hipStream_t s) {
+  const int k = (int)(g.n < knn ? g.n : knn);
+  (void)hipMemsetAsync(n_left, 0, sizeof(unsigned), s);
+  hipLaunchKernelGGL(k_pcd_knn_grid, dim3((unsigned)((g.n + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, g.pts, g.n, k, grid_dev(g), nbr, normals, left,
+                     n_left);
+}
+void launch_pcd_knn_normals_list(const double* pts, long n, int knn, const int* list, long nl, int* nbr, double* normals, hipStream_t s) {
+  const int k = (int)(n < knn ? n : knn);
+  hipLaunchKernelGGL(k_pcd_knn, dim3((unsigned)((nl + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, pts, n, k, list, nl, nbr, normals);
+}
+void launch_pcd_gather64(const double* src, const int* list, long nl, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_gather64, dim3(pcd_blocks(nl)), dim3(PB), 0, s, src, list, nl, out);
+}
+void launch_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist, hipStream_t s) {
+  hipLaunchKernelGGL(k_pcd_nn_scatter, dim3(pcd_blocks(nl)), dim3(PB), 0, s, list, nl, idx_l, dist_l, idx, dist);
 }

@@ -1,6 +1,7 @@
 // Host half of the point-to-point ICP of ug_eval_pcd: the 3x3 singular value decomposition as a one-sided Jacobi, the
-// Umeyama rotation (no scaling) from the Kabsch sums of kernels/pcd.hip, and 4x4 products.  Plain C++ with no GPU dependency: the stand-alone
-// test program of tests/test_pcd_cpu.py compiles it with the host compiler and sanitizers.
+// Umeyama rotation (no scaling) from the Kabsch sums of kernels/pcd.hip, and 4x4 products; and the shape of the search grid of section 20.  Plain
+// C++ with no GPU dependency: the stand-alone test programs of tests/test_pcd_cpu.py and tests/test_pcd_grid_cpu.py compile it with the host
+// compiler and sanitizers.
 #pragma once
 #include <math.h>
 
@@ -98,6 +99,53 @@ inline void mul44(const double* A, const double* B, double* C) {      // C = A B
       for (int k = 0; k < 4; ++k) v += A[r * 4 + k] * B[k * 4 + c];
       C[r * 4 + c] = v;
     }
+}
+
+// The uniform search grid of DESIGN.md section 20: cell edge h and cells per axis G from the bounding box of the n_in finite points
+// (box = min xyz, max xyz).  An axis is thick when its extent is at least h; over the d thick axes h solves
+// n_in * h^d = occ * (product of their extents), i.e. occ points per cell for a cloud that fills its box along those axes.  Starting from the
+// axes of positive extent, an axis thinner than the h it gives is dropped and h is solved again (at most three times); a cloud with no thick
+// axis (one point, all points equal) gets one cell.  Cells per axis are floor(extent / h) + 1, so an extent of 0 is one cell, and h grows by
+// a quarter at a time until the product respects max_cells.  No point (n_in <= 0): one cell at the origin with h = 1.
+inline void grid_shape(const double* box, long n_in, double occ, long max_cells, double mn[3], double* h_out, int G[3], long* cells_out) {
+  for (int a = 0; a < 3; ++a) { mn[a] = 0; G[a] = 1; }
+  *h_out = 1.0; *cells_out = 1;
+  if (n_in <= 0) return;
+  double e[3], L = 0;
+  bool thick[3];
+  for (int a = 0; a < 3; ++a) {
+    mn[a] = box[a];
+    e[a] = box[3 + a] - box[a];
+    if (!(e[a] >= 0)) e[a] = 0;
+    if (!(e[a] <= 1.7e308)) e[a] = 1.7e308;      // the difference of two finite coordinates may overflow
+    thick[a] = e[a] > 0;
+    L = e[a] > L ? e[a] : L;
+  }
+  double h = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    int d = 0;
+    double lg = log(occ / (double)n_in);
+    for (int a = 0; a < 3; ++a) if (thick[a]) { ++d; lg += log(e[a]); }
+    if (d == 0) { h = 0; break; }
+    h = exp(lg / d);
+    bool dropped = false;
+    for (int a = 0; a < 3; ++a) if (thick[a] && e[a] < h) { thick[a] = false; dropped = true; }
+    if (!dropped) break;
+  }
+  if (!(h > 0)) h = L > 0 ? 2.0 * L : 1.0;
+  if (!(h >= 1e-300)) h = 1e-300;                  // 1 / h stays finite
+  if (!(h <= 1e300)) h = 1e300;
+  for (;;) {
+    double cells = 1;
+    for (int a = 0; a < 3; ++a) {
+      const double c = floor(e[a] / h) + 1.0;
+      G[a] = c < 16777217.0 ? (int)c : 16777217;
+      cells *= (double)G[a];
+    }
+    if (cells <= (double)max_cells) { *cells_out = (long)cells; break; }
+    h *= 1.25;
+  }
+  *h_out = h;
 }
 
 }  // namespace pcd_host

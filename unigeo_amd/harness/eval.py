@@ -72,7 +72,8 @@ def parse_pcd_eval_config(config):
     """``eval_pcd`` (the reference's key, eval.py:66-83): ``pcd_downsample_num`` (default -1: every masked point), optional ``threshold``
     (ICP correspondence distance, default 0.1) and ``seed`` (default 0; a clip draws with ``seed + data index``) -> dict, or ``None`` without
     the key.  ``sampling`` is ``random`` (default: the seeded draw) or ``fps`` (farthest-point sampling; ``seed`` is not
-    used); anything else, and ``vis_pcd`` without ``eval_pcd``, is a ``ValueError``."""
+    used).  ``search`` is ``brute`` (default) or ``grid`` (the exact search through a uniform grid, DESIGN.md section 20: the same numbers, and the
+    one way to run ``pcd_downsample_num: -1`` on a full clip).  Anything else, and ``vis_pcd`` without ``eval_pcd``, is a ``ValueError``."""
     if "eval_pcd" not in config:
         if config.get("vis_pcd"):
             raise ValueError("vis_pcd needs eval_pcd: the point clouds it writes are the ones eval_pcd aligns")
@@ -81,8 +82,11 @@ def parse_pcd_eval_config(config):
     sampling = cfg.get("sampling", "random")
     if sampling not in ("random", "fps"):
         raise ValueError(f"eval_pcd.sampling must be 'random' or 'fps', not {sampling!r}")
+    search = cfg.get("search", "brute")
+    if search not in ("brute", "grid"):
+        raise ValueError(f"eval_pcd.search must be 'brute' or 'grid', not {search!r}")
     return {"downsample_num": int(cfg.get("pcd_downsample_num", -1)), "threshold": float(cfg.get("threshold", 0.1)), "seed": int(cfg.get("seed", 0)),
-            "sampling": sampling}
+            "sampling": sampling, "search": search}
 
 
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
@@ -159,7 +163,7 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
                 metric.update(normal_evaluation(output["pred_normals"], gt["gt_normals"], custom_mask=gt["gt_masks"]))
         if pcd_cfg is not None:
             kw = {"threshold": pcd_cfg["threshold"], "downsample_num": pcd_cfg["downsample_num"], "seed": pcd_cfg["seed"] + data_idx,
-                  "sampling": pcd_cfg["sampling"]}
+                  "sampling": pcd_cfg["sampling"], "search": pcd_cfg["search"]}
             pts = output.get("pred_world_pts")
             if hasattr(pts, "detach"):
                 pts = pts.detach().cpu().numpy()

@@ -261,14 +261,83 @@ def knn_brute(pts, k, chunk=1 << 22):
     return out
 
 
-def knn_normals(pts, knn=30):
+def _tree():
+    try:
+        from scipy.spatial import cKDTree
+    except ImportError:
+        return None
+    return cKDTree
+
+
+_TREE_SLACK = 1.0 - 1e-9      # the tree's own distances carry a few float64 roundings; a row must clear its radius by far more than that
+
+
+def nn_grid(q, t, extra=16):
+    """``nn_brute(q, t)`` exactly, from a host-side index: ``extra`` candidates per query from a k-d tree over the
+    targets, re-ranked by ``(dx*dx + dy*dy) + dz*dz`` and the index as ``nn_brute`` ranks them.  A row is accepted when its winner
+    lies inside the tree's radius (the distance of the farthest candidate, less a slack), so that no target outside the candidates can
+    beat or tie it; every other row (a tie that fills the candidates, a non-finite query) is redone by ``nn_brute``.  Without scipy, or
+    with a non-finite target, this is ``nn_brute``."""
+    q, t = np.asarray(q, np.float64).reshape(-1, 3), np.asarray(t, np.float64).reshape(-1, 3)
+    tree = _tree()
+    if tree is None or len(q) == 0 or len(t) == 0 or not np.isfinite(t).all():      # numpy's argmin stops at a NaN distance: leave such a target to it
+        return nn_brute(q, t)
+    fin = np.arange(len(t))
+    idx, dist = np.zeros(len(q), np.int64), np.full(len(q), np.inf)
+    ok = np.zeros(len(q), bool)
+    rows = np.nonzero(np.isfinite(q).all(1))[0]
+    if len(rows):
+        kk = min(extra, len(fin))
+        dt, it = tree(t[fin]).query(q[rows], k=kk)
+        dt, it = dt.reshape(len(rows), kk), fin[it.reshape(len(rows), kk)]
+        d = q[rows][:, None, :] - t[it]
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        o = np.lexsort((it, d2), axis=1)[:, 0]
+        ar = np.arange(len(rows))
+        best, bi = d2[ar, o], it[ar, o]
+        radius = dt[:, -1] * _TREE_SLACK
+        good = np.isfinite(best) & ((kk == len(fin)) | (best < radius * radius))
+        idx[rows[good]], dist[rows[good]] = bi[good], np.sqrt(best[good])
+        ok[rows[good]] = True
+    if not ok.all():
+        dist[~ok], idx[~ok] = nn_brute(q[~ok], t)
+    return dist, idx
+
+
+def knn_grid(pts, k, extra=16):
+    """``knn_brute(pts, k)`` exactly, from the same index: ``min(k, n) + extra`` candidates per point, re-ranked by (squared distance,
+    index); a row is accepted when its last kept neighbour lies inside the tree's radius, else it is redone by brute force.  A cloud with
+    a non-finite point, and a host without scipy, go to ``knn_brute``."""
+    pts = np.asarray(pts, np.float64).reshape(-1, 3)
+    n = len(pts)
+    k = min(k, n)
+    tree = _tree()
+    if tree is None or n == 0 or not np.isfinite(pts).all():
+        return knn_brute(pts, k)
+    kk = min(k + extra, n)
+    dt, it = tree(pts).query(pts, k=kk)
+    dt, it = dt.reshape(n, kk), it.reshape(n, kk)
+    d = pts[:, None, :] - pts[it]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    o = np.lexsort((it, d2), axis=1)[:, :k]
+    out = np.take_along_axis(it, o, 1).astype(np.int64)
+    radius = dt[:, -1] * _TREE_SLACK
+    last = np.take_along_axis(d2, o[:, -1:], 1)[:, 0]
+    good = (kk == n) | (last < radius * radius)
+    for r in np.nonzero(~good)[0]:
+        out[r] = np.argsort(_d2(pts[r:r + 1], pts)[0], kind="stable")[:k]
+    return out
+
+
+def knn_normals(pts, knn=30, knn_fn=None):
     """Open3D's ``estimate_normals()`` with its default KNN search: the unit eigenvector of the smallest eigenvalue of the float64 covariance
-    of the ``min(knn, n)`` nearest points about their mean; ``(0, 0, 1)`` with fewer than 3 points.  The sign is free."""
+    of the ``min(knn, n)`` nearest points about their mean; ``(0, 0, 1)`` with fewer than 3 points.  The sign is free.  ``knn_fn`` finds the
+    lists (default ``knn_brute``)."""
     pts = np.asarray(pts, np.float64)
     n = len(pts)
     if min(n, knn) < 3:
         return np.tile(np.array([0.0, 0.0, 1.0]), (n, 1))
-    nb = pts[knn_brute(pts, knn)]
+    nb = pts[(knn_fn or knn_brute)(pts, knn)]
     c = nb - nb.mean(1, keepdims=True)
     cov = np.einsum("nki,nkj->nij", c, c) / nb.shape[1]
     return np.linalg.eigh(cov)[1][:, :, 0]
@@ -330,8 +399,9 @@ def pcd_scores(gt_pts, pred_pts, gt_normals, pred_normals, nn=_nn):
             "acc_med": float(np.median(d1)), "comp_med": float(np.median(d2)), "nc1_med": float(np.median(n1)), "nc2_med": float(np.median(n2))}
 
 
-def pcd_metrics_from_clouds(p, g, threshold=0.1, knn=30, max_iteration=30, nn=_nn):
-    """ICP, normals and scores of two aligned float32 clouds ``[n,3]`` -> the eight keys plus the ICP record; NaN scores for no point."""
+def pcd_metrics_from_clouds(p, g, threshold=0.1, knn=30, max_iteration=30, nn=_nn, knn_fn=None):
+    """ICP, normals and scores of two aligned float32 clouds ``[n,3]`` -> the eight keys plus the ICP record; NaN scores for no point.
+    ``nn`` / ``knn_fn`` do the searches (defaults: the k-d tree or ``nn_brute``, and ``knn_brute``)."""
     p64, g64 = np.asarray(p, np.float32).astype(np.float64), np.asarray(g, np.float32).astype(np.float64)
     if len(p64) == 0:
         res = {k: math.nan for k in PCD_KEYS}
@@ -339,7 +409,7 @@ def pcd_metrics_from_clouds(p, g, threshold=0.1, knn=30, max_iteration=30, nn=_n
         return res
     T, it, fit, rmse, hist = icp_point_to_point(p64, g64, threshold, max_iteration, nn)
     moved = _move(T, p64)
-    res = pcd_scores(g64, moved, knn_normals(g64, knn), knn_normals(moved, knn), nn)
+    res = pcd_scores(g64, moved, knn_normals(g64, knn, knn_fn), knn_normals(moved, knn, knn_fn), nn)
     res.update(icp_iterations=it, icp_fitness=fit, icp_rmse=rmse, transformation=T, icp_history=hist)
     return res
 
@@ -388,15 +458,21 @@ def pcd_sample_indices_fps(p, g, downsample_num):
     return None
 
 
-def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30, sampling="random"):
+def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30, sampling="random",
+                   search="brute"):
     """``pcd_evaluation`` of the reference (``metrics/eval_pcd.py:10-168``) -> dict: masked selection in pixel order,
     ``pcd_align``, seeded downsampling (the reference draws from the unseeded global generator and raises when ``downsample_num`` exceeds the
     point count; here that uses every point), point-to-point ICP from the identity, KNN normals, ``accuracy`` / ``completion``.
     ``pred_pcd`` / ``gt_pcd`` are ``(points float32 [n,3], colours float32 [n,3])`` taken before ICP (zeros without ``rgbs``).
     ``sampling="fps"`` ignores ``seed``, samples each aligned cloud with ``pcd_fps_indices`` and adds ``pred_idx`` /
-    ``gt_idx``, the picked positions among the masked points; each cloud then carries the colours of its own points."""
+    ``gt_idx``, the picked positions among the masked points; each cloud then carries the colours of its own points.
+    ``search="grid"`` does every search with ``nn_grid`` / ``knn_grid``, which return what ``nn_brute`` / ``knn_brute``
+    return; ``search="brute"`` keeps the default searches."""
     if sampling not in ("random", "fps"):
         raise ValueError(f"pcd_evaluation: sampling must be 'random' or 'fps', not {sampling!r}")
+    if search not in ("brute", "grid"):
+        raise ValueError(f"pcd_evaluation: search must be 'brute' or 'grid', not {search!r}")
+    how = {"nn": nn_grid, "knn_fn": knn_grid} if search == "grid" else {}
     m = _np(masks).reshape(-1) > 0
     p = _np(pred_pts).astype(np.float32).reshape(-1, 3)[m]
     g = _np(gt_pts).astype(np.float32).reshape(-1, 3)[m]
@@ -408,14 +484,14 @@ def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample
         pair = pcd_sample_indices_fps(p, g, downsample_num)
         ip, ig = pair if pair is not None else (np.arange(len(p), dtype=np.int64),) * 2
         p, g, cp, cg = (p, g, col, col.copy()) if pair is None else (p[ip], g[ig], col[ip], col[ig])
-        res = pcd_metrics_from_clouds(p, g, threshold, knn, max_iteration)
+        res = pcd_metrics_from_clouds(p, g, threshold, knn, max_iteration, **how)
         res.update(n_points=len(p), pred_scale=float(scal[0]), gt_scale=float(scal[1]), pred_shift_z=float(scal[2]), gt_shift_z=float(scal[3]),
                    pred_pcd=(p, cp), gt_pcd=(g, cg), pred_idx=ip, gt_idx=ig)
         return res
     idx = pcd_sample_indices(len(p), downsample_num, seed)
     if idx is not None:
         p, g, col = p[idx], g[idx], col[idx]
-    res = pcd_metrics_from_clouds(p, g, threshold, knn, max_iteration)
+    res = pcd_metrics_from_clouds(p, g, threshold, knn, max_iteration, **how)
     res.update(n_points=len(p), pred_scale=float(scal[0]), gt_scale=float(scal[1]), pred_shift_z=float(scal[2]), gt_shift_z=float(scal[3]),
                pred_pcd=(p, col), gt_pcd=(g, col.copy()))
     return res
