@@ -265,6 +265,32 @@ int ug_eval_pcd_ex(ug_ctx* ctx, const float* pred_pts /* NULL: resident points *
                    float* pred_cloud_out /* or NULL */, float* gt_cloud_out /* or NULL */, long* pred_idx_out /* or NULL */,
                    long* gt_idx_out /* or NULL */, long* search_stats /* [8] or NULL */);
 
+/* Focal, camera poses and depth from world point maps: what the reference's point-map plugins take from
+ * solve_depth_and_camera_from_3d_points (metrics/utils.py:68-160, called from model/spann3r.py:43; kernels/pointmap.hip).
+ * The arithmetic is that of harness/pointmap.py in unfused float64, every sum in a fixed order; two calls return the same bytes.
+ * ug_pointmap_focal: estimate_focal_knowing_depth(pts[0:1], pp, 'weiszfeld') (metrics/utils.py:93-115) of pts0 float32 [H,W,3], the point map of
+ *   the frame whose camera is the world frame; pp = (cx, cy), the reference passes (W/2, H/2).  xy = (x/z, y/z) with non-finite values set to 0,
+ *   pixel grid 0..W-1, 0..H-1 minus pp, f0 = mean(xy.px) / mean(xy.xy), ten steps f = mean(w xy.px) / mean(w xy.xy) with
+ *   w = 1 / max(|px - f xy|, 1e-8), means over all pixels, clipped below at 0.  The reference runs this in float32.
+ * ug_pointmap_poses: in place of cv2.solvePnPRansac (random samples) a deterministic solver.  pts float32 [T,H,W,3] world points; mask uint8
+ *   [T,H,W] (> 0 keeps, may be NULL); a pixel is valid when its three coordinates are finite and the mask keeps it.  Unit rays
+ *   b = normalize(K^-1 (col, row, 1)), K from focal and (cx, cy).  Per frame the orthogonal (object-space) iteration of Lu, Hager and Mjolsness
+ *   with V = b b^T: t = (1/n) (I - mean V)^-1 sum (V - I) R X, q = V (R X + t), next R = Kabsch of the centred X onto the centred q; frame 0 starts
+ *   from the identity, every other frame from the frame before.  A fit ends when E = sum |(I - V)(R X + t)|^2 changes by less than a relative
+ *   1e-12, or E or its change is at most 1e-6 sum (2^-24 |X|)^2, or after max_iter iterations.  Then the pixels whose reprojection error exceeds
+ *   reproj_px or whose camera z <= 0 are dropped and the fit continues from the current pose, until no membership changes or max_rounds trims
+ *   were made (a trim that would leave fewer than 4 pixels is not made).  extrinsics_out [T,16] row-major world to camera (cam2world is its
+ *   inverse); depth_out float32 [T,H,W] = z of R X + t rounded once, 0 at invalid pixels; frame_stats_out [T,3] = inlier count, iterations (all
+ *   fits of the frame), rms reprojection error of the inliers in pixels; inliers_out uint8 [T,H,W] (may be NULL) the final inlier set.
+ * Errors (ug_last_error; the context stays usable): a NULL pts, opts or required output; T, H or W <= 0, or H * W >= 2^31; a focal that is not
+ *   positive and finite; reproj_px <= 0, max_iter < 1 or max_rounds < 0; a frame with fewer than 4 valid pixels (the frame is named). */
+typedef struct { double reproj_px; int max_iter; int max_rounds; } ug_pointmap_opts;
+void ug_pointmap_opts_default(ug_pointmap_opts* o);     /* 8.0 (cv2's default), 300, 5 */
+int ug_pointmap_focal(ug_ctx* ctx, const float* pts0, int H, int W, double cx, double cy, double* focal_out);
+int ug_pointmap_poses(ug_ctx* ctx, const float* pts, const unsigned char* mask /* or NULL */, int T, int H, int W, double focal, double cx,
+                      double cy, const ug_pointmap_opts* opts, double* extrinsics_out, float* depth_out, double* frame_stats_out,
+                      unsigned char* inliers_out /* or NULL */);
+
 /* Visualisation panels composed on the device: replaces save_depth_normal_maps / colorize / colorize_np (utils/vis_utils.py:38-84,139-199, as
  * eval.py:58-62 calls them under `vis_depth: True`).  One image per frame, uint8 [T,H,Wp,3] row-major,
  *   Wp = (rgb ? W : 0) + W + W + (cbar ? 5 + Wc : 0):   rgb | normals | coloured depth | 5 black columns | colour bar.

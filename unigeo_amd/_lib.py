@@ -26,6 +26,7 @@ EXPORTS = [
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
+    "ug_pointmap_opts_default", "ug_pointmap_focal", "ug_pointmap_poses",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
@@ -61,6 +62,10 @@ class DepthEvalOptsC(C.Structure):
 
 class PcdOptsC(C.Structure):
     _fields_ = [("threshold", C.c_float), ("max_iteration", C.c_int), ("knn", C.c_int)]
+
+
+class PointmapOptsC(C.Structure):
+    _fields_ = [("reproj_px", C.c_double), ("max_iter", C.c_int), ("max_rounds", C.c_int)]
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_ALIGN_* of include/unigeo_hip.h
@@ -138,6 +143,11 @@ def load_library():
     _set_argtypes(lib, {"ug_eval_pcd_ex": [vp, vp, vp, vp, C.c_long, vp, C.c_long, C.POINTER(PcdOptsC), ip, vp, vp, vp, vp, vp, vp],
                         "ug_op_pcd_nn_grid": [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp, vp],
                         "ug_op_pcd_knn_normals_grid": [vp, vp, C.c_long, ip, vp, vp, vp]})
+    _set_argtypes(lib, {"ug_pointmap_opts_default": [C.POINTER(PointmapOptsC)],
+                        "ug_pointmap_focal": [vp, vp, ip, ip, C.c_double, C.c_double, vp],
+                        "ug_pointmap_poses": [vp, vp, vp, ip, ip, ip, C.c_double, C.c_double, C.c_double, C.POINTER(PointmapOptsC), vp, vp, vp, vp]})
+    if hasattr(lib, "ug_pointmap_opts_default"):
+        lib.ug_pointmap_opts_default.restype = None
     _set_argtypes(lib, {"ug_vis_depth_range": [vp, vp, C.c_long, vp],
                         "ug_vis_panels": [vp, vp, vp, vp, ip, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]})
     _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
@@ -682,6 +692,44 @@ class Engine:
                    transformation=out[12:28].reshape(4, 4).copy(), pred_scale=float(out[28]), gt_scale=float(out[29]),
                    pred_shift_z=float(out[30]), gt_shift_z=float(out[31]))
         return res
+
+    # ---- focal, poses and depth from world point maps
+    def pointmap_focal(self, pts0, pp=None):
+        """``pointmap_focal`` of ``harness/pointmap.py`` on the device (``ug_pointmap_focal``): the Weiszfeld focal of the point map ``[H,W,3]`` of
+        the frame whose camera is the world frame; ``pp`` defaults to ``(W/2, H/2)``."""
+        p = _f32(pts0)
+        if p.ndim != 3 or p.shape[-1] != 3:
+            raise ValueError("pointmap_focal: pts0 must be [H,W,3]")
+        H, W = p.shape[:2]
+        cx, cy = (W / 2.0, H / 2.0) if pp is None else (float(pp[0]), float(pp[1]))
+        out = np.zeros(1, np.float64)
+        self._ck(self.lib.ug_pointmap_focal(self.ctx, _ptr(p), H, W, cx, cy, _ptr(out)))
+        return float(out[0])
+
+    def pointmap_poses(self, pts, focal, pp=None, mask=None, reproj_px=None, max_iter=None, max_rounds=None):
+        """``pointmap_poses`` of ``harness/pointmap.py`` on the device (``ug_pointmap_poses``) -> the same dict: ``extrinsics [T,4,4]`` float64
+        world to camera, ``depth [T,H,W]`` float32, ``focal``, per frame ``n_inliers``, ``iterations``, ``reproj_rms``, and ``inliers [T,H,W]``.
+        Options left at ``None`` take the library's defaults (``ug_pointmap_opts_default``)."""
+        p = _f32(pts)
+        if p.ndim != 4 or p.shape[-1] != 3:
+            raise ValueError("pointmap_poses: pts must be [T,H,W,3]")
+        T, H, W = p.shape[:3]
+        cx, cy = (W / 2.0, H / 2.0) if pp is None else (float(pp[0]), float(pp[1]))
+        m = None if mask is None else np.ascontiguousarray((np.asarray(mask).reshape(T, H, W) > 0).astype(np.uint8))
+        o = PointmapOptsC()
+        self.lib.ug_pointmap_opts_default(C.byref(o))
+        if reproj_px is not None:
+            o.reproj_px = float(reproj_px)
+        if max_iter is not None:
+            o.max_iter = int(max_iter)
+        if max_rounds is not None:
+            o.max_rounds = int(max_rounds)
+        ext, depth = np.zeros((T, 4, 4), np.float64), np.zeros((T, H, W), np.float32)
+        stats, inl = np.zeros((T, 3), np.float64), np.zeros((T, H, W), np.uint8)
+        self._ck(self.lib.ug_pointmap_poses(self.ctx, _ptr(p), _ptr(m), T, H, W, float(focal), cx, cy, C.byref(o), _ptr(ext), _ptr(depth),
+                                            _ptr(stats), _ptr(inl)))
+        return {"extrinsics": ext, "depth": depth, "focal": float(focal), "n_inliers": stats[:, 0].astype(np.int64),
+                "iterations": stats[:, 1].astype(np.int64), "reproj_rms": stats[:, 2].copy(), "inliers": inl > 0}
 
     def op_pcd_fps(self, pts, k):
         """Farthest-point sampling of a float32 cloud ``[n,3]`` alone (``pcd_fps_indices`` of ``harness/metrics.py``) ->

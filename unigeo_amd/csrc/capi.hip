@@ -640,6 +640,134 @@ int ug_eval_pcd_ex(ug_ctx* x, const float* pred_pts, const float* gt_pts, const 
   });
 }
 
+// ---------------------------------------------------------------- focal, poses and depth from point maps (kernels/pointmap.hip)
+void ug_pointmap_opts_default(ug_pointmap_opts* o) { o->reproj_px = 8.0; o->max_iter = 300; o->max_rounds = 5; }
+
+int ug_pointmap_focal(ug_ctx* x, const float* pts0, int H, int W, double cx, double cy, double* focal_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pts0 && focal_out, "pts0 and focal_out must not be NULL");
+    UG_REQUIRE(H > 0 && W > 0, "H and W must be positive");
+    const long n = (long)H * W;
+    UG_REQUIRE(n < (1L << 31), "pixel count");
+    float* d = c.ws.get<float>(n * 3); UG_CHECK(hipMemcpy(d, pts0, (size_t)n * 12, hipMemcpyHostToDevice));
+    double* part = c.ws.get<double>(PM_MAXB * 2); double* fz = c.ws.get<double>(1);
+    launch_pm_focal(d, n, PmCam{0.0, cx, cy, W}, 10, part, fz, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    double f = 0;
+    UG_CHECK(hipMemcpy(&f, fz, 8, hipMemcpyDeviceToHost));
+    *focal_out = f > 0.0 ? f : 0.0;      // clip(min = 0); a NaN (no usable pixel) comes out as 0
+  });
+}
+
+// inverse of a 3x3 by the adjugate, as _inv3 of harness/pointmap.py
+static void pm_inv3(const double m[3][3], double o[3][3]) {
+  const double c00 = m[1][1] * m[2][2] - m[1][2] * m[2][1], c01 = m[1][2] * m[2][0] - m[1][0] * m[2][2], c02 = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+  const double det = (m[0][0] * c00 + m[0][1] * c01) + m[0][2] * c02;
+  const double adj[3][3] = {{c00, m[0][2] * m[2][1] - m[0][1] * m[2][2], m[0][1] * m[1][2] - m[0][2] * m[1][1]},
+                            {c01, m[0][0] * m[2][2] - m[0][2] * m[2][0], m[0][2] * m[1][0] - m[0][0] * m[1][2]},
+                            {c02, m[0][1] * m[2][0] - m[0][0] * m[2][1], m[0][0] * m[1][1] - m[0][1] * m[1][0]}};
+  for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) o[r][k] = adj[r][k] / det;
+}
+
+// One fit of the orthogonal iteration over the pixels of `keep`, from pose.R; leaves (R, t) consistent and returns the iterations it took.
+static int pm_fit(Ctx& c, const float* pts, const unsigned char* keep, long n, const PmCam& cam, PmPose& pose, int max_iter, double* part) {
+  int nb = 0;
+  double s0[8];
+  launch_pm_pass0(pts, keep, n, cam, part, &nb, c.stream);
+  UG_CHECK(hipGetLastError());
+  fetch_partial_sums(c, part, nb, s0);
+  const double cnt = s0[0];
+  const double M[3][3] = {{1.0 - s0[1] / cnt, 0.0 - s0[2] / cnt, 0.0 - s0[3] / cnt},
+                          {0.0 - s0[2] / cnt, 1.0 - s0[4] / cnt, 0.0 - s0[5] / cnt},
+                          {0.0 - s0[3] / cnt, 0.0 - s0[5] / cnt, 1.0 - s0[6] / cnt}};
+  double Mi[3][3];
+  pm_inv3(M, Mi);
+  const double floor = (1e-6 * 0x1p-48) * s0[7];      // a millionth of the float32 rounding of the input, sum (2^-24 |X|)^2
+  double prev = -1.0;
+  int it = 1;
+  for (;; ++it) {
+    double sg[3], s[17];
+    launch_pm_pass1(pts, keep, n, cam, pose, part, &nb, c.stream);
+    UG_CHECK(hipGetLastError());
+    fetch_partial_sums(c, part, nb, sg);
+    for (int r = 0; r < 3; ++r) pose.t[r] = ((Mi[r][0] * sg[0] + Mi[r][1] * sg[1]) + Mi[r][2] * sg[2]) / cnt;
+    launch_pm_pass2(pts, keep, n, cam, pose, part, &nb, c.stream);
+    UG_CHECK(hipGetLastError());
+    fetch_partial_sums(c, part, nb, s);
+    const double err = s[16];
+    UG_REQUIRE(err == err, "the object-space error is NaN");
+    if (err <= floor || (prev >= 0.0 && fabs(prev - err) <= std::max(1e-12 * prev, floor)) || it == max_iter) break;
+    double T44[16];
+    pcd_host::umeyama_from_sums(s, T44);      // s = n, sum X, sum q, sum q X^T: the rotation of the centred X onto the centred q
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) pose.R[r * 3 + k] = T44[r * 4 + k];
+    prev = err;
+  }
+  return it;
+}
+
+int ug_pointmap_poses(ug_ctx* x, const float* pts, const unsigned char* mask, int T, int H, int W, double focal, double cx, double cy,
+                      const ug_pointmap_opts* o, double* ext_out, float* depth_out, double* stats_out, unsigned char* inliers_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pts && o, "pts and options must not be NULL");
+    UG_REQUIRE(ext_out && depth_out && stats_out, "extrinsics_out, depth_out and frame_stats_out must not be NULL");
+    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
+    const long n = (long)H * W;
+    UG_REQUIRE(n < (1L << 31), "pixel count");
+    UG_REQUIRE(focal > 0.0 && std::isfinite(focal) && std::isfinite(cx) && std::isfinite(cy), "the focal must be positive and finite");
+    UG_REQUIRE(o->reproj_px > 0.0 && o->max_iter >= 1 && o->max_rounds >= 0, "reproj_px must be positive, max_iter >= 1 and max_rounds >= 0");
+    float* dp = c.ws.get<float>(n * 3);
+    unsigned char* dm = mask ? (unsigned char*)c.ws.alloc(n) : nullptr;
+    unsigned char* valid = (unsigned char*)c.ws.alloc(n);
+    unsigned char* kbuf[2] = {(unsigned char*)c.ws.alloc(n), (unsigned char*)c.ws.alloc(n)};
+    float* dd = c.ws.get<float>(n);
+    double* part = c.ws.get<double>(PM_MAXB * 17);
+    const PmCam cam{focal, cx, cy, W};
+    const double thr2 = o->reproj_px * o->reproj_px;
+    PmPose pose;
+    for (int i = 0; i < 9; ++i) pose.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    for (int i = 0; i < 3; ++i) pose.t[i] = 0.0;
+    for (int f = 0; f < T; ++f) {
+      UG_CHECK(hipMemcpy(dp, pts + (size_t)f * n * 3, (size_t)n * 12, hipMemcpyHostToDevice));
+      if (mask) UG_CHECK(hipMemcpy(dm, mask + (size_t)f * n, n, hipMemcpyHostToDevice));
+      launch_pm_valid(dp, dm, n, valid, c.stream);
+      const unsigned char* keep = valid;      // the first fit takes every valid pixel; their count is the first of the pass-0 sums
+      int nb = 0;
+      double s0[8];
+      launch_pm_pass0(dp, valid, n, cam, part, &nb, c.stream);
+      UG_CHECK(hipGetLastError());
+      fetch_partial_sums(c, part, nb, s0);
+      if (s0[0] < 4.0) {
+        char msg[96]; snprintf(msg, sizeof msg, "ug_pointmap_poses: frame %d has %ld valid pixels; a pose needs at least 4", f, (long)s0[0]);
+        throw std::runtime_error(msg);
+      }
+      int iters = 0;
+      double in3[3] = {0, 0, 0};
+      unsigned char* fresh = kbuf[0];
+      for (int rnd = 0;; ++rnd) {
+        iters += pm_fit(c, dp, keep, n, cam, pose, o->max_iter, part);
+        launch_pm_inliers(dp, valid, keep, n, cam, pose, thr2, fresh, part, &nb, c.stream);
+        UG_CHECK(hipGetLastError());
+        fetch_partial_sums(c, part, nb, in3);
+        if (in3[1] == 0.0 || rnd == o->max_rounds || in3[0] < 4.0) break;
+        keep = fresh;
+        fresh = fresh == kbuf[0] ? kbuf[1] : kbuf[0];
+      }
+      launch_pm_depth(dp, valid, n, pose, dd, c.stream);
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      UG_CHECK(hipMemcpy(depth_out + (size_t)f * n, dd, (size_t)n * 4, hipMemcpyDeviceToHost));
+      if (inliers_out) UG_CHECK(hipMemcpy(inliers_out + (size_t)f * n, fresh, n, hipMemcpyDeviceToHost));
+      double* E = ext_out + (size_t)f * 16;
+      for (int r = 0; r < 3; ++r) { for (int k = 0; k < 3; ++k) E[r * 4 + k] = pose.R[r * 3 + k]; E[r * 4 + 3] = pose.t[r]; }
+      E[12] = 0; E[13] = 0; E[14] = 0; E[15] = 1;
+      stats_out[f * 3] = in3[0]; stats_out[f * 3 + 1] = (double)iters; stats_out[f * 3 + 2] = in3[0] > 0 ? sqrt(in3[2] / in3[0]) : NAN;
+    }
+  });
+}
+
 int ug_eval_normal(ug_ctx* x, const float* pred, const float* gt, const unsigned char* mask, long n, double* out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);

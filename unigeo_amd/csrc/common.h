@@ -363,6 +363,26 @@ void launch_pcd_knn_grid(const PcdGrid& g, int knn, int* nbr /* or NULL */, doub
 void launch_pcd_knn_normals_list(const double* pts, long n, int knn, const int* list, long nl, int* nbr, double* normals, hipStream_t s);
 void launch_pcd_gather64(const double* src, const int* list, long nl, double* out, hipStream_t s);                          // out[i] = src[list[i]]
 void launch_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist, hipStream_t s);
+// focal, poses and depth from world point maps (kernels/pointmap.hip): the arithmetic of harness/pointmap.py.  A frame is
+// n = H * W pixels of pts [n,3]; every sum is per-block fp64 partials (part: PM_MAXB rows) that the caller adds in block order.
+#define PM_MAXB 1024
+struct PmCam { double f, cx, cy; int W; };           // K = [[f, 0, cx], [0, f, cy], [0, 0, 1]], pixel i = (row i / W, column i % W)
+struct PmPose { double R[9], t[3]; };                // world to camera, R row-major
+// the Weiszfeld chain on the device: fz[0] = the focal after the closed-form start and `steps` reweighting steps; part [PM_MAXB * 2]
+void launch_pm_focal(const float* pts, long n, PmCam cam, int steps, double* part, double* fz, hipStream_t s);
+// valid[i] = all three coordinates finite and (mask NULL or mask[i] > 0)
+void launch_pm_valid(const float* pts, const unsigned char* mask, long n, unsigned char* valid, hipStream_t s);
+// per inlier set: n, the six entries of sum b b^T (xx xy xz yy yz zz), sum |X|^2 -> part [nb * 8]
+void launch_pm_pass0(const float* pts, const unsigned char* keep, long n, PmCam cam, double* part, int* nb, hipStream_t s);
+// sum (b b^T - I) R X -> part [nb * 3]
+void launch_pm_pass1(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part, int* nb, hipStream_t s);
+// q = b b^T (R X + t): n, sum X (3), sum q (3), sum q X^T (9, row = q), the object-space error sum |R X + t - q|^2 -> part [nb * 17]
+void launch_pm_pass2(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part, int* nb, hipStream_t s);
+// keep_new[i] = valid, z > 0 and squared reprojection error <= thr2; the count, how many differ from keep, the sum of the kept errors -> part [nb * 3]
+void launch_pm_inliers(const float* pts, const unsigned char* valid, const unsigned char* keep, long n, PmCam cam, PmPose pose, double thr2,
+                       unsigned char* keep_new, double* part, int* nb, hipStream_t s);
+// depth[i] = (float) z of R X + t, 0 where not valid
+void launch_pm_depth(const float* pts, const unsigned char* valid, long n, PmPose pose, float* depth, hipStream_t s);
 // depth / normal visualisation panels (kernels/vis.hip); part: 2 * 1024 floats of scratch, out2 (device) = (vmin, vmax)
 void launch_vis_range(const float* x, long n, float* part, float* out2, hipStream_t s);
 void launch_vis_panel(const float* rgb, const float* normals, const float* depth, const float* lut, const float* cbar, unsigned char* out, int T,

@@ -1,17 +1,21 @@
 """The evaluation loop - mirrors ``/root/reference/eval.py:10-99`` and ``configs/config_utils.py:3-35``.
 
-Differences kept deliberately small: the YAML path is an argument instead of being hard-coded (eval.py:11),
-dataset / model classes can be passed as objects, and the camera-pose branch (its inputs are not produced by the
-DepthCrafter / StableNormal plugins) is not reproduced.  ``vis_depth: True`` writes the reference's
+Differences kept deliberately small: the YAML path is an argument instead of being hard-coded (eval.py:11) and
+dataset / model classes can be passed as objects.  ``vis_depth: True`` writes the reference's
 depth / normal panels (eval.py:58-62; ``harness/vis.py``).  ``eval_pcd`` (eval.py:66-83) scores
 the model's world points, or those of its aligned depth, against the ground-truth cloud.
+``eval_camera`` (eval.py:85-95) scores the model's camera poses, or those recovered from its world points, with ATE and
+RPE (``harness/camera.py``, ``harness/pointmap.py``); the DepthCrafter / StableNormal plugins return
+neither, so a configuration that asks them for it is an error at the first clip.
 """
 import importlib
 import os
 
 import numpy as np
 
+from .camera import CAMERA_KEYS, camera_pose_evaluation, save_camera_trajectories
 from .io_utils import prepare_gt_label
+from .pointmap import poses_from_pointmap
 from .vis import save_depth_normal_maps, write_ply
 from .metrics import (DEPTH_ALIGNMENTS, PCD_KEYS, MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
                       pcd_evaluation, world_points_from_depth)
@@ -89,8 +93,29 @@ def parse_pcd_eval_config(config):
             "sampling": sampling, "search": search}
 
 
+CAMERA_EVAL_KEYS = ("metric_names", "reproj_px", "focal")
+
+
+def parse_camera_eval_config(config):
+    """``eval_camera`` (the reference's key, eval.py:85-95): optional ``reproj_px`` (the trim threshold of the pose recovery from point maps,
+    default 8.0) and ``focal`` (given: the focal step is skipped) -> dict, or ``None`` without the key.  An unknown key, a value that is not a
+    positive number, and ``vis_camera`` without ``eval_camera`` are a ``ValueError``."""
+    if "eval_camera" not in config:
+        if config.get("vis_camera"):
+            raise ValueError("vis_camera needs eval_camera: the trajectories it writes are the ones eval_camera scores")
+        return None
+    cfg = config["eval_camera"] or {}
+    unknown = sorted(set(cfg) - set(CAMERA_EVAL_KEYS))
+    if unknown:
+        raise ValueError(f"eval_camera: unknown key(s) {unknown}; known: {list(CAMERA_EVAL_KEYS)}")
+    out = {"reproj_px": float(cfg.get("reproj_px", 8.0)), "focal": None if cfg.get("focal") is None else float(cfg["focal"])}
+    if not out["reproj_px"] > 0 or (out["focal"] is not None and not out["focal"] > 0):
+        raise ValueError("eval_camera: reproj_px and focal must be positive")
+    return out
+
+
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
-             device_metrics=False, models=None):
+             device_metrics=False, models=None, engine=None):
     """Run the reference's per-clip loop.  With ``world > 1`` this rank only evaluates clips
     ``rank, rank+world, ...`` (clips are independent samples); rows are merged by the caller.
     ``device_metrics=True`` evaluates depth / normal metrics on the GPU against the outputs still resident in HBM
@@ -114,10 +139,18 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     ``device_metrics=True``), against ``gt_world_pts`` on ``gt_masks`` through ``pcd_evaluation`` / ``ug_eval_pcd``
     (``sampling: fps``: farthest-point sampling of each cloud, ``ug_eval_pcd_fps``).  ``vis_pcd: True`` writes
     ``save_dir/pcd_{seq}/pred.ply`` and ``gt.ply`` (the aligned clouds before ICP).  ``vis_pcd`` without ``eval_pcd``, or a clip without
-    ``intrinsics`` when the points have to come from the depth, raises ``ValueError`` before the first clip runs."""
+    ``intrinsics`` when the points have to come from the depth, raises ``ValueError`` before the first clip runs.
+    ``eval_camera`` (eval.py:85-95) adds ``ATE / RPE trans / RPE rot`` through ``camera_pose_evaluation``
+    (``harness/camera.py``): of the model's ``pred_poses`` when it returns them; else of the poses recovered from its ``pred_world_pts``
+    (``harness/pointmap.py``; on the device through ``ug_pointmap_focal`` / ``ug_pointmap_poses`` under ``device_metrics=True``, with the
+    model's own engine or with ``engine=`` for a model that has none); a model that returns neither raises a ``ValueError`` that names the
+    clip and the plugin.  Optional keys ``eval_camera.reproj_px`` and ``eval_camera.focal``; an unknown key raises before the first clip.
+    ``vis_camera: True`` writes ``save_dir/camera_{seq}/pred_traj.txt``, ``gt_traj.txt`` (TUM format) and, with matplotlib, ``traj.png``;
+    without ``eval_camera`` it is a ``ValueError``.  A configuration without ``eval_camera`` gives the rows and bytes it gave before."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
     coord = parse_depth_coord(config)
     pcd_cfg = parse_pcd_eval_config(config)
+    cam_cfg = parse_camera_eval_config(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
     if dataset is None:
         dataset = import_class_from_module("unigeo_amd.harness", config["dataset"])(**parse_dataset_config(config))
@@ -183,6 +216,17 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
                 os.makedirs(pcd_dir, exist_ok=True)
                 write_ply(os.path.join(pcd_dir, "pred.ply"), *res["pred_pcd"])
                 write_ply(os.path.join(pcd_dir, "gt.ply"), *res["gt_pcd"])
+        if cam_cfg is not None:
+            poses = output.get("pred_poses")
+            if poses is None and output.get("pred_world_pts") is not None:
+                pm_eng = eng if eng is not None else (engine if device_metrics else None)
+                poses = poses_from_pointmap(output["pred_world_pts"], focal=cam_cfg["focal"], reproj_px=cam_cfg["reproj_px"], engine=pm_eng)[0]
+            if poses is None:
+                raise ValueError(f"eval_camera: clip {seq}: the model {type(mdl).__name__!r} returns neither 'pred_poses' nor 'pred_world_pts'; "
+                                 f"remove eval_camera from the configuration")
+            metric.update(zip(CAMERA_KEYS, camera_pose_evaluation(poses, gt["gt_poses"])))
+            if config.get("vis_camera"):
+                save_camera_trajectories(poses, gt["gt_poses"], os.path.join(save_dir, f"camera_{seq}"))
         if config.get("vis_depth"):
             vis_dir = os.path.join(save_dir, f"depth_{seq}")
             os.makedirs(vis_dir, exist_ok=True)
