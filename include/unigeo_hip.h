@@ -366,6 +366,40 @@ int ug_prep_gt_ex(ug_ctx* ctx, const unsigned short* depth_u16 /* [T,Hi,Wi] */, 
                   const int* col_idx /* [Wo] */, int Wo, float max_depth, float* cam_normal_out, float* cam_coord_out, float* world_normal_out,
                   float* world_coord_out, float* mask_out, unsigned flags);
 
+/* 7-Scenes depth registration on the device: the raw Kinect depth image warped into the colour camera - what the reference does once, offline,
+ * in dataset/sevenScenes/preprocess.py:82-140, to write the *.depth.proj.png files its loader reads.  A forward splat
+ * with a z-buffer.  depth_u16 / out: host uint16 [T,H,W]; the output has the input's size and both principal points sit at the image centre.
+ * fl32 / fl64 below are ONE IEEE operation in that type, never contracted into an FMA; every sum runs left to right.
+ *   depth    d = fl32(float(raw) / divisor).  The pixel takes part iff d > 0 && d < max_valid (and, with UG_REG_DROP_SENTINEL, raw != 65535).
+ *            From here on d is widened to float64.
+ *   source   X = fl64(fl64(fl64(fl64(0.5 + col) - W/2) / src_focal) * d),  Y likewise with row and H/2,  Z = d
+ *   target   x3 = fl64(fl64(fl64(fl64(m00*X) + fl64(m01*Y)) + fl64(m02*Z)) + m03), y3 and z3 likewise from rows 1 and 2 of src2dst
+ *   project  u = fl64(fl64(fl64(x3 / z3) * dst_focal) + W/2), v likewise with y3 and H/2;  xi = rint(u), yi = rint(v), ties to even.
+ *            The point is kept iff xi >= 0 && yi >= 0 && yi < H && xi < W, compared as float64 before any integer cast (a NaN is dropped).
+ *   minimum  zbuf[yi, xi] = min over the points that land there of fl32(z3), and 2000f where none does
+ *   output   z = zbuf > 1000f ? 0 : zbuf;  v = fl32(1000f * z);  out = int32(trunc(v)) modulo 65536.  A v outside int32 (it cannot occur with
+ *            the defaults) gives 0.
+ * The modulo is part of the definition: 7-Scenes marks an invalid raw pixel with 65535, which passes the depth test as 65.535 m; where such a
+ * point fills a hole with z3 > 65.535 m its output wraps to a few hundred millimetres, as it does in the reference's files.
+ * UG_REG_DROP_SENTINEL leaves those pixels out; after that only a measured depth beyond 65 m could wrap.  The minimum is one integer atomic per source pixel on an
+ * order-preserving key of fl32(z3): the output does not depend on scheduling, equals harness/rgbd.py's register_depth bit for bit and, with
+ * the defaults, the reference's files.  The clip is processed in chunks of frames of bounded device size.
+ * ug_register_opts_default: the 7-Scenes calibration (depth focal 585, colour focal 525, the depth-to-colour transform of the Kinect calibration
+ *   the reference cites, divisor 1000, max_valid 100), flags 0.
+ * Errors (ug_last_error; the context stays usable; all are found on the host before anything is uploaded): NULL depth_u16 or out; T, H or
+ *   W <= 0; T * H * W >= 2^31; a flag bit other than UG_REG_DROP_SENTINEL; a src_focal, dst_focal, divisor or max_valid that is not finite
+ *   and positive; a non-finite entry of src2dst. */
+typedef struct {
+  double src_focal, dst_focal;   /* 585, 525 */
+  double src2dst[12];            /* row-major 3x4 */
+  float divisor, max_valid;      /* 1000, 100 */
+  unsigned flags;
+} ug_register_opts;
+#define UG_REG_DROP_SENTINEL 1   /* raw == 65535 takes no part */
+void ug_register_opts_default(ug_register_opts* o);
+int ug_prep_register_depth(ug_ctx* ctx, const unsigned short* depth_u16 /* host [T,H,W] */, int T, int H, int W,
+                           const ug_register_opts* opts /* NULL: defaults */, unsigned short* out /* host [T,H,W] */);
+
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */
 int ug_profile_begin(ug_ctx* ctx);

@@ -28,6 +28,7 @@ EXPORTS = [
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
     "ug_pointmap_opts_default", "ug_pointmap_focal", "ug_pointmap_poses",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
+    "ug_register_opts_default", "ug_prep_register_depth",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -68,8 +69,14 @@ class PointmapOptsC(C.Structure):
     _fields_ = [("reproj_px", C.c_double), ("max_iter", C.c_int), ("max_rounds", C.c_int)]
 
 
+class RegisterOptsC(C.Structure):
+    _fields_ = [("src_focal", C.c_double), ("dst_focal", C.c_double), ("src2dst", C.c_double * 12), ("divisor", C.c_float),
+                ("max_valid", C.c_float), ("flags", C.c_uint)]
+
+
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_ALIGN_* of include/unigeo_hip.h
 PREP_DEPTH_F64, PREP_ZOOMED = 1, 2                                       # UG_PREP_* of include/unigeo_hip.h
+REG_DROP_SENTINEL = 1                                                    # UG_REG_* of include/unigeo_hip.h
 
 _lib = None
 
@@ -153,6 +160,8 @@ def load_library():
     _set_argtypes(lib, {"ug_prep_resize_frames": [vp, vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp, ip, vp],
                         "ug_prep_gt": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp],
                         "ug_prep_gt_ex": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp, C.c_uint]})
+    _set_argtypes(lib, {"ug_register_opts_default": [C.POINTER(RegisterOptsC)],
+                        "ug_prep_register_depth": [vp, vp, ip, ip, ip, C.POINTER(RegisterOptsC), vp]})
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -908,6 +917,31 @@ class Engine:
         self._ck(self.lib.ug_prep_gt_ex(self.ctx, _ptr(d), float(depth_divisor), _ptr(n), _ptr(k), _ptr(m), T, Hi, Wi, _ptr(ri), Ho, _ptr(ci), Wo,
                                         float(max_depth), _ptr(cn), _ptr(cc), _ptr(wn), _ptr(wc), _ptr(mask), flags))
         return cn, cc, wn, wc, mask
+
+    def prep_register_depth(self, depth_u16, opts=None, invalid="keep"):
+        """Raw depth warped into the colour camera on the device (``ug_prep_register_depth``): uint16 ``[T,H,W]`` or
+        ``[H,W]`` -> uint16 of the same shape, bit-equal to ``harness.rgbd.register_depth``.  ``opts``: a ``harness.rgbd.RegisterOpts``
+        (``None``: the library's defaults, the 7-Scenes calibration); ``invalid="drop"`` sets ``UG_REG_DROP_SENTINEL``."""
+        from .harness.rgbd import REGISTER_INVALID
+        if invalid not in REGISTER_INVALID:
+            raise ValueError(f"prep_register_depth: invalid must be one of {list(REGISTER_INVALID)}, not {invalid!r}")
+        d = np.asarray(depth_u16)
+        if d.dtype != np.uint16 or d.ndim not in (2, 3):
+            raise ValueError("prep_register_depth: depth must be uint16 [T,H,W] or [H,W]")
+        clip = np.ascontiguousarray(d if d.ndim == 3 else d[None])
+        T, H, W = clip.shape
+        o = RegisterOptsC()
+        self.lib.ug_register_opts_default(C.byref(o))
+        if opts is not None:
+            m = np.asarray(opts.src2dst, np.float64).reshape(-1)
+            if m.size != 12:
+                raise ValueError("prep_register_depth: src2dst holds 12 numbers, the top three rows of the transform")
+            o.src_focal, o.dst_focal, o.divisor, o.max_valid = float(opts.src_focal), float(opts.dst_focal), float(opts.divisor), float(opts.max_valid)
+            o.src2dst[:] = m.tolist()
+        o.flags = REG_DROP_SENTINEL if invalid == "drop" else 0
+        out = np.empty((T, H, W), np.uint16)
+        self._ck(self.lib.ug_prep_register_depth(self.ctx, _ptr(clip), T, H, W, C.byref(o), _ptr(out)))
+        return out if d.ndim == 3 else out[0]
 
     # ---- ops (parity tests)
     def op_linear(self, A, W, bias=None, R1=None, c0=1.0, c1=1.0, act=0, geglu=False):

@@ -949,4 +949,55 @@ int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, cons
                        world_coord, mask, (Ho != Hi || Wo != Wi) ? UG_PREP_ZOOMED : 0);
 }
 
+// ---------------------------------------------------------------- 7-Scenes depth registration (kernels/register.hip)
+// Depth focal length from the 7-Scenes page, colour focal length and the depth-to-colour transform from the Kinect calibration the reference's
+// dataset/sevenScenes/preprocess.py cites: https://projet.liris.cnrs.fr/voir/activities-dataset/kinect-calibration.html
+void ug_register_opts_default(ug_register_opts* o) {
+  if (!o) return;
+  static const double m[12] = {9.9996518012567637e-01,  2.6765126468950343e-03, -7.9041012313000904e-03, -2.5558943178152542e-02,
+                               -2.7409311281316700e-03, 9.9996302803027592e-01, -8.1504520778013286e-03, 1.0109636268061706e-04,
+                               7.8819942130445332e-03,  8.1718328771890631e-03, 9.9993554558014031e-01,  2.0318321729487039e-03};
+  o->src_focal = 585.0; o->dst_focal = 525.0;
+  memcpy(o->src2dst, m, sizeof(m));
+  o->divisor = 1000.f; o->max_valid = 100.f; o->flags = 0;
+}
+
+int ug_prep_register_depth(ug_ctx* x, const unsigned short* depth, int T, int H, int W, const ug_register_opts* opts, unsigned short* out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    ug_register_opts o;
+    if (opts) o = *opts; else ug_register_opts_default(&o);
+    const unsigned unknown = o.flags & ~(unsigned)UG_REG_DROP_SENTINEL;
+    if (unknown) {
+      char hex[16]; snprintf(hex, sizeof hex, "0x%x", unknown);
+      throw std::runtime_error(std::string("ug_prep_register_depth: unknown flag bits ") + hex + " (UG_REG_DROP_SENTINEL)");
+    }
+    UG_REQUIRE(depth && out, "depth_u16 and out must not be NULL");
+    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
+    UG_REQUIRE((long)T * H * W < (1L << 31), "T * H * W must stay below 2^31");
+    UG_REQUIRE(std::isfinite(o.src_focal) && o.src_focal > 0 && std::isfinite(o.dst_focal) && o.dst_focal > 0, "src_focal and dst_focal must be finite and positive");
+    UG_REQUIRE(std::isfinite(o.divisor) && o.divisor > 0 && std::isfinite(o.max_valid) && o.max_valid > 0, "divisor and max_valid must be finite and positive");
+    RegArgs a;
+    a.src_focal = o.src_focal; a.dst_focal = o.dst_focal; a.divisor = o.divisor; a.max_valid = o.max_valid;
+    a.drop_sentinel = (o.flags & UG_REG_DROP_SENTINEL) != 0;
+    for (int i = 0; i < 12; ++i) { UG_REQUIRE(std::isfinite(o.src2dst[i]), "src2dst must be finite"); a.m[i] = o.src2dst[i]; }
+    const size_t px_f = (size_t)H * W;
+    const int Tc = prep_chunk_frames(T, px_f * 8);             // per pixel: 2 bytes in, a 4-byte z-buffer word, 2 bytes out
+    unsigned short* dd = (unsigned short*)c.ws.alloc(px_f * 2 * Tc);
+    unsigned* dz = c.ws.get<unsigned>((long)(px_f * Tc));
+    unsigned short* dout = (unsigned short*)c.ws.alloc(px_f * 2 * Tc);
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+      const int tc = std::min(Tc, T - t0);
+      UG_CHECK(hipMemcpy(dd, depth + px_f * t0, px_f * 2 * tc, hipMemcpyHostToDevice));
+      ProfRec r; r.name = "register_depth"; r.flops = 0; r.bytes = (double)px_f * tc * 12;    // fill 4, splat 2 + 4, finalize 4 + 2; under ug_profile_begin only
+      if (c.prof_on) { UG_CHECK(hipEventCreate(&r.e0)); UG_CHECK(hipEventCreate(&r.e1)); UG_CHECK(hipEventRecord(r.e0, c.stream)); }
+      launch_register_depth(dd, tc, H, W, a, dz, dout, c.stream);
+      if (c.prof_on) { UG_CHECK(hipEventRecord(r.e1, c.stream)); c.prof.push_back(r); }
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      UG_CHECK(hipMemcpy(out + px_f * t0, dout, px_f * 2 * tc, hipMemcpyDeviceToHost));
+    }
+  });
+}
+
 }  // extern "C"

@@ -394,3 +394,7 @@ void launch_prep_resize(const unsigned char* frames, const int* ridx, const doub
 void launch_prep_gt(const unsigned short* depth, const unsigned char* normals, const double* cam, const int* row_idx, const int* col_idx, int T,
                     int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, int depth_f64, int zoomed, float* cam_normal, float* world_normal,
                     float* cam_coord, float* world_coord, float* mask, hipStream_t s);
+// 7-Scenes depth registration (kernels/register.hip): depth / out uint16 [T,H,W], zbuf T*H*W words of scratch, all on the
+// device; m: the source-to-target transform, row-major 3x4
+struct RegArgs { double src_focal, dst_focal; double m[12]; float divisor, max_valid; int drop_sentinel; };
+void launch_register_depth(const unsigned short* depth, int T, int H, int W, const RegArgs& a, unsigned* zbuf, unsigned short* out, hipStream_t s);

@@ -10,7 +10,7 @@ from .eval import (evaluate, parse_camera_eval_config, parse_dataset_config, par
 from .dataset import SyntheticGeometryDataset, split_clips
 from .scannetpp import ScannetPPDataset, ScannetPPSequence
 from .rgbd import (RGBDClipDataset, RGBDSequence, ScannetV2Dataset, bonnDataset, neuralRGBDDataset, read_tum_trajectory, replicaDataset,
-                   sevenScenesDataset)
+                   sevenScenesDataset, RegisterOpts, register_depth)
 from .distributed import evaluate_sharded
 from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, read_ply, save_depth_normal_maps, write_ply
 
@@ -19,7 +19,7 @@ __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_eval
            "parse_metric_config", "parse_pcd_eval_config", "parse_camera_eval_config", "import_class_from_module", "SyntheticGeometryDataset",
            "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence",
            "RGBDClipDataset", "RGBDSequence", "sevenScenesDataset", "bonnDataset", "neuralRGBDDataset", "replicaDataset", "ScannetV2Dataset",
-           "read_tum_trajectory",
+           "read_tum_trajectory", "RegisterOpts", "register_depth",
            "camera_pose_evaluation", "tum_poses", "write_tum_trajectory", "save_camera_trajectories",
            "pointmap_focal", "pointmap_poses", "poses_from_pointmap",
            "SPECTRAL_R_LUT", "colorbar_strip", "colorize", "panels_u8", "save_depth_normal_maps", "write_ply", "read_ply"]

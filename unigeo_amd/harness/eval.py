@@ -30,7 +30,8 @@ def parse_dataset_config(config):
            "clip_overlap": config.get("clip_overlap", 0), "input_size": (config["h"], config["w"]),
            "target_size": (config["h"], config["w"])}
     for k in ("split", "split_file", "scenes",       # optional: which scene list the loader walks (default: the split file)
-              "prep"):                               # optional: host | device clip preparation of the ScanNet++ / RGB-D loaders (DESIGN.md sections 16, 17)
+              "prep",                                # optional: host | device clip preparation of the ScanNet++ / RGB-D loaders (DESIGN.md sections 16, 17)
+              "register", "register_invalid"):       # optional, 7-Scenes: host | device registration of raw depth, keep | drop of its 65535 marker (section 22)
         if k in config:
             out[k] = config[k]
     return out

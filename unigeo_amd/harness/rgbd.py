@@ -19,9 +19,15 @@ Deliberate differences from the reference:
 * the TUM reader does not need ``evo``;
 * Hypersim is not covered (its loader needs ``h5py``; no DepthCrafter configuration names it).
 
+7-Scenes ships raw Kinect depth (``*.depth.png``), not the ``*.depth.proj.png`` files the reference's loader reads: its
+``dataset/sevenScenes/preprocess.py`` writes those, offline.  ``sevenScenesDataset(register="host" | "device")`` reads the raw files and warps
+them into the colour camera per clip (``register_depth`` here, ``ug_prep_register_depth`` on the GPU), bit-equal to the
+reference's files (``tests/golden/register_golden.npz``).  Without ``register`` nothing changes.
+
 ``prep="device"`` keeps the file decode, ScanNetv2's Pillow pre-resize and the small tables on the host and runs the pixel arithmetic on the
 GPU (``ug_prep_resize_frames`` / ``ug_prep_gt_ex``).  A crop needs no device code of its own: the tables carry its origin.
 """
+import dataclasses
 import glob
 import os
 import re
@@ -36,6 +42,76 @@ from .scannetpp import PREP_MODES, _backproject_gl, _resize, resize_pick, resize
 
 _GL_CV = np.float32([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]])
 MAX_DEPTH = 20.0                   # "indoor scene": the mask bound of all five loaders
+REGISTER_MODES = (None, "host", "device")
+REGISTER_INVALID = ("keep", "drop")
+RAW_SENTINEL = 65535               # 7-Scenes marks an invalid raw depth pixel with it
+SEVEN_SCENES_SIZE = (480, 640)
+
+
+@dataclasses.dataclass
+class RegisterOpts:
+    """``ug_register_opts`` of include/unigeo_hip.h without its flags.  The defaults are the 7-Scenes calibration: the depth focal length from
+    the dataset's page, the colour focal length and the depth-to-colour transform from the Kinect calibration the reference's
+    ``dataset/sevenScenes/preprocess.py`` cites, https://projet.liris.cnrs.fr/voir/activities-dataset/kinect-calibration.html"""
+    src_focal: float = 585.0
+    dst_focal: float = 525.0
+    src2dst: tuple = (9.9996518012567637e-01, 2.6765126468950343e-03, -7.9041012313000904e-03, -2.5558943178152542e-02,
+                      -2.7409311281316700e-03, 9.9996302803027592e-01, -8.1504520778013286e-03, 1.0109636268061706e-04,
+                      7.8819942130445332e-03, 8.1718328771890631e-03, 9.9993554558014031e-01, 2.0318321729487039e-03)    # row-major 3x4
+    divisor: float = 1000.0
+    max_valid: float = 100.0
+
+
+def _register_zbuf(frame, drop, o):
+    """The z-buffer of one frame before the conversion to millimetres: float32 [H,W], 2000 where no point landed."""
+    H, W = frame.shape
+    m = [float(x) for x in np.asarray(o.src2dst, np.float64).reshape(-1)]
+    sf, df = float(o.src_focal), float(o.dst_focal)
+    d32 = frame.astype(np.float32) / np.float32(o.divisor)
+    ok = (d32 > 0) & (d32 < np.float32(o.max_valid))
+    if drop:
+        ok &= frame != RAW_SENTINEL
+    row, col = np.nonzero(ok)
+    d = d32[ok].astype(np.float64)
+    X = (((0.5 + col) - W / 2) / sf) * d
+    Y = (((0.5 + row) - H / 2) / sf) * d
+    x3 = ((m[0] * X + m[1] * Y) + m[2] * d) + m[3]
+    y3 = ((m[4] * X + m[5] * Y) + m[6] * d) + m[7]
+    z3 = ((m[8] * X + m[9] * Y) + m[10] * d) + m[11]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        xi = np.rint(((x3 / z3) * df) + W / 2)                   # ties to even, as Python's round
+        yi = np.rint(((y3 / z3) * df) + H / 2)
+        keep = (xi >= 0) & (yi >= 0) & (yi < H) & (xi < W)       # as float64, before any integer cast; a NaN is dropped
+        zbuf = np.full(H * W, 2000.0, np.float32)
+        np.minimum.at(zbuf, yi[keep].astype(np.int64) * W + xi[keep].astype(np.int64), z3[keep].astype(np.float32))
+    return zbuf.reshape(H, W)
+
+
+def register_depth(raw_u16, invalid="keep", opts=None):
+    """Raw depth warped into the colour camera: the host mirror of ``ug_prep_register_depth`` (the arithmetic is documented operation by
+    operation in include/unigeo_hip.h) and a restatement of ``preprocess.py:82-140`` without its loop over the pixels.  ``raw_u16``: uint16
+    ``[H,W]`` or ``[T,H,W]`` -> uint16 of the same shape.  Element-wise float64 steps in the reference's order - its one matrix product is
+    written out left to right, which reproduces its files -, ``np.minimum.at`` for the z-buffer, and its ``astype(uint16)`` of values past
+    65535 as the modulo it is.  ``invalid="drop"`` leaves raw 65535 out (UNPINNED: the reference has no such mode); ``"keep"`` lets it take
+    part as 65.535 m, as the reference does."""
+    if invalid not in REGISTER_INVALID:
+        raise ValueError(f"invalid must be one of {list(REGISTER_INVALID)}, not {invalid!r}")
+    o = RegisterOpts() if opts is None else opts
+    raw = np.asarray(raw_u16)
+    if raw.dtype != np.uint16 or raw.ndim not in (2, 3):
+        raise ValueError("register_depth: raw depth must be uint16 [H,W] or [T,H,W]")
+    if np.asarray(o.src2dst).size != 12:
+        raise ValueError("register_depth: src2dst holds 12 numbers, the top three rows of the transform")
+    clip = raw if raw.ndim == 3 else raw[None]
+    out = np.empty(clip.shape, np.uint16)
+    for t, frame in enumerate(clip):
+        zbuf = _register_zbuf(frame, invalid == "drop", o)
+        zbuf[zbuf > np.float32(1000.0)] = 0
+        with np.errstate(over="ignore", invalid="ignore"):
+            v = np.float32(1000.0) * zbuf
+            v = np.where((v > -2.0 ** 31) & (v < 2.0 ** 31), v, np.float32(0))     # outside int32: 0 (custom options only)
+        out[t] = (v.astype(np.int64) % 65536).astype(np.uint16)
+    return out if raw.ndim == 3 else out[0]
 
 
 def _sorted_glob(base, pattern, number=None):
@@ -118,6 +194,7 @@ class Layout:
     clamp_depth = None                 # NeuralRGBD: d > clamp -> 0 and d < 1e-3 -> 0 before the back-projection
     color_size = None                  # ScanNetv2: (width, height) the colour image is resized to with Pillow's default filter
     crop_aspect = None                 # Replica: centred crop to this width / height AFTER the back-projection
+    raw_size = None                    # 7-Scenes: (height, width) of the raw depth that ``register=`` warps into the colour camera; None: no such step
 
     def discover(self, base):
         raise NotImplementedError
@@ -128,11 +205,17 @@ class Layout:
 
 
 class SevenScenesLayout(Layout):
-    """sevenScenes.py:48-72: ``*.color.png`` / ``*.depth.proj.png`` / ``*.pose.txt`` (OpenCV camera-to-world) sorted by name."""
+    """sevenScenes.py:48-72: ``*.color.png`` / ``*.depth.proj.png`` / ``*.pose.txt`` (OpenCV camera-to-world) sorted by name.
+    ``raw_depth=True``: the depth files are the dataset's own ``*.depth.png`` (a pattern that does not match ``*.depth.proj.png``), which the
+    dataset registers to the colour camera itself."""
     base_dataset = "7scenes"
+    raw_size = SEVEN_SCENES_SIZE
+
+    def __init__(self, raw_depth=False):
+        self.depth_pattern = "*.depth.png" if raw_depth else "*.depth.proj.png"
 
     def discover(self, base):
-        rgb, depth, pose = (_sorted_glob(base, p) for p in ("*.color.png", "*.depth.proj.png", "*.pose.txt"))
+        rgb, depth, pose = (_sorted_glob(base, p) for p in ("*.color.png", self.depth_pattern, "*.pose.txt"))
         _same_length(base, colour=rgb, depth=depth, poses=pose)
         if not rgb:
             return np.zeros((0, 4, 4)), np.zeros((0, 3, 3)), rgb, depth
@@ -261,6 +344,12 @@ def decode_clip(root, seq, ids):
     return frames, depth
 
 
+def decode_depth(root, seq, ids):
+    """The depth files of a clip alone: uint16 [T,H,W]."""
+    base = os.path.join(root, seq.scene_name)
+    return np.stack([_open_depth(os.path.join(base, seq.depth_paths[i])) for i in ids])
+
+
 def depth_metres(raw, layout):
     """The layout's depth arithmetic on a decoded depth image, before the back-projection."""
     raw = np.asarray(raw).astype(np.float32)
@@ -300,8 +389,9 @@ def _clip_cameras(seq, ids, box):
     return ext, K, Kc
 
 
-def load_clip(root, seq, ids, keyview_idx=0):
-    """One clip at native size on the host: the reference's ``*Sample.load`` + ``postprocess``, step for step."""
+def load_clip(root, seq, ids, keyview_idx=0, depth=None):
+    """One clip at native size on the host: the reference's ``*Sample.load`` + ``postprocess``, step for step.  ``depth`` (uint16 ``[T,H,W]``)
+    stands in for the depth files: the registered clip of ``sevenScenesDataset(register=...)``."""
     layout, base = seq.layout, os.path.join(root, seq.scene_name)
     frames = [_open_rgb(os.path.join(base, seq.rgb_paths[i]), layout) for i in ids]
     h, w = frames[0].shape[:2]
@@ -311,7 +401,7 @@ def load_clip(root, seq, ids, keyview_idx=0):
     images, cam, world, masks = [], [], [], []
     for j, i in enumerate(ids):
         images.append(frames[j].astype(np.float32).transpose(2, 0, 1)[:, y1:y2, x1:x2])
-        raw = _open_depth(os.path.join(base, seq.depth_paths[i]))
+        raw = _open_depth(os.path.join(base, seq.depth_paths[i])) if depth is None else depth[j]
         c = _backproject_gl(depth_metres(raw, layout), K[0])     # view 0's intrinsics for all views, uncropped, on the full frame
         M = ref @ np.linalg.inv(ext[j])                          # source camera -> key-view camera
         wc = (np.matmul(M[:3, :3], c.reshape(3, -1)) + M[:3, 3][:, None]).reshape(c.shape)
@@ -330,17 +420,30 @@ class RGBDClipDataset:
     """Clip-level dataset in the unified sample format over one ``Layout``; constructor, keys, dtypes and shapes as ``ScannetPPDataset``,
     without ``cam_normal`` / ``world_normal``.  ``scenes=[...]`` or ``split_file=`` (one scene per line, e.g. a UniGeo checkout's
     ``dataset/<name>/splits/test.txt``) names the scenes; ``"all"`` is not accepted because scene names can be nested (``chess/seq-03``).
-    ``prep="device"`` runs the resizes and the ground truth on the GPU; there is no fallback to the host path."""
+    ``prep="device"`` runs the resizes and the ground truth on the GPU; there is no fallback to the host path.
+    ``register="host" | "device"`` (7-Scenes only; anywhere else it is a ``ValueError``): the scene holds raw depth, which is warped into the
+    colour camera per clip before anything else sees it - on the host (``register_depth``) or on the dataset's engine (no fallback);
+    ``register_invalid="drop"`` leaves the raw 65535 marker out of it."""
 
     layout = None
 
     def __init__(self, root, scenes=None, split_file=None, split="test", clip_length=17, clip_overlap=0,
-                 input_size=None, target_size=None, verbose=False, prep="host", device_id=0, engine=None, **_):
+                 input_size=None, target_size=None, verbose=False, prep="host", device_id=0, engine=None, register=None,
+                 register_invalid="keep", **_):
         if prep not in PREP_MODES:
             raise ValueError(f"prep must be one of {list(PREP_MODES)}, not {prep!r}")
+        if register not in REGISTER_MODES:
+            raise ValueError(f"register must be one of {list(REGISTER_MODES)}, not {register!r}")
+        if register_invalid not in REGISTER_INVALID:
+            raise ValueError(f"register_invalid must be one of {list(REGISTER_INVALID)}, not {register_invalid!r}")
+        if register is not None:
+            if self.layout.raw_size is None:
+                raise ValueError(f"{self.layout.base_dataset}: register= is for 7-Scenes' raw depth; this dataset's depth needs no registration")
+            self.layout = type(self.layout)(raw_depth=True)     # this dataset's own layout: the class attribute keeps the default pattern
+        self.register, self.register_invalid = register, register_invalid
         self.prep, self.device_id, self.engine = prep, device_id, engine
         self._lock = threading.Lock()
-        self.last_timing = None                             # prep="device": seconds of the last sample's decode / resize / gt stages
+        self.last_timing = None                             # seconds of the last sample's stages: prep="device" decode / resize / gt, register= register
         name = self.layout.base_dataset
         if root is None or not os.path.isdir(root):
             raise FileNotFoundError(f"{name} root not found: {root!r}")
@@ -377,7 +480,14 @@ class RGBDClipDataset:
         if self.prep == "device":
             out = self._load_clip_device(seq, ids)
         else:
-            out = load_clip(self.root, seq, ids)
+            if self.register is None:
+                out = load_clip(self.root, seq, ids)
+            else:
+                raw = decode_depth(self.root, seq, ids)
+                t0 = time.perf_counter()
+                depth = self._register(raw)
+                self.last_timing = {"register": time.perf_counter() - t0}
+                out = load_clip(self.root, seq, ids, depth=depth)
             if self.input_size is not None:
                 ht, wd = self.input_size
                 oh, ow = out["images"][0].shape[-2:]
@@ -398,6 +508,16 @@ class RGBDClipDataset:
             self.engine = Engine(self.device_id, workspace_bytes=256 << 20, persist_bytes=1 << 20)
         return self.engine
 
+    def _register(self, raw):
+        """The raw depth clip warped into the colour camera, on the host or on the dataset's engine."""
+        if raw.shape[1:] != self.layout.raw_size:
+            raise ValueError(f"{self.base_dataset}: register= expects raw depth of {self.layout.raw_size[0]} x {self.layout.raw_size[1]}, "
+                             f"not {raw.shape[1]} x {raw.shape[2]}")
+        if self.register == "host":
+            return register_depth(raw, self.register_invalid)
+        with self._lock:
+            return self._device_engine().prep_register_depth(raw, invalid=self.register_invalid)
+
     def _load_clip_device(self, seq, ids, keyview_idx=0):
         """``load_clip`` + the two resizes with the pixel arithmetic on the GPU: same keys, shapes and dtypes.  The crop is in the tables:
         taps and picks are built for the cropped length and shifted by the crop origin, so the mirror extension reflects at the crop's edge."""
@@ -405,6 +525,10 @@ class RGBDClipDataset:
         t0 = time.perf_counter()
         frames, depth = decode_clip(self.root, seq, ids)
         t1 = time.perf_counter()
+        if self.register is not None:
+            depth = self._register(depth)
+        tr = time.perf_counter() - t1
+        t1 += tr
         T, hi, wi = depth.shape
         x1, y1, x2, y2 = box = _crop_box(layout, hi, wi)
         ch, cw = y2 - y1, x2 - x1
@@ -423,7 +547,9 @@ class RGBDClipDataset:
                                              depth_divisor=layout.depth_divisor, max_depth=layout.max_depth, depth_f64=layout.depth_f64,
                                              zoomed=(th, tw) != (ch, cw))
             t3 = time.perf_counter()
-        self.last_timing = {"decode": t1 - t0, "resize": t2 - t1, "gt": t3 - t2}
+        self.last_timing = {"decode": t1 - tr - t0, "resize": t2 - t1, "gt": t3 - t2}
+        if self.register is not None:
+            self.last_timing["register"] = tr
         if self.input_size is not None:
             scale = np.array([[iw / cw] * 3, [ih / ch] * 3, [1.0] * 3], np.float32)
             Kc = [k * scale for k in Kc]
