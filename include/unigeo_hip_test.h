@@ -65,6 +65,20 @@ int ug_op_groupnorm(ug_ctx* ctx, const float* x0, int C0, const float* x1, int C
                     int temporal, int silu, const float* gamma, const float* beta, float* out);
 int ug_op_layernorm(ug_ctx* ctx, const float* x, int M, int C, float eps, const float* gamma, const float* beta,
                     const float* addvec, int rows_per_vec, float* out, float* xout);
+/* The launch forms of kernels/norm.hip that the two entries above leave to the launcher's heuristics (tests/test_norm_forms_gpu.py).
+ *   ug_op_groupnorm_ex: mode -> GroupNormP::mode (0 = the launcher picks; 1 / 2 / 4 / 6 force a scheme, which the launcher may still replace when the
+ *     tensor cannot take it).  out_inout [T*HW + guard, C0+C1]: with guard > 0 all of it is uploaded as the caller gives it, and all of it comes back -
+ *     the guard rows must return unchanged.  plan_out [4] (may be NULL): the scheme launched, the slab kernel's threads and register vectors VMAX
+ *     (0, 0 unless scheme 4 / 6), chunks per frame (0 unless scheme 1).
+ *   ug_op_layernorm_ex: row0 -> LayerNormP::row0 (addvec then holds ceil((M + row0) / rows_per_vec) vectors); form 0 = the launcher picks, 1 = the
+ *     one-wave-per-row kernel also at C = 320 / 640 / 1280; out_inout [M + guard, C] as above; *form_out (may be NULL) = L (8 / 16 / 32) when
+ *     ln40_kernel<L> ran, -VPL (-1 .. -4) when ln_kernel<VPL> ran.  y8_out [M][C] with s8_out [C/128][round_up(M,256)] (both or neither; C % 128 == 0):
+ *     the same launch once more with the MX-fp8 output pair - e4m3 bytes and scale dwords in ug_op_linear_mx8's layout, zeroed before the launch. */
+int ug_op_groupnorm_ex(ug_ctx* ctx, const float* x0, int C0, const float* x1, int C1, int T, int HW, int G, float eps,
+                       int temporal, int silu, const float* gamma, const float* beta, int mode, long guard, float* out_inout, int* plan_out /*[4]*/);
+int ug_op_layernorm_ex(ug_ctx* ctx, const float* x, int M, int C, float eps, const float* gamma, const float* beta,
+                       const float* addvec, int rows_per_vec, long row0, int form, long guard, float* out_inout, float* xout,
+                       unsigned char* y8_out, unsigned* s8_out, int* form_out);
 int ug_op_flash_attn(ug_ctx* ctx, const float* qkv /*[B*S,3*H*64]*/, int B, int H, int S, float* out /*[B*S,H*64]*/);
 int ug_op_temporal_attn(ug_ctx* ctx, const float* qkv /*[T*HW,3*H*64]*/, int T, int HW, int H, float* out);
 /* The other launch forms of the d = 64 flash attention (the cross-attention of the StableNormal transformer blocks): Sk keys per batch (0: self-attention,

@@ -22,6 +22,7 @@ EXPORTS = [
     "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
+    "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
@@ -179,6 +180,8 @@ def load_library():
     lib.ug_op_euler_step.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float]
     _set_argtypes(lib, {"ug_op_flash_cross_attn": [vp, vp, vp, ip, ip, ip, ip, ip, C.c_long, C.c_long, C.c_long, C.c_long, vp],
                         "ug_op_temporal_attn_nv": [vp, vp, ip, ip, ip, ip, vp]})
+    _set_argtypes(lib, {"ug_op_groupnorm_ex": [vp, vp, ip, vp, ip, ip, ip, ip, C.c_float, ip, ip, vp, vp, ip, C.c_long, vp, vp],
+                        "ug_op_layernorm_ex": [vp, vp, ip, ip, C.c_float, vp, vp, vp, ip, C.c_long, ip, C.c_long, vp, vp, vp, vp, vp]})
     _set_argtypes(lib, {
         "ug_op_split_pair": [vp, vp, C.c_long, ip, vp, vp], "ug_op_gn32_pair": [vp, vp, ip, ip, ip, ip, C.c_float, ip, vp, vp, vp, vp],
         "ug_op_conv_wide": [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, ip, ip, ip, ip, ip, vp], "ug_op_attn_wide": [vp, vp, ip, ip, ip, vp]})
@@ -988,6 +991,35 @@ class Engine:
         self._ck(self.lib.ug_op_layernorm(self.ctx, _ptr(x), M, Cc, eps, _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(av),
                                           rows_per_vec, _ptr(out), _ptr(xout)))
         return (out, xout) if addvec is not None else out
+
+    def op_groupnorm_ex(self, x0, G, eps, gamma, beta, x1=None, temporal=False, silu=False, mode=0, guard=0, guard_fill=0.0):
+        """GroupNorm with the launch scheme forced (mode 1 / 2 / 4 / 6; 0 = the launcher picks).  The output buffer has guard extra rows and is filled with
+        guard_fill before it goes to the device.  Returns (out [T*HW + guard, C] as the device holds it, plan) with plan = (scheme launched, slab threads,
+        slab VMAX, chunks per frame) - zeros where they do not apply."""
+        x0 = _f32(x0); T, HW, C0 = x0.shape
+        x1a = None if x1 is None else _f32(x1); C1 = 0 if x1 is None else x1a.shape[-1]
+        out = np.full((T * HW + guard, C0 + C1), guard_fill, np.float32)
+        plan = (C.c_int * 4)()
+        self._ck(self.lib.ug_op_groupnorm_ex(self.ctx, _ptr(x0), C0, _ptr(x1a), C1, T, HW, G, eps, int(temporal), int(silu),
+                                             _ptr(_f32(gamma)), _ptr(_f32(beta)), int(mode), int(guard), _ptr(out), plan))
+        return out, tuple(plan)
+
+    def op_layernorm_ex(self, x, eps, gamma, beta, addvec=None, rows_per_vec=1, row0=0, form=0, guard=0, guard_fill=0.0, fp8=False):
+        """LayerNorm with the pre-add's row offset, the kernel forced (form 1: one wave per row also at C = 320 / 640 / 1280) and reported.  addvec holds
+        ceil((M + row0) / rows_per_vec) vectors.  Returns a dict: out [M + guard, C] as the device holds it (filled with guard_fill before the launch),
+        form (L of ln40_kernel<L>, or -VPL of ln_kernel<VPL>), xout (with addvec), y8 [M, C] uint8 and s8 [C/128, round_up(M,256)] uint32 (with fp8)."""
+        x = _f32(x); M, Cc = x.shape
+        out = np.full((M + guard, Cc), guard_fill, np.float32)
+        av = None if addvec is None else _f32(addvec)
+        if av is not None:
+            assert av.shape == ((M + row0 + rows_per_vec - 1) // rows_per_vec, Cc), av.shape
+        xout = None if av is None else np.empty((M, Cc), np.float32)
+        y8 = np.empty((M, Cc), np.uint8) if fp8 else None
+        s8 = np.empty((Cc // 128, (M + 255) // 256 * 256), np.uint32) if fp8 else None
+        form_out = C.c_int(0)
+        self._ck(self.lib.ug_op_layernorm_ex(self.ctx, _ptr(x), M, Cc, eps, _ptr(_f32(gamma)), _ptr(_f32(beta)), _ptr(av), int(rows_per_vec), int(row0),
+                                             int(form), int(guard), _ptr(out), _ptr(xout), _ptr(y8), _ptr(s8), C.byref(form_out)))
+        return {"out": out, "form": form_out.value, "xout": xout, "y8": y8, "s8": s8}
 
     def op_flash_attn(self, qkv, B, H, S):
         q = _f32(qkv); out = np.empty((B * S, H * 64), np.float32)

@@ -532,39 +532,74 @@ int ug_op_conv_gn(ug_ctx* x, const float* x0, int C0, int T, int H, int W, const
   });
 }
 
-int ug_op_groupnorm(ug_ctx* x, const float* x0, int C0, const float* x1, int C1, int T, int HW, int G, float eps,
-                    int temporal, int silu, const float* gamma, const float* beta, float* out) {
+// GroupNorm with the launch scheme forced (GroupNormP::mode) and the launcher's decision reported.  out_inout [T*HW + guard, C] goes to the device as the
+// caller gives it and all of it comes back: the rows past T*HW must return unchanged (the slab kernel drops them through its buffer descriptor).
+// plan_out [4]: scheme launched, slab threads, slab VMAX (0, 0 unless scheme 4 / 6), chunks per frame (0 unless scheme 1).
+int ug_op_groupnorm_ex(ug_ctx* x, const float* x0, int C0, const float* x1, int C1, int T, int HW, int G, float eps,
+                       int temporal, int silu, const float* gamma, const float* beta, int mode, long guard, float* out_inout, int* plan_out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && HW >= 1 && G >= 1 && C0 >= 1 && C1 >= 0 && guard >= 0 && x0 && (C1 == 0 || x1) && out_inout, "groupnorm shape");
     const int C = C0 + C1; const long M = (long)T * HW;
     GroupNormP p; memset(&p, 0, sizeof(p));
     p.X0 = up16(c, x0, M * C0); p.X1 = C1 ? up16(c, x1, M * C1) : nullptr; p.C0 = C0; p.C1 = C1;
-    p.T = T; p.HW = HW; p.G = G; p.eps = eps; p.temporal = temporal; p.silu = silu;
+    p.T = T; p.HW = HW; p.G = G; p.eps = eps; p.temporal = temporal; p.silu = silu; p.mode = mode;
     p.gamma = up16(c, gamma, C); p.beta = up16(c, beta, C);
-    f16* y = c.ws.get<f16>(M * C); p.Y = y;
+    f16* y = guard ? up16(c, out_inout, (M + guard) * C) : c.ws.get<f16>(M * C); p.Y = y;
     p.ws = c.ws.get<float>((long)groupnorm_ws_floats(T, HW, C, G));
     launch_groupnorm(p, c.stream);
-    down16(c, y, out, M * C);
+    if (plan_out) { const GnPlan pl = groupnorm_plan(p); plan_out[0] = pl.mode; plan_out[1] = pl.nt; plan_out[2] = pl.vmax; plan_out[3] = pl.nchunk; }
+    down16(c, y, out_inout, (M + guard) * C);
+  });
+}
+
+int ug_op_groupnorm(ug_ctx* x, const float* x0, int C0, const float* x1, int C1, int T, int HW, int G, float eps,
+                    int temporal, int silu, const float* gamma, const float* beta, float* out) {
+  return ug_op_groupnorm_ex(x, x0, C0, x1, C1, T, HW, G, eps, temporal, silu, gamma, beta, 0, 0, out, nullptr);
+}
+
+// LayerNorm with the row offset of the pre-add (LayerNormP::row0), the kernel forced (form 1: ln_kernel also at C = 320 / 640 / 1280) and reported
+// (*form_out: L for ln40_kernel<L>, -VPL for ln_kernel<VPL>).  out_inout [M + guard, C] goes up as given and all of it comes back.  y8_out / s8_out: the same
+// launch again with the MX-fp8 output pair -> bytes [M][C] and scale dwords [C/128][round_up(M,256)] (ug_op_linear_mx8's layout; the buffer is zeroed first,
+// so the dwords of rows >= M come back 0).
+int ug_op_layernorm_ex(ug_ctx* x, const float* xin, int M, int C, float eps, const float* gamma, const float* beta,
+                       const float* addvec, int rows_per_vec, long row0, int form, long guard, float* out_inout, float* xout,
+                       unsigned char* y8_out, unsigned* s8_out, int* form_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(M >= 1 && C >= 8 && row0 >= 0 && guard >= 0 && xin && out_inout && (!addvec || rows_per_vec >= 1) && !y8_out == !s8_out, "layernorm arguments");
+    LayerNormP p; memset(&p, 0, sizeof(p));
+    p.X = up16(c, xin, (long)M * C); p.M = M; p.C = C; p.eps = eps; p.gamma = up16(c, gamma, C); p.beta = up16(c, beta, C);
+    p.row0 = row0; p.form = form;
+    f16* y = guard ? up16(c, out_inout, (M + guard) * C) : c.ws.get<f16>((long)M * C); p.Y = y;
+    f16* xo = nullptr;
+    if (addvec) {
+      const long nv = (M + row0 + rows_per_vec - 1) / rows_per_vec;
+      p.addvec = up16(c, addvec, nv * C); p.rows_per_vec = rows_per_vec;
+      xo = c.ws.get<f16>((long)M * C); p.Xout = xo;
+    }
+    launch_layernorm(p, c.stream);
+    if (form_out) *form_out = layernorm_form(p);
+    down16(c, y, out_inout, (M + guard) * C);
+    if (xo && xout) down16(c, xo, xout, (long)M * C);
+    if (y8_out) {
+      UG_REQUIRE(C % 128 == 0, "layernorm MX-fp8 output: C % 128 == 0");
+      const long ld = ((long)M + 255) / 256 * 256;
+      const size_t sbytes = (size_t)(C / 128) * ld * 4;
+      unsigned char* y8 = (unsigned char*)c.ws.alloc((size_t)M * C); unsigned* s8 = (unsigned*)c.ws.alloc(sbytes);
+      UG_CHECK(hipMemsetAsync(s8, 0, sbytes, c.stream));
+      p.Y = nullptr; p.Xout = nullptr; p.Y8 = y8; p.S8 = s8; p.ld_s8 = ld;
+      launch_layernorm(p, c.stream);
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      UG_CHECK(hipMemcpy(y8_out, y8, (size_t)M * C, hipMemcpyDeviceToHost));
+      UG_CHECK(hipMemcpy(s8_out, s8, sbytes, hipMemcpyDeviceToHost));
+    }
   });
 }
 
 int ug_op_layernorm(ug_ctx* x, const float* xin, int M, int C, float eps, const float* gamma, const float* beta,
                     const float* addvec, int rows_per_vec, float* out, float* xout) {
-  UG_TRY(x, {
-    Ctx& c = x->c; Scope sc(c);
-    LayerNormP p; memset(&p, 0, sizeof(p));
-    p.X = up16(c, xin, (long)M * C); p.M = M; p.C = C; p.eps = eps; p.gamma = up16(c, gamma, C); p.beta = up16(c, beta, C);
-    f16* y = c.ws.get<f16>((long)M * C); p.Y = y;
-    f16* xo = nullptr;
-    if (addvec) {
-      const int nv = (M + rows_per_vec - 1) / rows_per_vec;
-      p.addvec = up16(c, addvec, (long)nv * C); p.rows_per_vec = rows_per_vec;
-      xo = c.ws.get<f16>((long)M * C); p.Xout = xo;
-    }
-    launch_layernorm(p, c.stream);
-    down16(c, y, out, (long)M * C);
-    if (xo && xout) down16(c, xo, xout, (long)M * C);
-  });
+  return ug_op_layernorm_ex(x, xin, M, C, eps, gamma, beta, addvec, rows_per_vec, 0, 0, 0, out, xout, nullptr, nullptr, nullptr);
 }
 
 int ug_op_flash_attn(ug_ctx* x, const float* qkv, int B, int H, int S, float* out) {

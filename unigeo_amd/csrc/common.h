@@ -137,6 +137,9 @@ struct GroupNormP {
 };
 bool launch_groupnorm(const GroupNormP& p, hipStream_t s);                 // true = the statistics came from p.part (no pass over X for them)
 bool groupnorm_uses_part(const GroupNormP& p, int part_rb);                // the launcher's rule for that, for the callers that decide whether a producer writes partial sums
+// the launcher's decision for p: the scheme (1 / 2 / 4 / 6), the slab's threads and register vectors (0, 0 unless 4 / 6), chunks per frame and rows per chunk (0 unless 1)
+struct GnPlan { int mode, nt, vmax, nchunk, rpc; };
+GnPlan groupnorm_plan(const GroupNormP& p);
 size_t groupnorm_ws_floats(int T, int HW, int C, int G);
 
 // LayerNorm over rows of [M, C]; optional pre-add of a per-frame broadcast vector
@@ -148,8 +151,10 @@ struct LayerNormP {
   long row0;                                        // index of row 0 in the addvec numbering (a row sub-range of a larger tensor)
   // optional MX-fp8 output INSTEAD of Y (fp8 linear path): e4m3 bytes [M][C] + e8m0 block scales, layout of launch_quant_mx8 (C % 128 == 0)
   unsigned char* Y8; unsigned* S8; long ld_s8;
+  int form;                                         // 0 = the launcher picks; 1 = the one-wave-per-row ln_kernel also at C = 320 / 640 / 1280 (op tests; 0 on the product path)
 };
 void launch_layernorm(const LayerNormP& p, hipStream_t s);
+int layernorm_form(const LayerNormP& p);            // the kernel the launcher runs for p: L for ln40_kernel<L>, -VPL for ln_kernel<VPL>
 
 // ---------------------------------------------------------------------------------------
 // Attention (kernels/attn.hip)

@@ -585,14 +585,26 @@ bool groupnorm_uses_part(const GroupNormP& p0, int part_rb) {
   return mode == 1 || mode == 6;
 }
 
+// what launch_groupnorm does for p (the one decision: the launcher below runs exactly this plan, the op test reports it): the scheme, the slab's
+// workgroup size and register vectors (scheme 4: the plan of the whole slab, scheme 6: of the per-frame slabs), the chunking of scheme 1
+GnPlan groupnorm_plan(const GroupNormP& p) {
+  GnPlan pl = {0, 0, 0, 0, 0};
+  int snt = 0, svmax = 0, tnt = 0, tvmax = 0;
+  pl.mode = gn_pick_mode(p, &snt, &svmax, &tnt, &tvmax);
+  if (pl.mode == 4) { pl.nt = snt; pl.vmax = svmax; }
+  else if (pl.mode == 6) { pl.nt = tnt; pl.vmax = tvmax; }
+  else if (pl.mode != 2) gn_chunks2(p.T, p.HW, p.C0 + p.C1, pl.nchunk, pl.rpc);
+  return pl;
+}
+
 bool launch_groupnorm(const GroupNormP& p, hipStream_t s) {
   const int C = p.C0 + p.C1;
   UG_REQUIRE(p.C0 % 8 == 0 && p.C1 % 8 == 0, "GroupNorm channels must be multiples of 8");
   UG_REQUIRE(C % p.G == 0 && p.G <= 256 && 256 % p.G == 0, "GroupNorm group count must divide 256");
   UG_REQUIRE(C <= GN_MAXV * GN_THREADS * 8, "GroupNorm too many channels");
   const int cpg = C / p.G;
-  int snt = 0, svmax = 0, tnt = 0, tvmax = 0;
-  int mode = gn_pick_mode(p, &snt, &svmax, &tnt, &tvmax);
+  const GnPlan pl = groupnorm_plan(p);
+  const int mode = pl.mode;
   if (p.part && p.mode == 0 && (mode == 1 || mode == 6)) {
     // the producing GEMM's epilogue left per-block column sums (GemmP::stat_part): no statistics pass over X - combine them, apply
     UG_REQUIRE(p.C1 == 0 && p.part_rb > 0 && p.HW % p.part_rb == 0, "GroupNorm: epilogue statistics need a single source and whole blocks per frame");
@@ -613,15 +625,14 @@ bool launch_groupnorm(const GroupNormP& p, hipStream_t s) {
     return true;
   }
   if (mode == 4) {
-    gn_slab_launch<0>(p, snt, svmax, dim3(p.G, p.temporal ? 1 : p.T), s);
+    gn_slab_launch<0>(p, pl.nt, pl.vmax, dim3(p.G, p.temporal ? 1 : p.T), s);
   } else if (mode == 6) {
-    gn_slab_launch<1>(p, tnt, tvmax, dim3(p.G, p.T), s);
-    gn_slab_launch<2>(p, tnt, tvmax, dim3(p.G, p.T), s);
+    gn_slab_launch<1>(p, pl.nt, pl.vmax, dim3(p.G, p.T), s);
+    gn_slab_launch<2>(p, pl.nt, pl.vmax, dim3(p.G, p.T), s);
   } else if (mode == 2) {
     hipLaunchKernelGGL(gn_small, dim3(p.G, p.T), dim3(256), 0, s, p);
   } else {
-    int nchunk, rpc;
-    gn_chunks2(p.T, p.HW, C, nchunk, rpc);
+    const int nchunk = pl.nchunk, rpc = pl.rpc;
     const GnGeom gg = gn_geom(C);
     const size_t lds = (size_t)gg.rpi * C * 2 * sizeof(float);
     float* ab = p.ws + (size_t)p.T * nchunk * p.G * 2;
@@ -789,14 +800,21 @@ __global__ __launch_bounds__(256) void ln40_kernel(const LayerNormP p) {
   }
 }
 
+// the kernel launch_layernorm runs for p: L = 8 / 16 / 32 for ln40_kernel<L>, -VPL = -1 .. -4 for ln_kernel<VPL> (the launcher switches on this value)
+int layernorm_form(const LayerNormP& p) {
+  static const bool no40 = getenv("UG_LN_NO40") != nullptr;   // A/B aid
+  if (!no40 && p.form != 1 && (p.C == 320 || p.C == 640 || p.C == 1280)) return p.C / 40;
+  return -cdiv(p.C / 8, 64);
+}
+
 void launch_layernorm(const LayerNormP& p, hipStream_t s) {
   UG_REQUIRE(p.C % 8 == 0, "LayerNorm C must be a multiple of 8");
-  const int vpl = cdiv(p.C / 8, 64);
-  UG_REQUIRE(vpl <= 4, "LayerNorm C too large");
+  UG_REQUIRE(cdiv(p.C / 8, 64) <= 4, "LayerNorm C too large");
+  UG_REQUIRE(p.form == 0 || p.form == 1, "LayerNorm form must be 0 (the launcher picks) or 1 (one wave per row)");
   if (p.Y8) UG_REQUIRE(p.C % 128 == 0 && p.S8 && p.ld_s8 >= p.M, "LayerNorm MX-fp8 output needs C % 128 == 0 and a scale buffer");
-  static const bool no40 = getenv("UG_LN_NO40") != nullptr;   // A/B aid
-  if (!no40 && (p.C == 320 || p.C == 640 || p.C == 1280)) {
-    const int L = p.C / 40, rows_per_block = 4 * (64 / L);
+  const int form = layernorm_form(p);
+  if (form > 0) {
+    const int L = form, rows_per_block = 4 * (64 / L);
     dim3 grid(cdiv(p.M, rows_per_block)), block(256);
     if (L == 8) hipLaunchKernelGGL(ln40_kernel<8>, grid, block, 0, s, p);
     else if (L == 16) hipLaunchKernelGGL(ln40_kernel<16>, grid, block, 0, s, p);
@@ -805,7 +823,7 @@ void launch_layernorm(const LayerNormP& p, hipStream_t s) {
     return;
   }
   dim3 grid(cdiv(p.M, 4)), block(256);
-  switch (vpl) {
+  switch (-form) {
     case 1: hipLaunchKernelGGL(ln_kernel<1>, grid, block, 0, s, p); break;
     case 2: hipLaunchKernelGGL(ln_kernel<2>, grid, block, 0, s, p); break;
     case 3: hipLaunchKernelGGL(ln_kernel<3>, grid, block, 0, s, p); break;
@@ -813,4 +831,3 @@ void launch_layernorm(const LayerNormP& p, hipStream_t s) {
   }
   UG_CHECK(hipGetLastError());
 }
-
