@@ -183,17 +183,33 @@ int ug_eval_normal(ug_ctx* ctx, const float* pred_normals, const float* gt_norma
  *                   this mode ill-conditioned at clip size - s moves by 1e-4 .. 3e-3 with the summation order alone, and the reference's float32
  *                   value is as far from any float64 one - so the value is deterministic, but no more "the" answer than another order's
  *   UG_ALIGN_METRIC (metric_scale=True)      s = 1, t = 0
+ *   UG_ALIGN_L1     (no reference flag; takes the place of align_with_lad)  the exact minimiser of sum |s p + t - gt| over mask1 (DESIGN.md
+ *                   section 23).  E = the smallest integer with max |p| < 2^E, q_i = rint(p_i * 2^(36 - E)) as a 64-bit integer (exact for every
+ *                   p_i within 12 binades of the largest).  A step from pivot j: over the i with q_i != q_j, weights w_i = |q_i - q_j| and slopes
+ *                   r_i = (double(g_i) - double(g_j)) / (double(q_i - q_j) * 2^(E - 36)), -0.0 read as 0.0; S = the LOWER WEIGHTED MEDIAN, the
+ *                   smallest r whose weight at or below it reaches the weight above it - integer sums, found by a weighted radix select.  The
+ *                   descent starts at the lowest index holding the lower median of p and takes one step.  At a vertex (j, S): Z = the points
+ *                   whose slope through j equals S, one (lowest index) per distinct q; for each z of Z in index order, with pivot z, B / A = the
+ *                   weight of the slopes below / above S and W the total; S is optimal along z's line iff 2B <= W and 2A <= W.  The first z
+ *                   that fails becomes the pivot of the next step; when none fails the vertex is the minimiser.  s = S and
+ *                   t = double(g_j) - s * (double(q_j) * 2^(E - 36)), each rounded once to float32.  Every q equal: s = 0, t = the lower median of
+ *                   gt.  At most 64 steps and 4096 tied points at a vertex; past either cap the current vertex is returned and the call still
+ *                   succeeds (ug_eval_depth_l1_info reports certified = 0).  2^26 valid pixels or more, or a non-finite prediction, is an error.
+ *                   Scratch comes from the workspace: 12 bytes per valid pixel plus 100 KB; a workspace too small for it is an error
  * out11 as ug_eval_depth.  err_map_out (host, [n], may be NULL) = |s * pred + t - gt| / gt on mask1 and 0 elsewhere, from the ORIGINAL
  * (unclipped) prediction - the reference's second return value.  No valid pixel: zero metrics, (s, t) = (1, 0) for METRIC, (0, 0) otherwise.
  * An unknown alignment is an error (ug_last_error).  With the default options the result equals ug_eval_depth's bit for bit.
  * align_with_lad / align_with_lad2 (BFGS / 1000-step Adam on a non-smooth objective: no reproducible answer) and disp_input (calls a
- * function the reference never defines) have no counterpart. */
-enum { UG_ALIGN_LSTSQ = 0, UG_ALIGN_MEDIAN = 1, UG_ALIGN_SCALE = 2, UG_ALIGN_METRIC = 3 };
+ * function the reference never defines) have no counterpart; UG_ALIGN_L1 returns the exact minimiser of the objective lad / lad2 approach. */
+enum { UG_ALIGN_LSTSQ = 0, UG_ALIGN_MEDIAN = 1, UG_ALIGN_SCALE = 2, UG_ALIGN_METRIC = 3, UG_ALIGN_L1 = 4 };
 typedef struct { int alignment; float max_depth;            /* <= 0 or NaN: gt > 0 only */
                  float pre_clip_min, pre_clip_max, post_clip_min, post_clip_max; /* NaN: off */ } ug_depth_eval_opts;
 void ug_depth_eval_opts_default(ug_depth_eval_opts* o);     /* LSTSQ, 80, all clips off */
 int ug_eval_depth_ex(ug_ctx* ctx, const float* pred_depth /* NULL: resident depth */, const float* gt_depth, const unsigned char* custom_mask,
                      long n, const ug_depth_eval_opts* opts, double* out11, float* err_map_out /* [n] or NULL */);
+/* How the last UG_ALIGN_L1 evaluation on this context ended: out_info[4] = j, k (the two valid pixels, counted in pixel order, that the fitted
+ * line passes through; -1 where there is none), the number of pivot steps, certified (1: the vertex passed every check; 0: a cap was met). */
+int ug_eval_depth_l1_info(ug_ctx* ctx, long* out_info /*[4]*/);
 /* Depth evaluation in global coordinates: the reference's depth_evaluation_in_global_coord (metrics/eval_depth.py:250-441,
  * utils/geometry_utils.py:246-253).  mask1 = gt_depth > 0 (and gt_depth < max_depth) - from the ground-truth DEPTH, never
  * from the radius.  Fit 1: least squares (s_d, t_d) of clamp(pred, pre_clip) against gt_depth on mask1.  Every pixel, from the ORIGINAL

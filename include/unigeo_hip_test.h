@@ -120,6 +120,11 @@ int ug_op_u8_to_frames(ug_ctx* ctx, const unsigned char* frames_tchw, int T, int
  * pixels that is.  NaN clip bounds are off.  count = 0 leaves the medians 0. */
 int ug_op_masked_median(ug_ctx* ctx, const float* pred, const float* gt, long n, float max_depth, float pre_clip_min, float pre_clip_max,
                         float* out_medians /*[2]*/, long* out_count);
+/* The exact L1 scale-and-shift fit behind UG_ALIGN_L1 alone (kernels/metrics.hip; the definition stands with UG_ALIGN_L1 in
+ * unigeo_hip.h): opts gives max_depth and the pre-clip bounds, the other fields are not read.  out_st = (s, t) in double, before the rounding to
+ * float32; out_info = j, k, steps, certified as ug_eval_depth_l1_info.  No valid pixel: (0, 0) and j = k = -1; every q equal: k = -1, steps = 0. */
+int ug_op_l1_fit(ug_ctx* ctx, const float* pred /* NULL: resident depth */, const float* gt, long n, const ug_depth_eval_opts* opts,
+                 double* out_st /*[2]*/, long* out_info /*[4]*/);
 /* The kernels behind ug_eval_pcd one by one (kernels/pcd.hip).
  *   ug_op_pcd_nn         : nearest target of every query, float64 [n,3] each, the query first moved by T44 (row-major 4x4, may be NULL) as
  *                          ((r0 x + r1 y) + r2 z) + t -> idx_out [nq], dist_out [nq] = sqrt of the smallest (dx*dx + dy*dy) + dz*dz, ties to the

@@ -8,6 +8,7 @@ import ctypes as C
 import dataclasses
 import json
 import os
+import warnings
 
 import numpy as np
 
@@ -19,7 +20,7 @@ EXPORTS = [
     "ug_create", "ug_destroy", "ug_last_error", "ug_workspace_peak",
     "ug_load_tensor", "ug_bind_unet", "ug_bind_vae", "ug_bind_clip",
     "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_dc_set_inputs_ex", "ug_dc_get_noise", "ug_op_philox_u32", "ug_op_randn", "ug_op_u8_to_frames", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
-    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
+    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_eval_depth_l1_info", "ug_op_l1_fit", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
@@ -75,7 +76,7 @@ class RegisterOptsC(C.Structure):
                 ("max_valid", C.c_float), ("flags", C.c_uint)]
 
 
-DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3}    # UG_ALIGN_* of include/unigeo_hip.h
+DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3, "l1": 4}    # UG_ALIGN_* of include/unigeo_hip.h
 PREP_DEPTH_F64, PREP_ZOOMED = 1, 2                                       # UG_PREP_* of include/unigeo_hip.h
 REG_DROP_SENTINEL = 1                                                    # UG_REG_* of include/unigeo_hip.h
 
@@ -139,6 +140,8 @@ def load_library():
     lib.ug_eval_depth_ex.argtypes = [vp, vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_eval_depth_global.argtypes = [vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp]
     lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
+    _set_argtypes(lib, {"ug_eval_depth_l1_info": [vp, C.POINTER(C.c_long)],
+                        "ug_op_l1_fit": [vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, C.POINTER(C.c_long)]})
     lib.ug_pcd_opts_default.restype = None
     _set_argtypes(lib, {"ug_pcd_opts_default": [C.POINTER(PcdOptsC)],
                         "ug_pcd_world_points": [vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp],
@@ -260,6 +263,8 @@ class Engine:
         if not self.ctx:
             raise RuntimeError("ug_create failed: " + self.lib.ug_last_error(None).decode())
         self.device_id = device_id
+        self.l1_info = None          # j, k, steps, certified of the last eval_depth(alignment="l1")
+        self._l1_warned = False
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -568,8 +573,9 @@ class Engine:
     def eval_depth(self, gt, mask=None, pred=None, max_depth=80.0, alignment="lstsq", pre_clip_min=None, pre_clip_max=None,
                    post_clip_min=None, post_clip_max=None, return_error_map=False):
         """Depth metrics on the device -> ``(res, (s, t))``, with ``return_error_map=True`` ``(res, (s, t), error_map)``.
-        ``alignment``: "lstsq" | "median" | "scale" | "metric" (``ug_eval_depth_ex``); the clip bounds clamp the
-        prediction before / after the alignment; ``max_depth=None`` keeps every ``gt > 0``.  The defaults call ``ug_eval_depth``."""
+        ``alignment``: "lstsq" | "median" | "scale" | "metric" (``ug_eval_depth_ex``) | "l1" (the exact L1 scale and
+        shift; ``l1_info``, None until then, holds j, k, steps, certified, and an uncertified fit warns once); the clip bounds clamp
+        the prediction before / after the alignment; ``max_depth=None`` keeps every ``gt > 0``.  The defaults call ``ug_eval_depth``."""
         if alignment not in DEPTH_ALIGNMENTS:
             raise ValueError(f"alignment must be one of {sorted(DEPTH_ALIGNMENTS)}, not {alignment!r}")
         g = _f32(gt); n = g.size
@@ -585,6 +591,14 @@ class Engine:
                                *[float("nan") if c is None else float(c) for c in clips])
             emap = np.empty(g.shape, np.float32) if return_error_map else None
             self._ck(self.lib.ug_eval_depth_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, C.byref(o), _ptr(out), _ptr(emap)))
+            if alignment == "l1":
+                info = (C.c_long * 4)()
+                self._ck(self.lib.ug_eval_depth_l1_info(self.ctx, info))
+                self.l1_info = dict(zip(("j", "k", "steps", "certified"), (int(v) for v in info)))
+                if not self.l1_info["certified"] and not self._l1_warned:
+                    self._l1_warned = True
+                    warnings.warn("eval_depth(alignment='l1'): the descent met a cap (64 steps or 4096 tied points) and returned an uncertified "
+                                  "vertex; further such fits on this engine are not reported", RuntimeWarning, stacklevel=2)
         res = dict(zip(self.DEPTH_KEYS, out[:8].tolist()))
         res["valid_pixels"] = int(out[8])
         if return_error_map:
@@ -793,6 +807,18 @@ class Engine:
         nbr, nrm = np.empty((len(p), min(knn, len(p))), np.int32), np.empty((len(p), 3), np.float64)
         self._ck(self.lib.ug_op_pcd_knn_normals(self.ctx, _ptr(p), len(p), int(knn), _ptr(nbr), _ptr(nrm)))
         return nbr, nrm
+
+    def op_l1_fit(self, gt, pred=None, max_depth=80.0, pre_clip_min=None, pre_clip_max=None):
+        """The exact L1 scale-and-shift fit alone (``ug_op_l1_fit``) -> ``(s, t, info)`` as ``harness.metrics.l1_fit``
+        of the clamped prediction and ``gt`` over the valid ``gt``; ``pred=None`` fits the resident depth."""
+        g = _f32(gt).reshape(-1)
+        p = None if pred is None else _f32(pred).reshape(-1)
+        nan = float("nan")
+        o = DepthEvalOptsC(DEPTH_ALIGNMENTS["l1"], nan if max_depth is None else float(max_depth),
+                           nan if pre_clip_min is None else float(pre_clip_min), nan if pre_clip_max is None else float(pre_clip_max), nan, nan)
+        st = np.zeros(2, np.float64); info = (C.c_long * 4)()
+        self._ck(self.lib.ug_op_l1_fit(self.ctx, _ptr(p), _ptr(g), g.size, C.byref(o), _ptr(st), info))
+        return float(st[0]), float(st[1]), dict(zip(("j", "k", "steps", "certified"), (int(v) for v in info)))
 
     def op_masked_median(self, pred, gt, max_depth=80.0, pre_clip_min=None, pre_clip_max=None):
         """The exact masked selection alone -> (lower median of clamp(pred), lower median of gt, count) over the valid ``gt``."""

@@ -502,7 +502,7 @@ int ug_eval_depth_ex(ug_ctx* x, const float* pred, const float* gt, const unsign
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
     UG_REQUIRE(o != nullptr, "options must not be NULL");
-    UG_REQUIRE(o->alignment >= UG_ALIGN_LSTSQ && o->alignment <= UG_ALIGN_METRIC, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC)");
+    UG_REQUIRE(o->alignment >= UG_ALIGN_LSTSQ && o->alignment <= UG_ALIGN_L1, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC / L1)");
     UG_REQUIRE(n >= 0 && n < (1L << 32), "pixel count");
     const bool clips = !std::isnan(o->pre_clip_min) || !std::isnan(o->pre_clip_max) || !std::isnan(o->post_clip_min) || !std::isnan(o->post_clip_max);
     if (o->alignment == UG_ALIGN_LSTSQ && !clips && !emap_out && o->max_depth > 0.f) {   // what ug_eval_depth computes: its launches, its bits
@@ -531,11 +531,22 @@ int ug_eval_depth_ex(ug_ctx* x, const float* pred, const float* gt, const unsign
       double r[2];
       UG_CHECK(hipMemcpy(r, wz, sizeof(r), hipMemcpyDeviceToHost));
       if (r[1] >= 1) s_ = r[0] < 1e-3 ? 1e-3 : r[0];
+    } else if (o->alignment == UG_ALIGN_L1) {
+      double st[2];
+      l1_fit_device(c, d.dp, d.dg, n, md, lo, hi, st, x->l1_info);
+      s_ = (float)st[0]; t_ = (float)st[1];      // rounded once to float32, as least squares returns them
     } else s_ = 1.0;
     float* dmap = emap_out ? c.ws.get<float>(n) : nullptr;
-    launch_depth_metrics_ex(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, (float)s_, (float)t_, part, dmap, &nb, c.stream);
+    launch_depth_metrics_ex(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, (float)s_, (float)t_, part, dmap, &nb, c.stream, o->alignment == UG_ALIGN_L1);
     fetch_depth_metrics(c, part, nb, s_, t_, out);
     if (emap_out) UG_CHECK(hipMemcpy(emap_out, dmap, n * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int ug_eval_depth_l1_info(ug_ctx* x, long* out_info) {
+  UG_TRY(x, {
+    UG_REQUIRE(out_info != nullptr, "out_info must not be NULL");
+    for (int i = 0; i < 4; ++i) out_info[i] = x->l1_info[i];
   });
 }
 

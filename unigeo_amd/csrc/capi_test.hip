@@ -260,6 +260,18 @@ int ug_op_masked_median(ug_ctx* x, const float* pred, const float* gt, long n, f
   });
 }
 
+int ug_op_l1_fit(ug_ctx* x, const float* pred, const float* gt, long n, const ug_depth_eval_opts* o, double* out_st, long* out_info) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(o && out_st && out_info, "opts, out_st and out_info must not be NULL");
+    UG_REQUIRE(n >= 0 && n < (1L << 32), "pixel count");
+    if (n == 0) { out_st[0] = out_st[1] = 0.0; out_info[0] = out_info[1] = -1; out_info[2] = 0; out_info[3] = 1; return 0; }
+    UG_REQUIRE(gt != nullptr, "gt must not be NULL");
+    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, nullptr, n);
+    l1_fit_device(c, d.dp, d.dg, n, depth_bound(o->max_depth), clip_lo(o->pre_clip_min), clip_hi(o->pre_clip_max), out_st, out_info);
+  });
+}
+
 // the kernels of ug_eval_pcd one by one (kernels/pcd.hip)
 int ug_op_pcd_nn(ug_ctx* x, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out) {
   UG_TRY(x, {

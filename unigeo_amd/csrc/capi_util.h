@@ -15,7 +15,7 @@
 
 using namespace ug;
 
-struct ug_ctx { Ctx c; };
+struct ug_ctx { Ctx c; long l1_info[4] = {-1, -1, 0, 1}; };   // l1_info: j, k, steps, certified of the last UG_ALIGN_L1 evaluation
 
 #define UG_TRY(ctx, ...)                                   \
   if (!(ctx)) return -1;                                   \
@@ -157,4 +157,95 @@ static inline void read_masked_median(Ctx& c, const unsigned* sel, unsigned& cou
   unsigned r[3];
   UG_CHECK(hipMemcpy(r, sel + SEL_COUNT, sizeof(r), hipMemcpyDeviceToHost));
   count = r[0]; memcpy(&mp, &r[1], 4); memcpy(&mg, &r[2], 4);
+}
+
+// ------------------------------------------------------------------ exact L1 alignment: what ug_eval_depth_ex (product) and ug_op_l1_fit (test) share
+// t = g_j - s * (q_j * 2^(E - 36)), product and difference rounded separately
+static inline double l1_shift(double s, double gj, double qj, double down) {
+#pragma clang fp contract(off)
+  const double x = qj * down;
+  const double sx = s * x;
+  return gj - sx;
+}
+// The host loop over the kernels of kernels/metrics.hip: dp / dg are the n device pixels; st2 = (s, t) in double, info = j, k, steps, certified
+// (indices among the valid pixels in pixel order, -1 where there is none).  Leaves the stream idle.
+static inline void l1_fit_device(Ctx& c, const float* dp, const float* dg, long n, float md, float lo, float hi, double* st2, long* info) {
+  typedef unsigned long long u64;
+  st2[0] = st2[1] = 0.0;
+  info[0] = info[1] = -1; info[2] = 0; info[3] = 1;
+  if (n == 0) return;
+  unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
+  unsigned* aux = c.ws.get<unsigned>(L1_AUX_WORDS);
+  launch_masked_median(dp, dg, n, md, lo, hi, sel, c.stream);
+  launch_l1_maxabs(dp, dg, n, md, lo, hi, aux, c.stream);
+  UG_CHECK(hipGetLastError());
+  unsigned cnt; float mp, mg;
+  read_masked_median(c, sel, cnt, mp, mg);
+  if (cnt == 0) return;
+  UG_REQUIRE(cnt < (1u << 26), "l1 alignment: 2^26 valid pixels or more (the integer weights must sum below 2^63)");
+  unsigned mbits;
+  UG_CHECK(hipMemcpy(&mbits, aux, 4, hipMemcpyDeviceToHost));
+  float m; memcpy(&m, &mbits, 4);
+  UG_REQUIRE(std::isfinite(m), "l1 alignment: non-finite prediction");
+  int E = 0;
+  if (m > 0.f) (void)frexp((double)m, &E);      // m = f * 2^E with 0.5 <= f < 1: the smallest E with m < 2^E
+  const double up = ldexp(1.0, L1_BITS - E), down = ldexp(1.0, E - L1_BITS);
+  long long* qc = c.ws.get<long long>(cnt); float* gc = c.ws.get<float>(cnt);
+  u64* st = c.ws.get<u64>(L1_WORDS);
+  unsigned* tie_idx = c.ws.get<unsigned>(L1_MAX_TIES); long long* tie_q = c.ws.get<long long>(L1_MAX_TIES);
+  launch_l1_compact(dp, dg, n, md, lo, hi, aux, up, mp, cnt, qc, gc, c.stream);
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  unsigned j0;
+  UG_CHECK(hipMemcpy(&j0, aux + 1, 4, hipMemcpyDeviceToHost));
+  UG_REQUIRE(j0 < cnt, "l1 alignment: the median of the prediction was not found among the valid pixels");
+  long pivot = j0, j = j0, k = -1;
+  int steps = 0, certified = 1;
+  double S = 0.0;
+  std::vector<unsigned> ti; std::vector<long long> tq; std::vector<std::pair<unsigned, long long>> tied;
+  for (;;) {
+    launch_l1_step(qc, gc, cnt, pivot, down, st, tie_idx, tie_q, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    u64 r[5];      // key, target, W, lowest tied index, tied count
+    UG_CHECK(hipMemcpy(r, st + L1_PREFIX, sizeof(r), hipMemcpyDeviceToHost));
+    if (r[2] == 0) {      // every q equals the pivot's (the first step only): s = 0, t = the lower median of gt
+      st2[1] = mg; info[0] = j0;
+      return;
+    }
+    ++steps; j = pivot; S = pcd_unkey_f64(r[0]); k = (long)r[3];
+    UG_REQUIRE(r[4] >= 1 && k >= 0 && k < (long)cnt, "l1 alignment: the selected slope belongs to no point");
+    if (r[4] > L1_MAX_TIES) { certified = 0; break; }
+    const size_t nt = (size_t)r[4];
+    ti.resize(nt); tq.resize(nt); tied.resize(nt);
+    UG_CHECK(hipMemcpy(ti.data(), tie_idx, nt * 4, hipMemcpyDeviceToHost));
+    UG_CHECK(hipMemcpy(tq.data(), tie_q, nt * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nt; ++i) { UG_REQUIRE(ti[i] < cnt, "l1 alignment: tied index out of range"); tied[i] = {ti[i], tq[i]}; }
+    // one point per distinct q, the lowest index of each, in index order
+    std::sort(tied.begin(), tied.end(), [](const auto& a, const auto& b) { return a.second != b.second ? a.second < b.second : a.first < b.first; });
+    tied.erase(std::unique(tied.begin(), tied.end(), [](const auto& a, const auto& b) { return a.second == b.second; }), tied.end());
+    std::sort(tied.begin(), tied.end());
+    long next = -1;
+    for (size_t b0 = 0; b0 < tied.size() && next < 0; b0 += L1_CHK_SLOTS) {
+      const size_t nb = std::min(tied.size() - b0, (size_t)L1_CHK_SLOTS);
+      UG_CHECK(hipMemsetAsync(st + L1_CHK, 0, L1_CHK_SLOTS * 3 * sizeof(u64), c.stream));
+      for (size_t i = 0; i < nb; ++i) launch_l1_check(qc, gc, cnt, (long)tied[b0 + i].first, S, down, st + L1_CHK + 3 * i, c.stream);
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      u64 chk[L1_CHK_SLOTS * 3];
+      UG_CHECK(hipMemcpy(chk, st + L1_CHK, sizeof(chk), hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < nb && next < 0; ++i) {
+        const u64 B = chk[3 * i], A = chk[3 * i + 1], W = chk[3 * i + 2];
+        if (B > W - B || A > W - A) next = (long)tied[b0 + i].first;
+      }
+    }
+    if (next < 0) break;
+    if (steps == L1_MAX_STEPS) { certified = 0; break; }
+    pivot = next;
+  }
+  long long qj; float gj;
+  UG_CHECK(hipMemcpy(&qj, qc + j, 8, hipMemcpyDeviceToHost));
+  UG_CHECK(hipMemcpy(&gj, gc + j, 4, hipMemcpyDeviceToHost));
+  st2[0] = S; st2[1] = l1_shift(S, (double)gj, (double)qj, down);
+  info[0] = j; info[1] = k; info[2] = steps; info[3] = certified;
 }

@@ -287,7 +287,27 @@ void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float ma
                             double* part, hipStream_t s);
 void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s);
 void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
-                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s);
+                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s, bool unfused = false);
+// exact L1 scale-and-shift alignment (kernels/metrics.hip): state words (unsigned 64-bit) and caps
+#define L1_BITS 36            // q = rint(p * 2^(L1_BITS - E))
+#define L1_MAX_STEPS 64
+#define L1_MAX_TIES 4096
+#define L1_CHK_SLOTS 8        // vertex checks launched per readback
+#define L1_HIST 0             // 8 passes x 256 bins
+#define L1_PREFIX 2048
+#define L1_TARGET 2049
+#define L1_W 2050
+#define L1_TIE_MIN 2051
+#define L1_TIE_CNT 2052
+#define L1_CHK 2053           // L1_CHK_SLOTS x (below, above, total)
+#define L1_WORDS 2080
+#define L1_AUX_WORDS (1024 + 2)   // unsigned words: the bits of max |p|, j0, one count per block
+void launch_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, hipStream_t s);
+void launch_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, double up, float med,
+                       unsigned cap, long long* qc, float* gc, hipStream_t s);
+void launch_l1_step(const long long* qc, const float* gc, long nv, long j, double down, unsigned long long* st, unsigned* tie_idx,
+                    long long* tie_q, hipStream_t s);
+void launch_l1_check(const long long* qc, const float* gc, long nv, long z, double S, double down, unsigned long long* out3, hipStream_t s);
 // depth evaluation in global coordinates (kernels/metrics.hip); cam: 16 doubles per frame = fx, fy, cx, cy, R row-major, t
 void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s);

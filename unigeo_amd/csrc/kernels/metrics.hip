@@ -7,6 +7,7 @@
 // All reductions are two-stage with a fixed order (per-block fp64 partials, summed by the host in block order), the
 // median is an exact two-pass histogram selection with integer atomics: results are deterministic.
 #include "../common.h"
+#include <utility>
 
 #define MB 256   // threads per block
 #define MAXB 1024
@@ -237,8 +238,18 @@ __global__ __launch_bounds__(MB) void k_depth_fit_ex(const float* pred, const fl
 }
 
 // k_depth_metrics of p' = clamp(s * clamp(p, lo, hi) + t, plo, phi); optional error map |s * pred + t - gt| / gt on mask1 (0 elsewhere) from
-// the ORIGINAL prediction.  The product and the sum round separately, as the reference's tensor expressions do: a fused multiply-add moves
-// the map by more than its tolerance where the residual is small.
+// the ORIGINAL prediction.  The reference's tensor expressions round the product and the sum separately; a fused multiply-add moves the map
+// by more than its tolerance where the residual is small.
+// UNFUSED: in this toolchain __fmul_rn / __fadd_rn are plain operators, and the default instantiation's s * p + t does come out as one fused
+// operation (see world_point below).  With t = 0 (median, scale, metric) that changes no bit, and least squares is compared within a tolerance; the
+// L1 alignment's line passes through two of the pixels, where the residual is a rounding error and the fused form differs from the host's in every
+// digit.  It instantiates the kernel with contraction off; the other modes keep the code, and the bytes, they had.
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float m = a * b;
+  return m + c;
+}
+template <bool UNFUSED>
 __global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n,
                                                          float max_depth, float lo, float hi, float plo, float phi, float s, float t,
                                                          double* part, float* emap) {
@@ -248,9 +259,9 @@ __global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, cons
     const float g = gt[i];
     const bool v1 = depth_valid(g, max_depth);
     const float p0 = pred[i];
-    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(__fadd_rn(__fmul_rn(p0, s), t), g)) / g : 0.f;
+    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(UNFUSED ? mul_add_unfused(p0, s, t) : __fadd_rn(__fmul_rn(p0, s), t), g)) / g : 0.f;
     if (v1 && (!cmask || cmask[i])) {
-      const float p = clipf(__fadd_rn(__fmul_rn(s, clipf(p0, lo, hi)), t), plo, phi);
+      const float p = clipf(UNFUSED ? mul_add_unfused(s, clipf(p0, lo, hi), t) : __fadd_rn(__fmul_rn(s, clipf(p0, lo, hi)), t), plo, phi);
       metric_terms(p, g, a);
     }
   }
@@ -387,9 +398,10 @@ void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_d
   hipLaunchKernelGGL(k_depth_fit_ex, dim3(*nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, part);
 }
 void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
-                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s) {
+                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s, bool unfused) {
   *nb = nblocks(n);
-  hipLaunchKernelGGL(k_depth_metrics_ex, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
+  if (unfused) hipLaunchKernelGGL(k_depth_metrics_ex<true>, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
+  else hipLaunchKernelGGL(k_depth_metrics_ex<false>, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
 }
 void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s) {
@@ -404,4 +416,227 @@ void launch_radius_metrics(const float* radius, const float* gt, const float* gt
                            float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s) {
   *nb = nblocks(n);
   hipLaunchKernelGGL(k_radius_metrics, dim3(*nb), dim3(MB), 0, s, radius, gt, gt_radius, cmask, n, max_depth, sc, sh, part, rmap);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Exact L1 scale-and-shift alignment (UG_ALIGN_L1): min over (s, t) of sum |s p_i + t - g_i| on mask1.  The pre-clipped
+// prediction is held as the integers q = rint(p * 2^(36 - E)), E the smallest integer with max |p| < 2^E, so every weight |q_i - q_j| and every
+// sum of weights is an exact integer; q and g of the valid pixels are compacted once, in pixel order.  One step from pivot j is a WEIGHTED
+// radix select - the lower weighted median of the slopes r_i = (g_i - g_j) / ((q_i - q_j) * 2^(E - 36)) with the weights |q_i - q_j| - over the
+// order-preserving 64-bit key of r_i, 8 bits per pass, then a pass that collects the points whose slope equals the result.  The host
+// (capi_util.h: l1_fit_device) walks from vertex to vertex with k_l1_check.  Every accumulated quantity is an integer: no result depends on the
+// order in which workgroups arrive.  State words (unsigned 64-bit, offsets in common.h): L1_HIST + pass * 256 + bin, L1_PREFIX the key bits
+// fixed so far, L1_TARGET the weight still to reach inside that prefix, L1_W the total weight, L1_TIE_MIN / L1_TIE_CNT the lowest index and
+// the number of points whose key equals the selected one, L1_CHK + 3 * slot the sums (below, above, total) of one k_l1_check.
+typedef unsigned long long u64;
+
+// the valid pixels are compacted in pixel order: block b owns the pixels [b * chunk, (b + 1) * chunk), chunk a multiple of the block size
+static long l1_chunk(long n, int nb) { const long c = (n + nb - 1) / nb; return (c + MB - 1) / MB * MB; }
+
+__device__ __forceinline__ double l1_slope(long long dq, float gi, double gj, double down) {
+#pragma clang fp contract(off)
+  const double r = ((double)gi - gj) / ((double)dq * down);
+  return r == 0.0 ? 0.0 : r;      // -0.0 -> 0.0
+}
+
+// the bits of max |clamp(pred)| over mask1 (integer atomicMax: non-negative floats order as their bits do) and every block's count of valid pixels
+__global__ __launch_bounds__(MB) void k_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, long chunk,
+                                                  unsigned* maxbits, unsigned* bcount) {
+  __shared__ unsigned sm[MB], sc[MB];
+  const int tid = threadIdx.x;
+  const long beg = (long)blockIdx.x * chunk, end = beg + chunk < n ? beg + chunk : n;
+  unsigned mx = 0, cnt = 0;
+  for (long i = beg + tid; i < end; i += MB) {
+    if (!depth_valid(gt[i], max_depth)) continue;
+    const unsigned b = __float_as_uint(fabsf(clipf(pred[i], lo, hi)));
+    mx = b > mx ? b : mx; ++cnt;
+  }
+  sm[tid] = mx; sc[tid] = cnt;
+  __syncthreads();
+  for (int o = MB / 2; o > 0; o >>= 1) {
+    if (tid < o) { sm[tid] = sm[tid + o] > sm[tid] ? sm[tid + o] : sm[tid]; sc[tid] += sc[tid + o]; }
+    __syncthreads();
+  }
+  if (tid == 0) { if (sm[0]) atomicMax(maxbits, sm[0]); bcount[blockIdx.x] = sc[0]; }
+}
+
+// q = rint(clamp(pred) * up) and gt of the valid pixels, written in pixel order: a block starts at the sum of the counts of the blocks before
+// it and scans each of its 256-pixel tiles.  *j0 = the lowest compacted index whose clamped prediction equals med.  cap = the compacted length.
+// launch_pcd_compact (kernels/pcd.hip) keeps the same order but copies float32 pairs on the custom mask; this one selects on mask1, clamps and
+// quantises as it writes and finds j0 in the same trip, and the block counts come from k_l1_maxabs, which reads the pixels anyway.
+__global__ __launch_bounds__(MB) void k_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, long chunk,
+                                                   const unsigned* bcount, double up, float med, unsigned cap, long long* qc, float* gc,
+                                                   unsigned* j0) {
+  __shared__ unsigned sc[MB];
+  const int tid = threadIdx.x;
+  unsigned part = 0;
+  for (int b = tid; b < (int)blockIdx.x; b += MB) part += bcount[b];
+  sc[tid] = part;
+  __syncthreads();
+  for (int o = MB / 2; o > 0; o >>= 1) {
+    if (tid < o) sc[tid] += sc[tid + o];
+    __syncthreads();
+  }
+  unsigned running = sc[0];
+  __syncthreads();
+  const long beg = (long)blockIdx.x * chunk, end = beg + chunk < n ? beg + chunk : n;
+  for (long t0 = beg; t0 < end; t0 += MB) {
+    const long i = t0 + tid;
+    const float g = i < end ? gt[i] : 0.f;
+    const bool v = i < end && depth_valid(g, max_depth);
+    sc[tid] = v;
+    __syncthreads();
+    for (int o = 1; o < MB; o <<= 1) {
+      const unsigned a = tid >= o ? sc[tid - o] : 0u;
+      __syncthreads();
+      sc[tid] += a;
+      __syncthreads();
+    }
+    const unsigned pos = running + sc[tid] - 1u;
+    running += sc[MB - 1];
+    if (v && pos < cap) {
+      const float p = clipf(pred[i], lo, hi);
+      qc[pos] = __double2ll_rn((double)p * up);
+      gc[pos] = g;
+      if (p == med) atomicMin(j0, pos);
+    }
+    __syncthreads();
+  }
+}
+
+// one 8-bit pass of the weighted select: the weight |q_i - q_j| of every point whose key matches the prefix goes into the bin of its next 8 bits.
+// A thread sums the weights of consecutive points that fall into one bin in a register and issues the LDS atomic only when the bin changes:
+// in the first passes (sign and exponent bits) nearly every slope shares a bin, and one atomic per point would serialise on that address.
+// The sums are integers, so the grouping changes no bit.
+template <int PASS>
+__global__ __launch_bounds__(MB) void k_l1_hist(const long long* qc, const float* gc, long nv, long j, double down, u64* st) {
+  __shared__ u64 h[256];
+  const int tid = threadIdx.x;
+  h[tid] = 0;
+  __syncthreads();
+  constexpr int shift = 56 - 8 * PASS;
+  const long long qj = qc[j];
+  const double gj = gc[j];
+  const u64 prefix = st[L1_PREFIX];
+  unsigned bin = 0;
+  u64 run = 0;
+  for (long i = (long)blockIdx.x * MB + tid; i < nv; i += (long)gridDim.x * MB) {
+    const long long dq = qc[i] - qj;
+    if (dq == 0) continue;
+    const u64 key = pcd_key(l1_slope(dq, gc[i], gj, down));
+    if constexpr (PASS > 0) { if ((key >> (shift + 8)) != (prefix >> (shift + 8))) continue; }
+    const unsigned b = (unsigned)(key >> shift) & 255u;
+    if (b != bin) {
+      if (run) atomicAdd(&h[bin], run);
+      bin = b; run = 0;
+    }
+    run += (u64)(dq < 0 ? -dq : dq);
+  }
+  if (run) atomicAdd(&h[bin], run);
+  __syncthreads();
+  const u64 c = h[tid];
+  if (c) atomicAdd(&st[L1_HIST + PASS * 256 + tid], c);
+}
+
+// one workgroup: the bin in which the running weight first reaches the target; pass 0 sets the target ceil(W / 2) and arms the tie words
+template <int PASS>
+__global__ __launch_bounds__(256) void k_l1_scan(u64* st) {
+  __shared__ u64 sc[256];
+  const int tid = threadIdx.x;
+  constexpr int shift = 56 - 8 * PASS;
+  const u64 cnt = st[L1_HIST + PASS * 256 + tid];
+  sc[tid] = cnt;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const u64 v = tid >= o ? sc[tid - o] : 0ull;
+    __syncthreads();
+    sc[tid] += v;
+    __syncthreads();
+  }
+  const u64 incl = sc[tid], excl = incl - cnt, total = sc[255];
+  const u64 target = PASS == 0 ? total / 2 + (total & 1ull) : st[L1_TARGET];
+  __syncthreads();   // every thread has read the target before one of them writes
+  if (PASS == 0 && tid == 0) { st[L1_W] = total; st[L1_TIE_MIN] = ~0ull; }
+  if (cnt && excl < target && target <= incl) {
+    st[L1_PREFIX] = st[L1_PREFIX] | ((u64)tid << shift);
+    st[L1_TARGET] = target - excl;
+  }
+}
+
+// the points whose slope through j has the selected key: the lowest index, how many, and the first L1_MAX_TIES of them (index and q, any order)
+__global__ __launch_bounds__(MB) void k_l1_tie(const long long* qc, const float* gc, long nv, long j, double down, u64* st, unsigned* tie_idx,
+                                               long long* tie_q) {
+  const long long qj = qc[j];
+  const double gj = gc[j];
+  const u64 want = st[L1_PREFIX];
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < nv; i += (long)gridDim.x * MB) {
+    const long long qi = qc[i], dq = qi - qj;
+    if (dq == 0 || pcd_key(l1_slope(dq, gc[i], gj, down)) != want) continue;
+    atomicMin(&st[L1_TIE_MIN], (u64)i);
+    const u64 c = atomicAdd(&st[L1_TIE_CNT], 1ull);
+    if (c < L1_MAX_TIES) { tie_idx[c] = (unsigned)i; tie_q[c] = qi; }
+  }
+}
+
+// with pivot z: the weight of the slopes below S, above S, and the total weight -> out3 (one 64-bit integer atomicAdd per block and sum)
+__global__ __launch_bounds__(MB) void k_l1_check(const long long* qc, const float* gc, long nv, long z, double S, double down, u64* out3) {
+  __shared__ u64 sh[3][MB];
+  const int tid = threadIdx.x;
+  const long long qz = qc[z];
+  const double gz = gc[z];
+  u64 a[3] = {0, 0, 0};
+  for (long i = (long)blockIdx.x * MB + tid; i < nv; i += (long)gridDim.x * MB) {
+    const long long dq = qc[i] - qz;
+    if (dq == 0) continue;
+    const double r = l1_slope(dq, gc[i], gz, down);
+    const u64 w = (u64)(dq < 0 ? -dq : dq);
+    if (r < S) a[0] += w;
+    if (r > S) a[1] += w;
+    a[2] += w;
+  }
+  for (int k = 0; k < 3; ++k) sh[k][tid] = a[k];
+  __syncthreads();
+  for (int o = MB / 2; o > 0; o >>= 1) {
+    if (tid < o) for (int k = 0; k < 3; ++k) sh[k][tid] += sh[k][tid + o];
+    __syncthreads();
+  }
+  if (tid < 3 && sh[tid][0]) atomicAdd(&out3[tid], sh[tid][0]);
+}
+
+// aux: [0] the bits of max |p|, [1] j0, [2 ..] MAXB block counts.  Counts the valid pixels per block and finds max |p|.
+void launch_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, hipStream_t s) {
+  const int nb = nblocks(n);
+  (void)hipMemsetAsync(aux, 0, 4, s);
+  (void)hipMemsetAsync(aux + 1, 0xff, 4, s);
+  hipLaunchKernelGGL(k_l1_maxabs, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, l1_chunk(n, nb), aux, aux + 2);
+}
+void launch_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, double up, float med,
+                       unsigned cap, long long* qc, float* gc, hipStream_t s) {
+  const int nb = nblocks(n);
+  hipLaunchKernelGGL(k_l1_compact, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, l1_chunk(n, nb), aux + 2, up, med, cap, qc, gc,
+                     aux + 1);
+}
+// one hist / scan pair of the weighted select, and the eight of them from the top byte of the key down
+template <int PASS>
+static void l1_select_pass(dim3 g, hipStream_t s, const long long* qc, const float* gc, long nv, long j, double down, u64* st) {
+  hipLaunchKernelGGL(k_l1_hist<PASS>, g, dim3(MB), 0, s, qc, gc, nv, j, down, st);
+  hipLaunchKernelGGL(k_l1_scan<PASS>, dim3(1), dim3(256), 0, s, st);
+}
+template <int... PASS>
+static void l1_select_passes(std::integer_sequence<int, PASS...>, dim3 g, hipStream_t s, const long long* qc, const float* gc, long nv, long j,
+                             double down, u64* st) {
+  (l1_select_pass<PASS>(g, s, qc, gc, nv, j, down, st), ...);
+}
+// one pivot step from point j of the nv compacted points: st ends with the selected key (L1_PREFIX), W, and the tie words; tie_idx / tie_q hold
+// L1_MAX_TIES entries
+void launch_l1_step(const long long* qc, const float* gc, long nv, long j, double down, u64* st, unsigned* tie_idx, long long* tie_q,
+                    hipStream_t s) {
+  (void)hipMemsetAsync(st, 0, L1_WORDS * sizeof(u64), s);
+  const dim3 g(nblocks(nv)), b(MB);
+  l1_select_passes(std::make_integer_sequence<int, 8>{}, g, s, qc, gc, nv, j, down, st);
+  hipLaunchKernelGGL(k_l1_tie, g, b, 0, s, qc, gc, nv, j, down, st, tie_idx, tie_q);
+}
+// out3 must be zero before the launch
+void launch_l1_check(const long long* qc, const float* gc, long nv, long z, double S, double down, u64* out3, hipStream_t s) {
+  hipLaunchKernelGGL(k_l1_check, dim3(nblocks(nv)), dim3(MB), 0, s, qc, gc, nv, z, S, down, out3);
 }

@@ -1,8 +1,8 @@
 """Host-side mirror of the reference harness (eval.py loop, GT preparation, depth / normal / point-cloud / camera metrics, CSV sink).
 Plain numpy / Python; the model call inside the loop is the only GPU work."""
 from .io_utils import prepare_gt_label
-from .metrics import (MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation, pcd_evaluation,
-                      world_points_from_depth)
+from .metrics import (MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, l1_fit, l1_objective, normal_evaluation,
+                      pcd_evaluation, world_points_from_depth)
 from .camera import camera_pose_evaluation, save_camera_trajectories, tum_poses, write_tum_trajectory
 from .pointmap import pointmap_focal, pointmap_poses, poses_from_pointmap
 from .eval import (evaluate, parse_camera_eval_config, parse_dataset_config, parse_depth_coord, parse_metric_config, parse_pcd_eval_config,
@@ -15,7 +15,7 @@ from .distributed import evaluate_sharded
 from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, read_ply, save_depth_normal_maps, write_ply
 
 __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_evaluation_in_global_coord",
-           "normal_evaluation", "pcd_evaluation", "world_points_from_depth", "evaluate", "parse_dataset_config", "parse_depth_coord",
+           "l1_fit", "l1_objective", "normal_evaluation", "pcd_evaluation", "world_points_from_depth", "evaluate", "parse_dataset_config", "parse_depth_coord",
            "parse_metric_config", "parse_pcd_eval_config", "parse_camera_eval_config", "import_class_from_module", "SyntheticGeometryDataset",
            "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence",
            "RGBDClipDataset", "RGBDSequence", "sevenScenesDataset", "bonnDataset", "neuralRGBDDataset", "replicaDataset", "ScannetV2Dataset",

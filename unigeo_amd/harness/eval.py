@@ -46,7 +46,7 @@ def parse_metric_config(config):
 
 
 def parse_depth_eval_config(config):
-    """``eval_depth.depth_alignment`` (lstsq | median | scale | metric, default lstsq), optional ``max_depth`` and the four clip keys ->
+    """``eval_depth.depth_alignment`` (lstsq | median | scale | metric | l1, default lstsq), optional ``max_depth`` and the four clip keys ->
     (alignment, max_depth, clips).  An unknown alignment is a ``ValueError``."""
     cfg = config.get("eval_depth") or {}
     alignment = cfg.get("depth_alignment", "lstsq")
@@ -124,7 +124,7 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     ``models`` = several instances of the plugin on ONE GPU (round 5): this rank's k-th clip runs on ``models[k % len(models)]``, each instance on its own host
     thread - independent clips in flight on one GPU, the sharding over GPUs one level down (+10 % aggregate frames/s with two DepthCrafter contexts: a second
     clip fills the CUs that one clip's tile tails and under-filled launches leave idle).  Rows / CSV come out in dataset order, identical to the serial loop.
-    ``eval_depth.depth_alignment`` (lstsq | median | scale | metric, default lstsq), ``eval_depth.max_depth`` and the four ``eval_depth.*_clip_*`` keys select
+    ``eval_depth.depth_alignment`` (lstsq | median | scale | metric | l1, default lstsq), ``eval_depth.max_depth`` and the four ``eval_depth.*_clip_*`` keys select
     the alignment of the depth metrics on both the host and the device path; an unknown value raises ``ValueError`` before the first clip runs.  A deliberate
     difference: the reference reads ``depth_alignment`` (eval.py:48) and always aligns with least squares.
     ``eval_depth.coord: global`` (default ``camera``) evaluates the depth in world coordinates instead: the radius
@@ -152,7 +152,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     coord = parse_depth_coord(config)
     pcd_cfg = parse_pcd_eval_config(config)
     cam_cfg = parse_camera_eval_config(config)
-    host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True}}[alignment]
+    host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True},
+                 "l1": {"align_with_l1": True}}[alignment]
     if dataset is None:
         dataset = import_class_from_module("unigeo_amd.harness", config["dataset"])(**parse_dataset_config(config))
     if model is None and not models:

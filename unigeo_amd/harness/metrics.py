@@ -12,7 +12,8 @@
   rmse / % under 5, 7.5, 11.25, 22.5, 30 degrees.
 * ``MetricsManager``    <- ``/root/reference/metrics/save_utils.py:5-90``: one row per sequence, NaN for missing
   metrics, trailing ``Average`` row (NaN-skipping mean), ``%.5f``.
-The lad / lad2 / disp_input modes of the reference function raise here (see ``depth_evaluation``).
+The lad / lad2 / disp_input modes of the reference function raise here (see ``depth_evaluation``); ``align_with_l1`` is the exact
+minimiser of the objective lad / lad2 approach (``l1_fit``).
 """
 import math
 import os
@@ -26,7 +27,95 @@ def _np(x):
     return np.asarray(x)
 
 
-DEPTH_ALIGNMENTS = ("lstsq", "median", "scale", "metric")
+DEPTH_ALIGNMENTS = ("lstsq", "median", "scale", "metric", "l1")
+
+L1_BITS, L1_MAX_STEPS, L1_MAX_TIES = 36, 64, 4096      # fixed-point bits of the prediction, and the two caps of the descent
+
+
+def _l1_quantise(p):
+    """``(q, E)``: ``E`` the smallest integer with ``max |p| < 2^E`` (0 for an all-zero ``p``), ``q = rint(p * 2^(36 - E))`` as int64.  The
+    product is exact, so a value within 12 binades of the largest keeps every bit."""
+    p = np.asarray(p, np.float32).reshape(-1)
+    m = float(np.max(np.abs(p))) if p.size else 0.0
+    E = math.frexp(m)[1] if m > 0 else 0
+    return np.rint(p.astype(np.float64) * math.ldexp(1.0, L1_BITS - E)).astype(np.int64), E
+
+
+def _l1_slopes(q, g64, j, down):
+    """Every ``i`` with ``q_i != q_j`` -> (indices, integer weights ``|q_i - q_j|``, float64 slopes through point ``j``)."""
+    dq = q - q[j]
+    idx = np.nonzero(dq)[0]
+    d = dq[idx]
+    r = (g64[idx] - g64[j]) / (d.astype(np.float64) * down)
+    return idx, np.abs(d), r + 0.0          # -0.0 + 0.0 = +0.0
+
+
+def _l1_step(q, g64, j, down):
+    """One pivot step: the lower weighted median ``S`` of the slopes through ``j`` and the indices whose slope equals it (index order);
+    ``None`` when every ``q`` equals ``q_j``."""
+    idx, w, r = _l1_slopes(q, g64, j, down)
+    if idx.size == 0:
+        return None
+    o = np.argsort(r, kind="stable")
+    cw = np.cumsum(w[o])
+    S = r[o[int(np.argmax(cw >= cw[-1] - cw))]]
+    return float(S), idx[r == S]
+
+
+def _l1_vertex_holds(q, g64, z, S, down):
+    """Is ``S`` optimal along the line of fits through ``z``: neither side of ``S`` holds more than half of the weight."""
+    _, w, r = _l1_slopes(q, g64, z, down)
+    B, A, W = int(w[r < S].sum()), int(w[r > S].sum()), int(w.sum())
+    return B <= W - B and A <= W - A
+
+
+def l1_fit(p, g):
+    """The exact least-absolute-deviations fit ``min sum |s p_i + t - g_i|`` of float32 ``p`` against float32 ``g``
+    -> ``(s, t, info)``, ``info = {j, k, steps, certified}``: the optimal line passes through points ``j`` and ``k`` (``k`` the lowest-index
+    partner of the last step).  ``p`` is held as the integers ``q = rint(p * 2^(36 - E))``, so that every weight ``|q_i - q_j|`` and every
+    sum of weights is an exact integer; a step from pivot ``j`` takes the lower weighted median of the slopes through ``j``, which minimises
+    the objective along the line of fits through that point.  The descent starts at the lowest index holding the lower median of ``p``;
+    at each vertex ``(j, S)`` every point ``z`` on the line (one per distinct ``q``, in index order) is asked whether ``S`` is also optimal
+    along ITS line, and the first that says no becomes the pivot.  When all agree the vertex is the minimiser.  ``certified = 0``: one of
+    the caps (64 steps, 4096 tied points) was met and the current vertex is returned.  No point: ``(0, 0)``; every ``q`` equal: ``s = 0``,
+    ``t`` the lower median of ``g``."""
+    p, g = np.asarray(p, np.float32).reshape(-1), np.asarray(g, np.float32).reshape(-1)
+    n = p.size
+    if n == 0:
+        return 0.0, 0.0, {"j": -1, "k": -1, "steps": 0, "certified": 1}
+    if n >= 1 << 26:
+        raise ValueError("l1_fit: 2^26 points or more (the integer weights must sum below 2^63)")
+    q, E = _l1_quantise(p)
+    down, g64 = math.ldexp(1.0, E - L1_BITS), g.astype(np.float64)
+    pivot = int(np.argmax(p == np.sort(p)[(n - 1) // 2]))
+    step = _l1_step(q, g64, pivot, down)
+    if step is None:
+        return 0.0, float(np.sort(g)[(n - 1) // 2]), {"j": pivot, "k": -1, "steps": 0, "certified": 1}
+    steps, certified = 1, 1
+    while True:
+        j, (S, tied) = pivot, step
+        if tied.size > L1_MAX_TIES:
+            certified = 0
+            break
+        _, first = np.unique(q[tied], return_index=True)          # the first occurrence of each distinct q; tied is in index order
+        nxt = next((int(z) for z in tied[np.sort(first)] if not _l1_vertex_holds(q, g64, int(z), S, down)), None)
+        if nxt is None:
+            break
+        if steps == L1_MAX_STEPS:
+            certified = 0
+            break
+        pivot, step, steps = nxt, _l1_step(q, g64, nxt, down), steps + 1
+    t = float(g64[j]) - S * (float(q[j]) * down)
+    return S, t, {"j": j, "k": int(tied[0]), "steps": steps, "certified": certified}
+
+
+def l1_objective(p, g, s, t):
+    """``sum |s p_i + t - g_i|`` in float64 and plain index order, on the de-quantised prediction ``q * 2^(E - 36)`` that ``l1_fit`` fits."""
+    g = np.asarray(g, np.float32).reshape(-1).astype(np.float64)
+    if g.size == 0:
+        return 0.0
+    q, E = _l1_quantise(p)
+    return float(np.cumsum(np.abs(float(s) * (q.astype(np.float64) * math.ldexp(1.0, E - L1_BITS)) + float(t) - g))[-1])
 
 
 def _scale_l1(p, g):
@@ -77,13 +166,14 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
                      post_clip_min=None, post_clip_max=None, pre_clip_min=None, pre_clip_max=None,
                      align_with_lstsq=False, align_with_lad=False, align_with_lad2=False, metric_scale=False,
                      align_with_scale=False, disp_input=False, lr=1e-4, max_iters=1000, use_gpu=False, return_error_map=False,
-                     **unsupported):
+                     align_with_l1=False, **unsupported):
     """``depth_evaluation`` of the reference (``metrics/eval_depth.py:59-204``) -> ``(res, (s, t))``, with
     ``return_error_map=True`` ``(res, (s, t), error_map)``.
 
     On mask1 = ``gt > 0`` (and ``gt < max_depth`` unless that is ``None``): clamp the prediction to the pre-clip bounds,
     align, clamp to the post-clip bounds, apply the custom mask, compute the metrics.  The alignment keeps the
-    reference's precedence: ``metric_scale`` (s = 1), then ``align_with_lstsq`` (scale and shift), then
+    reference's precedence: ``metric_scale`` (s = 1), then ``align_with_lstsq`` (scale and shift), then ``align_with_l1`` (the exact
+    least-absolute-deviations scale and shift of ``l1_fit``, rounded once to float32; in the place the reference gives lad), then
     ``align_with_scale`` (Weiszfeld L1 scale, here in float64 and plain index order; clamped to >= 1e-3), then the
     default: ``s = median(gt) / median(pred)`` with ``torch.median``'s LOWER median, element ``(n - 1) // 2`` of the
     sorted values.  The error map is ``|s * pred + t - gt| / gt`` on mask1 and 0 elsewhere, from the ORIGINAL prediction
@@ -92,7 +182,8 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
 
     Still rejected with ``NotImplementedError``: ``align_with_lad`` / ``align_with_lad2`` run a scipy BFGS and a
     1000-step Adam on a non-smooth objective, which gives no reproducible answer; ``disp_input`` calls ``depth2disparity``,
-    which the reference defines nowhere, so its own call raises ``NameError``.  ``lr`` / ``max_iters`` (lad2 only) and
+    which the reference defines nowhere, so its own call raises ``NameError``.  The objective lad / lad2 approach has an exact
+    minimiser: ``align_with_l1`` returns it.  ``lr`` / ``max_iters`` (lad2 only) and
     ``use_gpu`` (tensor placement) are accepted and have no effect.
     """
     if align_with_lad or align_with_lad2 or disp_input or any(v for v in unsupported.values()):
@@ -112,6 +203,8 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
         s, t = f32(1), f32(0)
     elif align_with_lstsq:
         s, t = _lstsq_f32(p, g)
+    elif align_with_l1:
+        s, t = (f32(v) for v in l1_fit(p, g)[:2])
     elif p.size == 0:
         s, t = f32(0), f32(0)
     elif align_with_scale:
