@@ -199,8 +199,9 @@ int ug_eval_normal(ug_ctx* ctx, const float* pred_normals, const float* gt_norma
  * out11 as ug_eval_depth.  err_map_out (host, [n], may be NULL) = |s * pred + t - gt| / gt on mask1 and 0 elsewhere, from the ORIGINAL
  * (unclipped) prediction - the reference's second return value.  No valid pixel: zero metrics, (s, t) = (1, 0) for METRIC, (0, 0) otherwise.
  * An unknown alignment is an error (ug_last_error).  With the default options the result equals ug_eval_depth's bit for bit.
- * align_with_lad / align_with_lad2 (BFGS / 1000-step Adam on a non-smooth objective: no reproducible answer) and disp_input (calls a
- * function the reference never defines) have no counterpart; UG_ALIGN_L1 returns the exact minimiser of the objective lad / lad2 approach. */
+ * align_with_lad / align_with_lad2 (BFGS / 1000-step Adam on a non-smooth objective: no reproducible answer) have no counterpart; UG_ALIGN_L1
+ * returns the exact minimiser of the objective lad / lad2 approach.  disp_input (alignment in disparity space) is ug_eval_depth_ex2 below, with the
+ * function the reference calls and never defines supplied. */
 enum { UG_ALIGN_LSTSQ = 0, UG_ALIGN_MEDIAN = 1, UG_ALIGN_SCALE = 2, UG_ALIGN_METRIC = 3, UG_ALIGN_L1 = 4 };
 typedef struct { int alignment; float max_depth;            /* <= 0 or NaN: gt > 0 only */
                  float pre_clip_min, pre_clip_max, post_clip_min, post_clip_max; /* NaN: off */ } ug_depth_eval_opts;
@@ -210,6 +211,31 @@ int ug_eval_depth_ex(ug_ctx* ctx, const float* pred_depth /* NULL: resident dept
 /* How the last UG_ALIGN_L1 evaluation on this context ended: out_info[4] = j, k (the two valid pixels, counted in pixel order, that the fitted
  * line passes through; -1 where there is none), the number of pivot steps, certified (1: the vertex passed every check; 0: a cap was met). */
 int ug_eval_depth_l1_info(ug_ctx* ctx, long* out_info /*[4]*/);
+/* ug_eval_depth_ex with the alignment in DISPARITY space (the reference's depth_evaluation(..., disp_input=True), metrics/eval_depth.py:75-78,
+ * 123-126,169-198, with the depth2disparity it never defines taken as y = 1 / x where x > 0, else 0).  With
+ * UG_DEPTH_ALIGN_DISPARITY in flags, pred is a disparity.  Every operation below is one float32 operation rounded on its own, never fused:
+ *   p = clamp(pred, pre_clip) and gd = 1 / (gt + 1e-8f) on mask1 = gt > 0 (and gt < max_depth), mask1 from the original gt
+ *   (s, t) = the alignment of opts->base of p against gd, each mode exactly as ug_eval_depth_ex defines it with gd in the place of gt
+ *   a = s * p + t;  with disp_clip_min = c (NaN: off), a = c where a < c;  d = 1 / a where a > 0, else 0 (a NaN a gives 0), the division
+ *   correctly rounded;  d = clamp(d, post_clip);  the metrics of ug_eval_depth on d against the REAL gt over mask1 & custom_mask
+ * err_map_out = |d0 - gt| / gt on mask1 and 0 elsewhere, d0 made in the same way from a0 = pred * s + t of the ORIGINAL prediction (no pre- or
+ * post-clip; the floor applies).  No valid pixel: zero metrics and a zero map, (s, t) = (1, 0) for METRIC, (0, 0) otherwise.  Without the floor a
+ * pixel whose aligned disparity is not positive becomes depth 0 (near); with it, 1 / c (far, then post-clipped) - the floor is not in the
+ * reference; the benchmark protocol its file descends from clamps the aligned disparity at 1e-3.
+ * pred_disp == NULL with the flag: the resident DISPARITY of the last ug_dc_run / ug_dc_run_windows - x = (m - lo) / (hi - lo), m the channel
+ * mean of the resident decoded frames and (lo, hi) its min and max over the clip, the value the resident depth 1 / (x + 0.1f) was made from -
+ * produced at evaluation time from the resident frames; ug_dc_get_disparity copies the same array to the host ([T*H*W], min 0, max 1).  Without
+ * the flag pred == NULL is the resident depth, and with flags == 0 and the floor off the call is ug_eval_depth_ex: its launches, its bytes.
+ * ug_eval_depth_l1_info reports the last UG_ALIGN_L1 fit of either call.  Errors (ug_last_error; the context stays usable): an unknown flag bit;
+ * a disp_clip_min that is not NaN and is <= 0 or infinite; a disp_clip_min without the flag; pred == NULL without a resident output of that
+ * size (for the disparity: before any run); everything ug_eval_depth_ex rejects.  Scratch: 4 bytes per pixel more than ug_eval_depth_ex (8 with
+ * the resident disparity). */
+#define UG_DEPTH_ALIGN_DISPARITY 1
+typedef struct { ug_depth_eval_opts base; unsigned flags; float disp_clip_min; /* NaN: off */ } ug_depth_eval_opts2;
+void ug_depth_eval_opts2_default(ug_depth_eval_opts2* o);   /* base defaults, flags 0, NaN */
+int ug_eval_depth_ex2(ug_ctx* ctx, const float* pred /* NULL: resident */, const float* gt_depth, const unsigned char* custom_mask, long n,
+                      const ug_depth_eval_opts2* opts, double* out11, float* err_map_out /* [n] or NULL */);
+int ug_dc_get_disparity(ug_ctx* ctx, float* disp_out /* host, [T*H*W] */);
 /* Depth evaluation in global coordinates: the reference's depth_evaluation_in_global_coord (metrics/eval_depth.py:250-441,
  * utils/geometry_utils.py:246-253).  mask1 = gt_depth > 0 (and gt_depth < max_depth) - from the ground-truth DEPTH, never
  * from the radius.  Fit 1: least squares (s_d, t_d) of clamp(pred, pre_clip) against gt_depth on mask1.  Every pixel, from the ORIGINAL

@@ -20,7 +20,7 @@ EXPORTS = [
     "ug_create", "ug_destroy", "ug_last_error", "ug_workspace_peak",
     "ug_load_tensor", "ug_bind_unet", "ug_bind_vae", "ug_bind_clip",
     "ug_dc_set_inputs", "ug_dc_run", "ug_dc_run_windows", "ug_dc_get_outputs", "ug_dc_device_ptrs", "ug_dc_set_trace", "ug_dc_set_guidance", "ug_unet_forward_pair", "ug_dc_set_inputs_ex", "ug_dc_get_noise", "ug_op_philox_u32", "ug_op_randn", "ug_op_u8_to_frames", "ug_set_vae_encode_fp32", "ug_set_concurrency", "ug_set_coscheduled", "ug_set_fp8_linears", "ug_op_linear_mx8", "ug_set_ff_fused", "ug_op_ff", "ug_op_ln_ff", "ug_bench_ff", "ug_bench_flash", "ug_tune_flash", "ug_tune_ff",
-    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_eval_depth_l1_info", "ug_op_l1_fit", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
+    "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_eval_depth_l1_info", "ug_op_l1_fit", "ug_depth_eval_opts2_default", "ug_eval_depth_ex2", "ug_dc_get_disparity", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
@@ -63,6 +63,10 @@ class DepthEvalOptsC(C.Structure):
                 ("post_clip_min", C.c_float), ("post_clip_max", C.c_float)]
 
 
+class DepthEvalOpts2C(C.Structure):
+    _fields_ = [("base", DepthEvalOptsC), ("flags", C.c_uint), ("disp_clip_min", C.c_float)]
+
+
 class PcdOptsC(C.Structure):
     _fields_ = [("threshold", C.c_float), ("max_iteration", C.c_int), ("knn", C.c_int)]
 
@@ -77,6 +81,7 @@ class RegisterOptsC(C.Structure):
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3, "l1": 4}    # UG_ALIGN_* of include/unigeo_hip.h
+DEPTH_ALIGN_DISPARITY = 1                                                # UG_DEPTH_ALIGN_DISPARITY of include/unigeo_hip.h
 PREP_DEPTH_F64, PREP_ZOOMED = 1, 2                                       # UG_PREP_* of include/unigeo_hip.h
 REG_DROP_SENTINEL = 1                                                    # UG_REG_* of include/unigeo_hip.h
 
@@ -142,6 +147,11 @@ def load_library():
     lib.ug_op_masked_median.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float, C.c_float, vp, C.POINTER(C.c_long)]
     _set_argtypes(lib, {"ug_eval_depth_l1_info": [vp, C.POINTER(C.c_long)],
                         "ug_op_l1_fit": [vp, vp, vp, C.c_long, C.POINTER(DepthEvalOptsC), vp, C.POINTER(C.c_long)]})
+    _set_argtypes(lib, {"ug_depth_eval_opts2_default": [C.POINTER(DepthEvalOpts2C)],
+                        "ug_eval_depth_ex2": [vp, vp, vp, vp, C.c_long, C.POINTER(DepthEvalOpts2C), vp, vp],
+                        "ug_dc_get_disparity": [vp, vp]})
+    if hasattr(lib, "ug_depth_eval_opts2_default"):
+        lib.ug_depth_eval_opts2_default.restype = None
     lib.ug_pcd_opts_default.restype = None
     _set_argtypes(lib, {"ug_pcd_opts_default": [C.POINTER(PcdOptsC)],
                         "ug_pcd_world_points": [vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(DepthEvalOptsC), vp, vp],
@@ -514,6 +524,16 @@ class Engine:
         self._ck(self.lib.ug_dc_get_outputs(self.ctx, _ptr(fo), _ptr(do), _ptr(no)))
         return fo, do, no
 
+    def get_disparity(self):
+        """The normalised disparity of the last run -> ``[T, H, W]`` float32 in [0, 1] (``ug_dc_get_disparity``): the
+        ``x`` the resident depth ``1 / (x + 0.1)`` was made from, produced on the device from the resident frames when it is asked for."""
+        shape = getattr(self, "_shape", None)
+        if shape is None:
+            raise RuntimeError("get_disparity: no clip has been run on this engine")
+        out = np.empty(shape, np.float32)
+        self._ck(self.lib.ug_dc_get_disparity(self.ctx, _ptr(out)))
+        return out
+
     def device_ptrs(self):
         """(frames, depth, normals) device addresses of the resident outputs + their shapes."""
         f, d, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
@@ -571,26 +591,35 @@ class Engine:
     NORMAL_KEYS = ["normal mean", "normal median", "normal rmse", "angle < 5", "angle < 7.5", "angle < 11.25", "angle < 22.5", "angle < 30"]
 
     def eval_depth(self, gt, mask=None, pred=None, max_depth=80.0, alignment="lstsq", pre_clip_min=None, pre_clip_max=None,
-                   post_clip_min=None, post_clip_max=None, return_error_map=False):
+                   post_clip_min=None, post_clip_max=None, return_error_map=False, space="depth", disp_clip_min=None):
         """Depth metrics on the device -> ``(res, (s, t))``, with ``return_error_map=True`` ``(res, (s, t), error_map)``.
         ``alignment``: "lstsq" | "median" | "scale" | "metric" (``ug_eval_depth_ex``) | "l1" (the exact L1 scale and
         shift; ``l1_info``, None until then, holds j, k, steps, certified, and an uncertified fit warns once); the clip bounds clamp
-        the prediction before / after the alignment; ``max_depth=None`` keeps every ``gt > 0``.  The defaults call ``ug_eval_depth``."""
+        the prediction before / after the alignment; ``max_depth=None`` keeps every ``gt > 0``.  The defaults call ``ug_eval_depth``.
+        ``space="disparity"`` (``ug_eval_depth_ex2``): the prediction (``pred=None``: the resident DISPARITY of the last
+        run, ``get_disparity()``) is aligned against ``1 / gt``, inverted, and scored against ``gt``; ``disp_clip_min`` floors the aligned
+        disparity before the inversion."""
         if alignment not in DEPTH_ALIGNMENTS:
             raise ValueError(f"alignment must be one of {sorted(DEPTH_ALIGNMENTS)}, not {alignment!r}")
+        from .harness.metrics import check_disp_clip_min
+        check_disp_clip_min(space, disp_clip_min, "eval_depth")
         g = _f32(gt); n = g.size
         p = None if pred is None else _f32(pred)
         m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
         out = np.zeros(11, np.float64)
         clips = (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)
         emap = None
-        if alignment == "lstsq" and max_depth is not None and not return_error_map and all(c is None for c in clips):
+        if space == "depth" and alignment == "lstsq" and max_depth is not None and not return_error_map and all(c is None for c in clips):
             self._ck(self.lib.ug_eval_depth(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, float(max_depth), _ptr(out)))
         else:
             o = DepthEvalOptsC(DEPTH_ALIGNMENTS[alignment], float("nan") if max_depth is None else float(max_depth),
                                *[float("nan") if c is None else float(c) for c in clips])
             emap = np.empty(g.shape, np.float32) if return_error_map else None
-            self._ck(self.lib.ug_eval_depth_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, C.byref(o), _ptr(out), _ptr(emap)))
+            if space == "depth":
+                self._ck(self.lib.ug_eval_depth_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, C.byref(o), _ptr(out), _ptr(emap)))
+            else:
+                o2 = DepthEvalOpts2C(o, DEPTH_ALIGN_DISPARITY, float("nan") if disp_clip_min is None else float(disp_clip_min))
+                self._ck(self.lib.ug_eval_depth_ex2(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, C.byref(o2), _ptr(out), _ptr(emap)))
             if alignment == "l1":
                 info = (C.c_long * 4)()
                 self._ck(self.lib.ug_eval_depth_l1_info(self.ctx, info))

@@ -483,6 +483,66 @@ static void prep_upload_taps(Ctx& c, const int* idx, const double* w, int n_out,
   *didx = di; *dw = dwt;
 }
 
+// ug_eval_depth_ex and ug_eval_depth_ex2 (DESIGN.md sections 13, 23, 24).  disparity: the prediction (NULL: the resident disparity of the last run,
+// made here from the resident frames and min-max) is fitted against gfit = mask1 ? 1 / (gt + 1e-8f) : 0 by the same fit kernels with the depth bound
+// off, and k_disp_metrics inverts the aligned disparity; floor_ = NaN: no floor.  Without it: the launches and the bits of ug_eval_depth_ex.
+static void eval_depth_modes(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, const ug_depth_eval_opts* o,
+                             bool disparity, float floor_, double* out, float* emap_out) {
+  Ctx& c = x->c;
+  UG_REQUIRE(o->alignment >= UG_ALIGN_LSTSQ && o->alignment <= UG_ALIGN_L1, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC / L1)");
+  UG_REQUIRE(n >= 0 && n < (1L << 32), "pixel count");
+  const bool clips = !std::isnan(o->pre_clip_min) || !std::isnan(o->pre_clip_max) || !std::isnan(o->post_clip_min) || !std::isnan(o->post_clip_max);
+  if (!disparity && o->alignment == UG_ALIGN_LSTSQ && !clips && !emap_out && o->max_depth > 0.f) {   // what ug_eval_depth computes: its launches, its bits
+    eval_depth_lstsq(c, pred, gt, cmask, n, o->max_depth, out);
+    return;
+  }
+  const float md = depth_bound(o->max_depth);
+  const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
+  if (disparity && !pred) UG_REQUIRE(c.io_ready && c.out_ready && n == (long)c.T * c.H * c.W, "no resident disparity of that size (run a clip first)");
+  DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
+  const float* fit_g = d.dg;      // the target of the fit and its depth bound
+  float fit_md = md;
+  if (disparity) {
+    if (!pred) {
+      float* dx = c.ws.get<float>(n);
+      launch_disparity_from_frames(c.d_out_frames, c.d_mm, dx, n, c.stream);
+      d.dp = dx;
+    }
+    float* gfit = c.ws.get<float>(n);
+    launch_disp_target(d.dg, n, md, gfit, c.stream);
+    fit_g = gfit; fit_md = NAN;
+  }
+  double* part = c.ws.get<double>(1024 * 9);
+  int nb = 0;
+  double s_ = 0.0, t_ = 0.0;
+  if (o->alignment == UG_ALIGN_LSTSQ) {
+    launch_depth_fit_ex(d.dp, fit_g, n, fit_md, lo, hi, part, &nb, c.stream);
+    fetch_lstsq(c, part, nb, s_, t_);
+  } else if (o->alignment == UG_ALIGN_MEDIAN) {
+    unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
+    launch_masked_median(d.dp, fit_g, n, fit_md, lo, hi, sel, c.stream);
+    unsigned cnt; float mp, mg;
+    read_masked_median(c, sel, cnt, mp, mg);
+    if (cnt > 0) { const float sf = mg / mp; s_ = sf; }
+  } else if (o->alignment == UG_ALIGN_SCALE) {
+    double* wz = c.ws.get<double>(2);
+    launch_weiszfeld_scale(d.dp, fit_g, n, fit_md, lo, hi, 10, wz, part, c.stream);
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    double r[2];
+    UG_CHECK(hipMemcpy(r, wz, sizeof(r), hipMemcpyDeviceToHost));
+    if (r[1] >= 1) s_ = r[0] < 1e-3 ? 1e-3 : r[0];
+  } else if (o->alignment == UG_ALIGN_L1) {
+    double st[2];
+    l1_fit_device(c, d.dp, fit_g, n, fit_md, lo, hi, st, x->l1_info);
+    s_ = (float)st[0]; t_ = (float)st[1];      // rounded once to float32, as least squares returns them
+  } else s_ = 1.0;
+  float* dmap = emap_out ? c.ws.get<float>(n) : nullptr;
+  if (disparity) launch_disp_metrics(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, floor_, (float)s_, (float)t_, part, dmap, &nb, c.stream);
+  else launch_depth_metrics_ex(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, (float)s_, (float)t_, part, dmap, &nb, c.stream, o->alignment == UG_ALIGN_L1);
+  fetch_depth_metrics(c, part, nb, s_, t_, out);
+  if (emap_out) UG_CHECK(hipMemcpy(emap_out, dmap, n * 4, hipMemcpyDeviceToHost));
+}
+
 extern "C" {
 
 int ug_eval_depth(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, double* out) {
@@ -500,46 +560,42 @@ void ug_depth_eval_opts_default(ug_depth_eval_opts* o) {
 int ug_eval_depth_ex(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, const ug_depth_eval_opts* o,
                      double* out, float* emap_out) {
   UG_TRY(x, {
-    Ctx& c = x->c; Scope sc(c);
+    Scope sc(x->c);
     UG_REQUIRE(o != nullptr, "options must not be NULL");
-    UG_REQUIRE(o->alignment >= UG_ALIGN_LSTSQ && o->alignment <= UG_ALIGN_L1, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC / L1)");
-    UG_REQUIRE(n >= 0 && n < (1L << 32), "pixel count");
-    const bool clips = !std::isnan(o->pre_clip_min) || !std::isnan(o->pre_clip_max) || !std::isnan(o->post_clip_min) || !std::isnan(o->post_clip_max);
-    if (o->alignment == UG_ALIGN_LSTSQ && !clips && !emap_out && o->max_depth > 0.f) {   // what ug_eval_depth computes: its launches, its bits
-      eval_depth_lstsq(c, pred, gt, cmask, n, o->max_depth, out);
-      return 0;
-    }
-    const float md = depth_bound(o->max_depth);
-    const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
-    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
-    double* part = c.ws.get<double>(1024 * 9);
-    int nb = 0;
-    double s_ = 0.0, t_ = 0.0;
-    if (o->alignment == UG_ALIGN_LSTSQ) {
-      launch_depth_fit_ex(d.dp, d.dg, n, md, lo, hi, part, &nb, c.stream);
-      fetch_lstsq(c, part, nb, s_, t_);
-    } else if (o->alignment == UG_ALIGN_MEDIAN) {
-      unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
-      launch_masked_median(d.dp, d.dg, n, md, lo, hi, sel, c.stream);
-      unsigned cnt; float mp, mg;
-      read_masked_median(c, sel, cnt, mp, mg);
-      if (cnt > 0) { const float sf = mg / mp; s_ = sf; }
-    } else if (o->alignment == UG_ALIGN_SCALE) {
-      double* wz = c.ws.get<double>(2);
-      launch_weiszfeld_scale(d.dp, d.dg, n, md, lo, hi, 10, wz, part, c.stream);
-      UG_CHECK(hipStreamSynchronize(c.stream));
-      double r[2];
-      UG_CHECK(hipMemcpy(r, wz, sizeof(r), hipMemcpyDeviceToHost));
-      if (r[1] >= 1) s_ = r[0] < 1e-3 ? 1e-3 : r[0];
-    } else if (o->alignment == UG_ALIGN_L1) {
-      double st[2];
-      l1_fit_device(c, d.dp, d.dg, n, md, lo, hi, st, x->l1_info);
-      s_ = (float)st[0]; t_ = (float)st[1];      // rounded once to float32, as least squares returns them
-    } else s_ = 1.0;
-    float* dmap = emap_out ? c.ws.get<float>(n) : nullptr;
-    launch_depth_metrics_ex(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, (float)s_, (float)t_, part, dmap, &nb, c.stream, o->alignment == UG_ALIGN_L1);
-    fetch_depth_metrics(c, part, nb, s_, t_, out);
-    if (emap_out) UG_CHECK(hipMemcpy(emap_out, dmap, n * 4, hipMemcpyDeviceToHost));
+    eval_depth_modes(x, pred, gt, cmask, n, o, false, NAN, out, emap_out);
+  });
+}
+
+void ug_depth_eval_opts2_default(ug_depth_eval_opts2* o) {
+  ug_depth_eval_opts_default(&o->base);
+  o->flags = 0u; o->disp_clip_min = NAN;
+}
+
+int ug_eval_depth_ex2(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, const ug_depth_eval_opts2* o,
+                      double* out, float* emap_out) {
+  UG_TRY(x, {
+    Scope sc(x->c);
+    UG_REQUIRE(o != nullptr, "options must not be NULL");
+    UG_REQUIRE((o->flags & ~(unsigned)UG_DEPTH_ALIGN_DISPARITY) == 0u, "unknown flag bit (UG_DEPTH_ALIGN_DISPARITY)");
+    const bool disparity = (o->flags & UG_DEPTH_ALIGN_DISPARITY) != 0u;
+    const float fl = o->disp_clip_min;
+    UG_REQUIRE(std::isnan(fl) || (fl > 0.f && std::isfinite(fl)), "disp_clip_min must be finite and positive (NaN: off)");
+    UG_REQUIRE(std::isnan(fl) || disparity, "disp_clip_min needs UG_DEPTH_ALIGN_DISPARITY");
+    eval_depth_modes(x, pred, gt, cmask, n, &o->base, disparity, fl, out, emap_out);
+  });
+}
+
+int ug_dc_get_disparity(ug_ctx* x, float* disp_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(disp_out != nullptr, "disp_out must not be NULL");
+    UG_REQUIRE(c.io_ready && c.out_ready, "no resident disparity (run a clip first)");
+    const long px = (long)c.T * c.H * c.W;
+    float* dx = c.ws.get<float>(px);
+    launch_disparity_from_frames(c.d_out_frames, c.d_mm, dx, px, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(disp_out, dx, px * 4, hipMemcpyDeviceToHost));
   });
 }
 

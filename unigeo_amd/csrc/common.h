@@ -239,6 +239,8 @@ void launch_time_conv_out(const f16* x, const f16* w, const f16* b, float* frame
                           long HW, int Cs, hipStream_t s);  // + (x/2+0.5).clamp(0,1) -> f32 [T,HW,3]
 void launch_depth_post(const float* frames, float* depth, float* minmax_ws, long pixels,
                        hipStream_t s);        // channel mean, clip-global min-max, 1/(x+0.1)
+void launch_disparity_from_frames(const float* frames, const float* minmax_ws, float* disp, long pixels,
+                                  hipStream_t s);   // the x of launch_depth_post, from its frames and the min-max it left
 void launch_normals(const float* depth, const float* K33, float* normals, int T, int H, int W,
                     hipStream_t s);
 
@@ -288,6 +290,11 @@ void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float ma
 void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s);
 void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
                              float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s, bool unfused = false);
+// alignment in disparity space (kernels/metrics.hip): gfit = mask1 ? 1 / (gt + 1e-8f) : 0, the target the fit kernels above take
+// with the depth bound off; then the metrics of the inverted aligned disparity against the real gt (floor_ = NaN: no floor)
+void launch_disp_target(const float* gt, long n, float max_depth, float* gfit, hipStream_t s);
+void launch_disp_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi, float plo,
+                         float phi, float floor_, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s);
 // exact L1 scale-and-shift alignment (kernels/metrics.hip): state words (unsigned 64-bit) and caps
 #define L1_BITS 36            // q = rint(p * 2^(L1_BITS - E))
 #define L1_MAX_STEPS 64

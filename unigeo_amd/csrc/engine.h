@@ -155,6 +155,7 @@ struct Ctx {
   f16* d_clip_emb = nullptr; f16* d_cond = nullptr; f16* d_lat = nullptr;
   size_t io_mark = 0; bool io_ready = false;
   bool normals_ready = false;   // d_normals holds the normals of the last dc_run (with_normals = 1) on the current inputs
+  bool out_ready = false;       // d_out_frames / d_depth / d_mm hold the outputs of a dc_run on the current inputs (the resident disparity reads them)
   // world points of the last ug_pcd_world_points ([pcd_pixels,3] float32).  An allocation of its own, grown on demand and freed
   // with the context: the workspace is a stack that every call unwinds, so nothing in it outlives the call that made it
   float* d_pcd_pts = nullptr; long pcd_cap = 0, pcd_pixels = 0;

@@ -1550,7 +1550,7 @@ static void dc_alloc_io(Ctx& c, int T, int H, int W) {
   UG_REQUIRE(H % 64 == 0 && W % 64 == 0, "height and width must be multiples of 64 (VAE /8, UNet /8)");
   UG_REQUIRE(T >= 1 && T <= 4096, "1..4096 frames (at most 128 per denoising window)");
   if (c.io_ready) { c.ws.release(c.io_mark); c.io_ready = false; }
-  c.normals_ready = false;
+  c.normals_ready = false; c.out_ready = false;
   c.io_mark = c.ws.mark();
   c.T = T; c.H = H; c.W = W;
   const long px = (long)T * H * W, lp = (long)T * (H / 8) * (W / 8);
@@ -1792,6 +1792,7 @@ void dc_run(Ctx& c, int steps, int chunk, int with_normals, int window, int over
   }
   UG_CHECK(hipStreamSynchronize(c.stream));
   c.normals_ready = with_normals != 0;
+  c.out_ready = true;
 }
 
 void dc_get_outputs(Ctx& c, float* frames, float* depth, float* normals) {

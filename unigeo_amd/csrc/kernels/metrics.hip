@@ -272,6 +272,48 @@ __global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// Alignment in disparity space (UG_DEPTH_ALIGN_DISPARITY; the disp_input branch of /root/reference/metrics/eval_depth.py:75-78,
+// 123-126,169-198 with the depth2disparity it never defines supplied: y = 1 / x where x > 0, else 0).  The prediction is a disparity: it is fitted
+// against gd = 1 / (gt + 1e-8f) on mask1, the aligned disparity is inverted, and the metrics are taken against the real gt.
+// Target pass: gfit = mask1 ? gd : 0.  gd > 0 on mask1, so the fit kernels above, launched with gfit in the place of gt and the depth bound off, see
+// mask1 through their own test g > 0.
+__global__ __launch_bounds__(MB) void k_disp_target(const float* gt, long n, float max_depth, float* gfit) {
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const float g = gt[i];
+    gfit[i] = depth_valid(g, max_depth) ? 1.0f / (g + 1e-8f) : 0.f;
+  }
+}
+// aligned disparity -> depth: the optional floor (NaN: off; a NaN disparity stays NaN), then 1 / a where a > 0, else 0.  The division is the
+// compiler's default, correctly rounded one.
+__device__ __forceinline__ float disp_to_depth(float a, float floor_) {
+  if (a < floor_) a = floor_;
+  return a > 0.f ? 1.0f / a : 0.f;
+}
+// The counterpart of k_depth_metrics_ex: p' = clamp(disp_to_depth(s * clamp(p, lo, hi) + t), plo, phi) against the real gt on mask1 & custom mask;
+// optional error map |disp_to_depth(pred * s + t) - gt| / gt on mask1 (0 elsewhere) from the ORIGINAL prediction.  s * p + t is unfused in every
+// mode: the inversion carries a rounding of the aligned disparity into the depth, and the depth is compared with the host's byte for byte.
+__global__ __launch_bounds__(MB) void k_disp_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth,
+                                                     float lo, float hi, float plo, float phi, float floor_, float s, float t, double* part,
+                                                     float* emap) {
+  __shared__ double sh[MB];
+  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+    const float g = gt[i];
+    const bool v1 = depth_valid(g, max_depth);
+    const float p0 = pred[i];
+    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(disp_to_depth(mul_add_unfused(p0, s, t), floor_), g)) / g : 0.f;
+    if (v1 && (!cmask || cmask[i])) {
+      const float p = clipf(disp_to_depth(mul_add_unfused(s, clipf(p0, lo, hi), t), floor_), plo, phi);
+      metric_terms(p, g, a);
+    }
+  }
+  for (int k = 0; k < 9; ++k) {
+    const double r = block_sum(a[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Depth evaluation in global coordinates (restated from /root/reference/metrics/eval_depth.py:250-441 and
 // utils/geometry_utils.py:246-253).  After the first fit (k_depth_fit_ex) gave (s, t): the aligned, post-clipped depth
 // d = clamp(s * pred + t, plo, phi) of EVERY pixel from the ORIGINAL prediction, float32 with the product and the sum rounded separately;
@@ -402,6 +444,14 @@ void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned 
   *nb = nblocks(n);
   if (unfused) hipLaunchKernelGGL(k_depth_metrics_ex<true>, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
   else hipLaunchKernelGGL(k_depth_metrics_ex<false>, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
+}
+void launch_disp_target(const float* gt, long n, float max_depth, float* gfit, hipStream_t s) {
+  hipLaunchKernelGGL(k_disp_target, dim3(nblocks(n)), dim3(MB), 0, s, gt, n, max_depth, gfit);
+}
+void launch_disp_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi, float plo,
+                         float phi, float floor_, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s) {
+  *nb = nblocks(n);
+  hipLaunchKernelGGL(k_disp_metrics, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, floor_, sc, sh, part, emap);
 }
 void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s) {

@@ -527,6 +527,18 @@ void launch_depth_post(const float* frames, float* depth, float* minmax_ws, long
   hipLaunchKernelGGL(k_depth_minmax, gs_grid(pixels), dim3(256), 0, s, frames, mm, pixels);
   hipLaunchKernelGGL(k_depth_apply, gs_grid(pixels), dim3(256), 0, s, frames, depth, (const unsigned*)mm, pixels);
 }
+// the normalised disparity x of k_depth_apply on its own (evaluation in disparity space): the same expressions in the same
+// order, from the frames and the min-max words a run left resident, so that depth == 1.0f / (x + 0.1f) bit for bit
+__global__ void k_disparity_from_frames(const float* frames, float* disp, const unsigned* mm, long pixels) {
+  const float lo = ord2f(mm[0]), hi = ord2f(mm[1]);
+  GS_LOOP(p, pixels) {
+    const float d = (frames[p * 3] + frames[p * 3 + 1] + frames[p * 3 + 2]) / 3.0f;
+    disp[p] = (d - lo) / (hi - lo);
+  }
+}
+void launch_disparity_from_frames(const float* frames, const float* minmax_ws, float* disp, long pixels, hipStream_t s) {
+  hipLaunchKernelGGL(k_disparity_from_frames, gs_grid(pixels), dim3(256), 0, s, frames, disp, (const unsigned*)minmax_ws, pixels);
+}
 
 // ------------------------------------------------------------------------------------------
 // depth -> OpenGL-frame surface normals (reference model/depthcrafter.py:48-59 +

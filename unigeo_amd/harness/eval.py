@@ -17,7 +17,7 @@ from .camera import CAMERA_KEYS, camera_pose_evaluation, save_camera_trajectorie
 from .io_utils import prepare_gt_label
 from .pointmap import poses_from_pointmap
 from .vis import save_depth_normal_maps, write_ply
-from .metrics import (DEPTH_ALIGNMENTS, PCD_KEYS, MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
+from .metrics import (DEPTH_ALIGNMENTS, DEPTH_ALIGN_SPACES, PCD_KEYS, MetricsManager, check_disp_clip_min, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
                       pcd_evaluation, world_points_from_depth)
 
 
@@ -54,6 +54,23 @@ def parse_depth_eval_config(config):
         raise ValueError(f"eval_depth.depth_alignment must be one of {list(DEPTH_ALIGNMENTS)}, not {alignment!r}")
     clips = {k: cfg[k] for k in ("pre_clip_min", "pre_clip_max", "post_clip_min", "post_clip_max") if cfg.get(k) is not None}
     return alignment, cfg.get("max_depth", 80), clips
+
+
+def parse_depth_space_config(config):
+    """``eval_depth.space``: ``depth`` (default: the prediction is a depth and is aligned against the ground-truth depth) or ``disparity`` (the
+    prediction is a disparity: it is aligned against ``1 / gt``, inverted, and scored against the depth), and
+    ``eval_depth.disp_clip_min`` (optional, disparity only: a floor under the aligned disparity before it is inverted) ->
+    ``(space, disp_clip_min)``.  An unknown space, a floor that is not a finite positive number, a floor with ``space: depth``, and
+    ``space: disparity`` together with ``coord: global`` are a ``ValueError``."""
+    cfg = config.get("eval_depth") or {}
+    space = cfg.get("space", "depth")
+    if space not in DEPTH_ALIGN_SPACES:
+        raise ValueError(f"eval_depth.space must be one of {list(DEPTH_ALIGN_SPACES)}, not {space!r}")
+    floor = cfg.get("disp_clip_min")
+    check_disp_clip_min(space, floor, "eval_depth.disp_clip_min")
+    if space == "disparity" and cfg.get("coord", "camera") == "global":
+        raise ValueError("eval_depth.space: disparity does not go with coord: global (the world-frame evaluation aligns the depth itself)")
+    return space, (None if floor is None else float(floor))
 
 
 DEPTH_COORDS = ("camera", "global")
@@ -130,6 +147,11 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     ``eval_depth.coord: global`` (default ``camera``) evaluates the depth in world coordinates instead: the radius
     ``|gt_world_pts|``, the poses of ``prepare_gt_label`` and the sample's intrinsics go to ``depth_evaluation_in_global_coord`` on the host and to
     ``ug_eval_depth_global`` on the device path; the row keys stay the same.  It goes with ``depth_alignment: lstsq`` only (``ValueError`` otherwise).
+    ``eval_depth.space: disparity`` (default ``depth``) aligns in disparity space, the protocol of the published video-depth
+    numbers: the model's ``pred_disps`` on the host path (``depth_evaluation(align_space="disparity")``; a model that returns none raises a
+    ``ValueError`` at its first clip that names the clip, the plugin and ``return_disparity``), the resident disparity of the last run under
+    ``device_metrics=True`` (``ug_eval_depth_ex2``; the plugin needs no option).  ``eval_depth.disp_clip_min`` floors the aligned disparity.
+    Not with ``coord: global``; ``eval_pcd``'s world points keep coming from the least-squares-aligned depth.
     ``vis_depth: True`` (the reference's key, eval.py:58-62) writes ``save_dir/depth_{seq}/frame_%04d.webp`` after the clip's metrics: rgb | normals |
     coloured depth | colour bar, composed on the GPU from the resident outputs under ``device_metrics=True`` and by the numpy mirror otherwise
     (DESIGN.md section 15).  Rows and CSV do not change.
@@ -150,6 +172,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     without ``eval_camera`` it is a ``ValueError``.  A configuration without ``eval_camera`` gives the rows and bytes it gave before."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
     coord = parse_depth_coord(config)
+    space, disp_clip_min = parse_depth_space_config(config)
+    space_kw = {} if space == "depth" else {"disp_clip_min": disp_clip_min}
     pcd_cfg = parse_pcd_eval_config(config)
     cam_cfg = parse_camera_eval_config(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True},
@@ -184,6 +208,17 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
             else:
                 res = depth_evaluation_in_global_coord(output["pred_depths"], gt["gt_depths"], gt_radius, poses, K, max_depth=max_depth,
                                                        custom_mask=gt["gt_masks"], align_with_lstsq=True, **clips)
+            metric.update(res[0])
+        elif "eval_depth" in config and space == "disparity":
+            if eng is not None:
+                res = eng.eval_depth(gt["gt_depths"].numpy(), gt["gt_masks"].numpy(), max_depth=max_depth, alignment=alignment, space="disparity",
+                                     **space_kw, **clips)
+            else:
+                if output.get("pred_disps") is None:
+                    raise ValueError(f"eval_depth.space: disparity: clip {seq}: the model {type(mdl).__name__!r} returns no 'pred_disps'; "
+                                     f"construct it with return_disparity=True (model_params), or evaluate with space: depth")
+                res = depth_evaluation(output["pred_disps"], gt["gt_depths"], max_depth=max_depth, custom_mask=gt["gt_masks"],
+                                       align_space="disparity", **space_kw, **host_mode, **clips)
             metric.update(res[0])
         elif "eval_depth" in config:
             if eng is not None:

@@ -13,7 +13,8 @@
 * ``MetricsManager``    <- ``/root/reference/metrics/save_utils.py:5-90``: one row per sequence, NaN for missing
   metrics, trailing ``Average`` row (NaN-skipping mean), ``%.5f``.
 The lad / lad2 / disp_input modes of the reference function raise here (see ``depth_evaluation``); ``align_with_l1`` is the exact
-minimiser of the objective lad / lad2 approach (``l1_fit``).
+minimiser of the objective lad / lad2 approach (``l1_fit``); ``align_space="disparity"`` is what ``disp_input``
+means, with the function the reference never defines supplied (``disparity_to_depth``).
 """
 import math
 import os
@@ -162,11 +163,43 @@ def _metric_values(p, g):
     return res
 
 
+DEPTH_ALIGN_SPACES = ("depth", "disparity")
+
+
+def check_disp_clip_min(align_space, disp_clip_min, who="depth_evaluation"):
+    """The two option checks every layer shares: a known ``align_space``; ``disp_clip_min`` finite and positive, and only in disparity space."""
+    if align_space not in DEPTH_ALIGN_SPACES:
+        raise ValueError(f"{who}: the alignment space must be one of {DEPTH_ALIGN_SPACES}, not {align_space!r}")
+    if disp_clip_min is None:
+        return
+    try:
+        c = float(disp_clip_min)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: disp_clip_min must be a finite positive number, not {disp_clip_min!r}") from None
+    if isinstance(disp_clip_min, bool) or not (math.isfinite(c) and c > 0):
+        raise ValueError(f"{who}: disp_clip_min must be a finite positive number, not {disp_clip_min!r}")
+    if align_space != "disparity":
+        raise ValueError(f"{who}: disp_clip_min floors the aligned disparity and needs the alignment space 'disparity'")
+
+
+def disparity_to_depth(a, disp_clip_min=None):
+    """Aligned float32 disparity -> float32 depth: with ``disp_clip_min = c``, ``a = c`` where ``a < c`` (a NaN stays
+    NaN); then ``1 / a`` where ``a > 0``, else 0.  Without the floor this is the three-line ``depth2disparity`` the reference's
+    ``disp_input`` branch calls and never defines."""
+    a = np.asarray(a, np.float32)
+    if disp_clip_min is not None:
+        a = np.where(a < np.float32(disp_clip_min), np.float32(disp_clip_min), a)
+    out = np.zeros(a.shape, np.float32)
+    pos = a > 0
+    out[pos] = np.float32(1) / a[pos]
+    return out
+
+
 def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_depth=80, custom_mask=None,
                      post_clip_min=None, post_clip_max=None, pre_clip_min=None, pre_clip_max=None,
                      align_with_lstsq=False, align_with_lad=False, align_with_lad2=False, metric_scale=False,
                      align_with_scale=False, disp_input=False, lr=1e-4, max_iters=1000, use_gpu=False, return_error_map=False,
-                     align_with_l1=False, **unsupported):
+                     align_with_l1=False, align_space="depth", disp_clip_min=None, **unsupported):
     """``depth_evaluation`` of the reference (``metrics/eval_depth.py:59-204``) -> ``(res, (s, t))``, with
     ``return_error_map=True`` ``(res, (s, t), error_map)``.
 
@@ -184,11 +217,22 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
     1000-step Adam on a non-smooth objective, which gives no reproducible answer; ``disp_input`` calls ``depth2disparity``,
     which the reference defines nowhere, so its own call raises ``NameError``.  The objective lad / lad2 approach has an exact
     minimiser: ``align_with_l1`` returns it.  ``lr`` / ``max_iters`` (lad2 only) and
-    ``use_gpu`` (tensor placement) are accepted and have no effect.
+    ``use_gpu`` (tensor placement) are accepted and have no effect.  The flag ``disp_input`` keeps raising; what it means, with the
+    missing function supplied, is ``align_space="disparity"``:
+
+    ``align_space="disparity"``: the prediction is a DISPARITY.  On mask1 (from the original gt), with every
+    operation one float32 rounding: ``p = clamp(pred, pre_clip)``, ``gd = 1 / (gt + 1e-8)``, ``(s, t)`` = the chosen alignment of ``p``
+    against ``gd`` (each mode as above, same precedence), ``a = s * p + t``, with ``disp_clip_min = c`` ``a = max(a, c)``,
+    ``d = 1 / a`` where ``a > 0`` else 0 (``disparity_to_depth``), ``d = clamp(d, post_clip)``, then the custom mask and the metrics
+    against the REAL gt.  The error map is ``|d0 - gt| / gt`` on mask1, ``d0`` made the same way from ``a0 = pred * s + t`` of the
+    original prediction (the floor applies, the clips do not).  ``align_space="depth"`` (the default) is everything above, unchanged;
+    ``disp_clip_min`` with it, a ``disp_clip_min`` that is not finite and positive, or an unknown ``align_space`` is a ``ValueError``.
     """
     if align_with_lad or align_with_lad2 or disp_input or any(v for v in unsupported.values()):
         raise NotImplementedError("align_with_lad / align_with_lad2 (no reproducible optimum) and disp_input (undefined in the "
                                   "reference) are not restated")
+    check_disp_clip_min(align_space, disp_clip_min)
+    disparity = align_space == "disparity"
     f32 = np.float32
     pred = _np(predicted_depth_original).astype(np.float32).reshape(-1)
     gt = _np(ground_truth_depth_original).astype(np.float32).reshape(-1)
@@ -199,6 +243,8 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
         p = np.maximum(p, f32(pre_clip_min))
     if pre_clip_max is not None:
         p = np.minimum(p, f32(pre_clip_max))
+    if disparity:
+        real_g, g = g, f32(1) / (g + f32(1e-8))
     if metric_scale:
         s, t = f32(1), f32(0)
     elif align_with_lstsq:
@@ -215,6 +261,8 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
     s_ret = float(s)
     s = f32(s)
     p = s * p + t
+    if disparity:
+        p, g = disparity_to_depth(p, disp_clip_min), real_g
     if post_clip_min is not None:
         p = np.maximum(p, f32(post_clip_min))
     if post_clip_max is not None:
@@ -226,7 +274,8 @@ def depth_evaluation(predicted_depth_original, ground_truth_depth_original, max_
     if not return_error_map:
         return res, (s_ret, float(t))
     emap = np.zeros(gt.shape, f32)
-    emap[mask] = np.abs((pred[mask] * s + t) - gt[mask]) / gt[mask]
+    p0 = pred[mask] * s + t
+    emap[mask] = np.abs((disparity_to_depth(p0, disp_clip_min) if disparity else p0) - gt[mask]) / gt[mask]
     return res, (s_ret, float(t)), emap.reshape(np.shape(_np(ground_truth_depth_original)))
 
 

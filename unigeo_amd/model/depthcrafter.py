@@ -15,6 +15,9 @@ Differences that are deliberate and visible:
     held between calls; a different (equally reproducible, rank-independent) noise sequence than the CPU generator's;
   * ``num_inference_steps`` defaults to the reference's shipped value 5 (:86) and is a kwarg;
   * ``guidance_scale`` (kwarg / YAML model_params) defaults to the reference's 1.0 (:85); > 1 switches on classifier-free guidance;
+  * ``return_disparity`` (kwarg / YAML model_params; default ``False``): ``forward`` also returns ``pred_disps`` ``[Nf,H,W]``, the normalised
+    disparity ``x`` in [0, 1] that ``pred_depths = 1 / (x + 0.1)`` is made from (:92-97), for the evaluation in disparity space
+    (``eval_depth.space: disparity``, DESIGN.md section 24);
   * without checkpoints on disk the constructor raises unless ``synthetic_weights=True`` is passed.
 """
 import os
@@ -32,6 +35,7 @@ class DepthCrafter:
         self.noise = str(kwargs.get("noise", "host"))                    # "host": seeded CPU generator (+ prefetch thread); "device": generated on the GPU from the seed
         if self.noise not in ("host", "device"):
             raise ValueError('noise must be "host" or "device"')
+        self.return_disparity = bool(kwargs.get("return_disparity", False))
         self._calls = 0
         device_id = int(kwargs.get("device_id", 0))
         self.device = f"hip:{device_id}"
@@ -98,6 +102,15 @@ class DepthCrafter:
         th.start()
         self._noise_pf = ((shape, seed), th, box)
 
+    def _disparity_kw(self):
+        return {"return_disparity": True} if getattr(self, "return_disparity", False) else {}
+
+    def _with_disparity(self, out, res):
+        if getattr(self, "return_disparity", False):
+            import torch
+            out["pred_disps"] = torch.from_numpy(np.ascontiguousarray(res.disparity)).float()
+        return out
+
     def _forward_device_noise(self, data):
         """``noise="device"``: uint8 planar frames up, one seed down to the library; nothing drawn, started or kept on the host."""
         frames = np.stack([np.asarray(x).astype(np.uint8) for x in data["images"]], axis=0)       # [T,3,H,W]: prepare_input without the transpose and the division
@@ -107,8 +120,8 @@ class DepthCrafter:
         res = self.pipeline(frames, height=frames.shape[2], width=frames.shape[3], output_type="np",
                             guidance_scale=getattr(self, "guidance_scale", 1.0), num_inference_steps=self.num_inference_steps,
                             window_size=len(frames), overlap=25, track_time=False, seed=clip_seed, noise="device",
-                            intrinsics=K, with_normals=True, return_frames=False)
-        return self.prepare_output(list(res.depth), data, _device_normals=res.normals)
+                            intrinsics=K, with_normals=True, return_frames=False, **self._disparity_kw())
+        return self._with_disparity(self.prepare_output(list(res.depth), data, _device_normals=res.normals), res)
 
     def forward(self, data):
         if getattr(self, "noise", "host") == "device":
@@ -132,5 +145,5 @@ class DepthCrafter:
                             guidance_scale=getattr(self, "guidance_scale", 1.0), num_inference_steps=self.num_inference_steps,
                             window_size=len(frames), overlap=25, track_time=False, seed=clip_seed,
                             noise_latents=noise_latents, noise_aug=noise_aug,
-                            intrinsics=K, with_normals=True, return_frames=False)
-        return self.prepare_output(list(res.depth), data, _device_normals=res.normals)
+                            intrinsics=K, with_normals=True, return_frames=False, **self._disparity_kw())
+        return self._with_disparity(self.prepare_output(list(res.depth), data, _device_normals=res.normals), res)

@@ -84,10 +84,12 @@ class DepthCrafterPipelineHIP:
     def __call__(self, video, height=None, width=None, num_inference_steps=25, guidance_scale=1.0,
                  window_size=110, noise_aug_strength=0.02, decode_chunk_size=None, output_type="np",
                  overlap=25, track_time=False, noise_latents=None, noise_aug=None, seed=None,
-                 intrinsics=None, with_normals=False, return_frames=True, noise="host"):
+                 intrinsics=None, with_normals=False, return_frames=True, noise="host", return_disparity=False):
         """``noise="host"`` (default): ``noise_latents`` / ``noise_aug``, or a draw from ``make_noise(seed)``.  ``noise="device"``: both tensors
         are generated on the GPU from ``seed`` (or ``self.seed``); passing noise arrays as well is an error.  ``video``: float ``[T,H,W,3]``
-        in [0,1], or a uint8 array ``[T,3,H,W]`` (planar, as the dataset delivers it) that the device converts to ``x / 255``."""
+        in [0,1], or a uint8 array ``[T,3,H,W]`` (planar, as the dataset delivers it) that the device converts to ``x / 255``.
+        ``return_disparity=True`` adds ``disparity`` ``[T,H,W]``: the normalised disparity ``x`` in [0, 1] behind ``depth = 1 / (x + 0.1)``, one more
+        engine call (``get_disparity``) after the outputs; by default the engine sees the calls it always saw and ``disparity`` is ``None``."""
         if noise not in ("host", "device"):
             raise ValueError('noise must be "host" or "device"')
         if noise == "device" and (noise_latents is not None or noise_aug is not None):
@@ -139,4 +141,5 @@ class DepthCrafterPipelineHIP:
         eng.run(num_inference_steps, chunk, with_normals=with_normals, window=window_size if T > window_size else 0, overlap=overlap)
         # return_frames=False (the plugin's forward, which consumes depth / normals only): the decoded frames stay in HBM - 59 MB less to download per clip
         frames, depth, normals = eng.get_outputs(frames=bool(return_frames), depth=True, normals=with_normals)
-        return SimpleNamespace(frames=[frames], depth=depth, normals=normals)
+        disparity = eng.get_disparity() if return_disparity else None
+        return SimpleNamespace(frames=[frames], depth=depth, normals=normals, disparity=disparity)
