@@ -106,6 +106,22 @@ int ug_op_gn32_pair(ug_ctx* ctx, const float* x, int T, int HW, int C, int G, fl
 int ug_op_conv_wide(ug_ctx* ctx, const float* x_thwc, int T, int H, int W, int C, const float* weight, const float* bias, int O, const float* res, int res_in_place,
                     int k, int stride, int pad_t, int pad_l, float* out_thwc);
 int ug_op_attn_wide(ug_ctx* ctx, const float* qkv, int T, int S, int C, float* out);
+/* One convolution through the product's own path (tests/test_conv_bound_gpu.py): the checkpoint-layout weight [O][cin][k][k] (kt == 1) or [O][cin][3][1][1]
+ * (kt == 3, k == 1) and the optional bias are bound on the device by the engine's bind_conv - upsampler != 0 as the models' upsamplers are bound, with the
+ * sub-pixel phase weights - and launched by the engine's conv().  ug_op_conv packs its weights on the host instead.
+ *   ug_op_bind_conv : the bound tensors, fp16 widened to float: w_out [O * kt*k*k * cinp]; wphase_out [4 * O * 4 * cinp] (may be NULL; written only if phase
+ *                     weights were bound); info_out [3] = cinp (cin rounded up to 8), the chunk-major flag (Conv::kchunk), 1 if phase weights were bound.
+ *   ug_op_conv_bound: x0 [T,H,W,C0] and x1 [T,H,W,C1] (may be NULL, C1 = 0) with C0 + C1 == cin; with cin % 8 != 0 one source of cin channels, which is
+ *                     padded with zero channels on the device.  ups == 2 with upsampler != 0, stride 1 and pads (1, 1): four 2x2 phase launches that scatter
+ *                     to the output parities; every other form: one launch, with the optional residual R1 [rows, O]: out = act(c0 * (conv + bias) + c1 * R1).
+ *                     out_inout [rows + guard, ldo], rows = T * (H*ups/stride) * (W*ups/stride), ldo >= O: uploaded as the caller gives it and all of it
+ *                     comes back - guard rows, surplus columns and pixels no launch wrote return unchanged.  plan_out [9] (may be NULL): the number of GEMM
+ *                     launches (1 or 4), then the planner's (tile config, split factor) of each in launch order, -1 where there was none. */
+int ug_op_bind_conv(ug_ctx* ctx, const float* weight, const float* bias, int cin, int O, int kt, int k, int upsampler,
+                    float* w_out, float* wphase_out, int* info_out /*[3]*/);
+int ug_op_conv_bound(ug_ctx* ctx, const float* weight, const float* bias, int cin, int O, int kt, int k, int upsampler,
+                     const float* x0_thwc, int C0, const float* x1_thwc, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
+                     const float* R1, float c0, float c1, int act, long ldo, long guard, float* out_inout, int* plan_out /*[9]*/);
 /* Clip inputs made on the device (kernels/noise.hip; behind ug_dc_set_inputs_ex of the product header).
  *   ug_op_philox_u32  : Philox4x32-10 words of blocks block_offset .. block_offset + nblocks - 1 for key = seed (lo, hi) and counter
  *                       (q lo, q hi, stream, 0) -> out [nblocks][4] uint32 (the generator against the published known-answer vectors)

@@ -23,8 +23,7 @@ import torch
 import torch.nn.functional as F
 
 import test_ops_gpu
-from test_splitk_gpu import conv_f64
-from util import h16, rel_err, report
+from util import conv_f64, h16, rel_err, report
 
 pytestmark = pytest.mark.gpu
 

@@ -110,3 +110,35 @@ def mx8_quantise(x):
     q = e4m3_rne(xb * 2.0 ** (-ex[..., None]))
     deq = (q.astype(np.float64) * 2.0 ** ex[..., None]).reshape(M, K).astype(np.float32)
     return deq, e4m3_encode(q).reshape(M, K), (ex + 127).astype(np.uint8)
+
+
+def conv_f64(x, w, b, x1=None, kt=1, k=3, stride=1, pad_t=1, pad_l=1, ups=1):
+    """Convolution of channels-last x [T,H,W,C] (+ x1 concatenated) with w [O,C,kt,k,k] as one fp64 matrix product per tap, straight from the
+    definition: output (t, oy, ox) reads frame t + it - kt // 2, row oy * stride - pad_t + iy, column ox * stride - pad_l + ix of the
+    (nearest-2x upsampled) source, zero outside.  On integer data every partial sum is an integer far below 2^53: exact."""
+    x = np.asarray(x, np.float64)
+    if x1 is not None:
+        x = np.concatenate([x, np.asarray(x1, np.float64)], -1)
+    if ups == 2:
+        x = x.repeat(2, 1).repeat(2, 2)
+    T, H, W, C = x.shape
+    wt = np.ascontiguousarray(np.asarray(w, np.float64).reshape(-1, C, kt, k, k).transpose(2, 3, 4, 1, 0))     # [kt][k][k][C][O]
+    Ho, Wo = H // stride, W // stride
+    xp = np.zeros((T + kt - 1, H + k, W + k, C))
+    xp[kt // 2:kt // 2 + T, pad_t:pad_t + H, pad_l:pad_l + W] = x
+    out = np.zeros((T * Ho * Wo, wt.shape[-1]))
+    for it in range(kt):
+        for iy in range(k):
+            for ix in range(k):
+                rows = np.ascontiguousarray(xp[it:it + T, iy:iy + stride * Ho:stride, ix:ix + stride * Wo:stride]).reshape(-1, C)
+                out += rows @ wt[it, iy, ix]
+    out = out.reshape(T, Ho, Wo, -1)
+    return out if b is None else out + np.asarray(b, np.float64)
+
+
+def where_differ(got, ref):
+    """Where two outputs differ, for localising a slice / tile-edge bug from the pattern."""
+    bad = np.argwhere(got != ref)
+    first = tuple(int(v) for v in bad[0])
+    return (f"{len(bad)} of {got.size} elements differ, first at {first} (got {got[first]}, expected {ref[first]}), "
+            f"rows {bad[:, 0].min()}..{bad[:, 0].max()}, last-axis columns {bad[:, -1].min()}..{bad[:, -1].max()}, max |diff| {np.abs(got - ref).max()}")

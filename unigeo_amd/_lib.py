@@ -25,6 +25,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
+    "ug_op_bind_conv", "ug_op_conv_bound",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
@@ -198,6 +199,9 @@ def load_library():
     _set_argtypes(lib, {
         "ug_op_split_pair": [vp, vp, C.c_long, ip, vp, vp], "ug_op_gn32_pair": [vp, vp, ip, ip, ip, ip, C.c_float, ip, vp, vp, vp, vp],
         "ug_op_conv_wide": [vp, vp, ip, ip, ip, ip, vp, vp, ip, vp, ip, ip, ip, ip, ip, vp], "ug_op_attn_wide": [vp, vp, ip, ip, ip, vp]})
+    _set_argtypes(lib, {
+        "ug_op_bind_conv": [vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, vp],
+        "ug_op_conv_bound": [vp, vp, vp, ip, ip, ip, ip, ip, vp, ip, vp, ip, ip, ip, ip, ip, ip, ip, ip, vp, C.c_float, C.c_float, ip, C.c_long, C.c_long, vp, vp]})
     lib.ug_bind_stablenormal.argtypes = [vp, C.POINTER(UNetConfigC), C.POINTER(VAEConfigC), C.POINTER(CLIPConfigC)]
     lib.ug_sn_run.argtypes = [vp, vp, ip, ip, ip, vp, C.c_float, ip, vp, vp, vp, vp]
     lib.ug_sn_unet_forward.argtypes = [vp, ip, vp, vp, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]
@@ -1134,6 +1138,37 @@ class Engine:
         out = np.empty((T, H // stride, W // stride, O), np.float32)
         self._ck(self.lib.ug_op_conv_wide(self.ctx, _ptr(x), T, H, W, Cc, _ptr(w), _ptr(b), O, _ptr(r), int(bool(res_in_place)), k, stride, pad_t, pad_l, _ptr(out)))
         return out
+
+    # one convolution through the product's own binding (bind_conv) and launch (conv()) code (tests/test_conv_bound_gpu.py)
+    def op_bind_conv(self, weight, bias=None, upsampler=False):
+        """weight [O, I, kt, k, k] bound on the device.  Returns a dict: w [O, kt*k*k*cinp] (the bound Conv::w, fp16 widened to float32), wphase
+        [4, O, 4*cinp] or None (the sub-pixel phase weights of an upsampler), cinp, kchunk (1: both are in the chunk-major K order)."""
+        w = _f32(weight); O, I, kt, k, _ = w.shape
+        b = None if bias is None else _f32(bias)
+        cinp = (I + 7) // 8 * 8
+        wo = np.empty((O, kt * k * k * cinp), np.float32); wp = np.full((4, O, 4 * cinp), np.nan, np.float32)
+        info = (C.c_int * 3)()
+        self._ck(self.lib.ug_op_bind_conv(self.ctx, _ptr(w), _ptr(b), I, O, kt, k, int(bool(upsampler)), _ptr(wo), _ptr(wp), info))
+        assert info[0] == cinp, (info[0], cinp)
+        return {"w": wo, "wphase": wp if info[2] else None, "cinp": info[0], "kchunk": info[1]}
+
+    def op_conv_bound(self, x0, weight, bias=None, x1=None, stride=1, pad_t=1, pad_l=1, ups=1, upsampler=False, R1=None, c0=1.0, c1=1.0, act=0,
+                      ldo=0, guard=0, fill=0.0):
+        """weight [O, I, kt, k, k] bound on the device and launched by the engine's conv() on x0 [T,H,W,C0] (+ x1 [T,H,W,C1]), C0 + C1 == I (I % 8 != 0:
+        one source, padded on the device).  The output buffer [rows + guard, ldo] (ldo 0: O) is filled with `fill` before it goes to the device.
+        Returns (out as the device holds it, plan) with plan = ((tile config, split factor), ...) of the launches as the planner gave them."""
+        x0 = _f32(x0); T, H, W, C0 = x0.shape
+        x1a = None if x1 is None else _f32(x1); C1 = 0 if x1 is None else x1a.shape[-1]
+        w = _f32(weight); O, I, kt, k, _ = w.shape
+        b = None if bias is None else _f32(bias)
+        rows = T * (H * ups // stride) * (W * ups // stride)
+        r = None if R1 is None else _f32(R1).reshape(rows, O)
+        ldo = ldo or O
+        out = np.full((rows + guard, ldo), fill, np.float32)
+        plan = (C.c_int * 9)()
+        self._ck(self.lib.ug_op_conv_bound(self.ctx, _ptr(w), _ptr(b), I, O, kt, k, int(bool(upsampler)), _ptr(x0), C0, _ptr(x1a), C1, T, H, W,
+                                           stride, pad_t, pad_l, ups, _ptr(r), c0, c1, act, int(ldo), int(guard), _ptr(out), plan))
+        return out, tuple((plan[1 + 2 * i], plan[2 + 2 * i]) for i in range(plan[0]))
 
     def op_attn_wide(self, qkv, T, S):
         q = _f32(qkv); Cc = q.shape[1] // 3

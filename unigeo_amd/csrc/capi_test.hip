@@ -774,6 +774,55 @@ int ug_op_conv_wide(ug_ctx* x, const float* xin, int T, int H, int W, int C, con
     down32(c, dO, out, Mo * O);
   });
 }
+// ---- one convolution bound on the device and launched by the engine's conv(), as every convolution of the models is (tests/test_conv_bound_gpu.py).
+// The raw checkpoint-layout weight goes through bind_conv (k_permute_conv_w, k_rechunk_conv_w, k_upsample_phase_w), not through pack_conv_weight.
+static Conv bind_op_conv(Ctx& c, const std::string& name, const float* weight, const float* bias, int cin, int O, int kt, int k, int upsampler) {
+  UG_REQUIRE(weight && cin >= 1 && O >= 1 && k >= 1 && (kt == 1 || (kt == 3 && k == 1)), "bound conv: weight [O][cin][k][k] or [O][cin][3][1][1]");
+  if (kt > 1) upload_raw(c, name + ".weight", 1, {O, cin, kt, 1, 1}, weight);
+  else upload_raw(c, name + ".weight", 1, {O, cin, k, k}, weight);
+  if (bias) upload_raw(c, name + ".bias", 1, {O}, bias);
+  return test_bind_conv(c, name, cin, O, kt, k, bias != nullptr, upsampler != 0);
+}
+int ug_op_bind_conv(ug_ctx* x, const float* weight, const float* bias, int cin, int O, int kt, int k, int upsampler,
+                    float* w_out, float* wphase_out, int* info_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c); BindScope bs(c, "op_bind_conv.");
+    UG_REQUIRE(w_out && info_out, "ug_op_bind_conv: w_out and info_out must not be NULL");
+    const Conv cv = bind_op_conv(c, "op_bind_conv.conv", weight, bias, cin, O, kt, k, upsampler);
+    finish_binding(c, "op_bind_conv.");
+    info_out[0] = cv.cinp; info_out[1] = cv.kchunk; info_out[2] = cv.wphase != nullptr;
+    down16(c, cv.w, w_out, (long)O * kt * k * k * cv.cinp);
+    if (cv.wphase && wphase_out) down16(c, cv.wphase, wphase_out, (long)4 * O * 4 * cv.cinp);
+  });
+}
+int ug_op_conv_bound(ug_ctx* x, const float* weight, const float* bias, int cin, int O, int kt, int k, int upsampler,
+                     const float* x0, int C0, const float* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
+                     const float* R1, float c0, float c1, int act, long ldo, long guard, float* out_inout, int* plan_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c); BindScope bs(c, "op_conv_bound.");
+    UG_REQUIRE(x0 && out_inout && T >= 1 && H >= 1 && W >= 1 && guard >= 0 && C0 >= 1 && C1 >= 0 && (C1 == 0 || x1), "ug_op_conv_bound: shape");
+    UG_REQUIRE((ups == 1 || ups == 2) && stride >= 1 && (H * ups) % stride == 0 && (W * ups) % stride == 0, "ug_op_conv_bound: stride must divide the frame");
+    UG_REQUIRE(ldo >= O, "ug_op_conv_bound: rows narrower than the output channels");
+    const Conv cv = bind_op_conv(c, "op_conv_bound.conv", weight, bias, cin, O, kt, k, upsampler);
+    finish_binding(c, "op_conv_bound.");
+    const long px = (long)T * H * W, rows = (long)T * (H * ups / stride) * (W * ups / stride);
+    const f16* d0 = up16(c, x0, px * C0); const f16* d1 = C1 ? up16(c, x1, px * C1) : nullptr;
+    if (cin % 8 != 0) {      // a source narrower than the bound weight's padded channel count: zero channels behind it, as the VAE decoder does for its latent
+      UG_REQUIRE(C1 == 0 && C0 == cin, "ug_op_conv_bound: cin % 8 != 0 takes one source of cin channels");
+      f16* dp = c.ws.get<f16>(px * cv.cinp);
+      launch_pad_channels(d0, cin, dp, cv.cinp, px, c.stream);
+      d0 = dp; C0 = cv.cinp;
+    }
+    UG_REQUIRE(C0 % 8 == 0 && C1 % 8 == 0 && C0 + C1 == cv.cinp, "ug_op_conv_bound: C0 + C1 must be the bound channel count, each a multiple of 8");
+    const f16* dR = up16_opt(c, R1, rows * O);
+    f16* dO = up16(c, out_inout, (rows + guard) * ldo);
+    std::vector<int> plan;
+    test_conv_bound(c, cv, d0, C0, d1, C1, T, H, W, stride, pad_t, pad_l, ups, dR, c0, c1, act, dO, ldo, &plan);
+    UG_REQUIRE(plan.size() == 2 || plan.size() == 8, "ug_op_conv_bound: one launch, or the four phase launches");
+    if (plan_out) { plan_out[0] = (int)plan.size() / 2; for (size_t i = 0; i < 8; ++i) plan_out[1 + i] = i < plan.size() ? plan[i] : -1; }
+    down16(c, dO, out_inout, (rows + guard) * ldo);
+  });
+}
 int ug_op_attn_wide(ug_ctx* x, const float* qkv, int T, int S, int C, float* out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);

@@ -180,6 +180,7 @@ struct Ctx {
                              // last round of ONE kernel are off - the fused feed-forward takes all rows (no two-GEMM tail), the tile planner ignores the last-round fill
   int ff_variant = 0, flash_variant = -1;   // ug_tune_ff / ug_tune_flash: per-context A/B overrides copied into FFusedP / FlashP (0 / -1 = the defaults)
   GemmTune tune;             // ug_tune_force: tile-config / split-K / knob overrides for THIS context's GEMM launches (tests, A/B tools)
+  std::vector<int>* plan_log = nullptr;   // test_conv_bound: run_gemm appends the planner's (tile config, split factor) of every launch; null in the product
 };
 
 void* pinned(Ctx& c, int slot, size_t bytes);   // page-locked staging buffer of at least `bytes`
@@ -214,6 +215,13 @@ void attn_wide_core(Ctx& c, const float* qkv, int T, int S, int C, float* ao);
 // raw tensors name + ".weight" [cout][cin][k][k] (+ ".bias") -> bind_conv -> dup_conv; x fp32 [T,H,W,cin] -> split_pair -> conv_w -> out fp32 (+ res fp32, may be out)
 void test_conv_wide(Ctx& c, const std::string& name, bool bias, const float* x, int T, int H, int W, int cin, int cout, int k, int stride, int pad_t, int pad_l,
                     float* out, const float* res);
+// one convolution bound and launched as the graphs do it (op-level tests): test_bind_conv = bind_conv on the raw tensors name + ".weight"
+// [cout][cin][k][k] / [cout][cin][kt][1][1] (+ ".bias"), the bound copies in c.persist (the caller releases its mark); test_conv_bound = the engine's conv()
+// on device tensors - with ups == 2 and a bound wphase the four sub-pixel phase launches - with one optional residual, out [rows][ldo] (ldo 0: cout).
+// plan (may be NULL): the planner's (tile config, split factor) of every GEMM launch, in launch order.
+Conv test_bind_conv(Ctx& c, const std::string& name, int cin, int cout, int kt, int k, bool bias, bool upsampler);
+void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
+                     const f16* R1, float c0, float c1, int act, f16* out, long ldo, std::vector<int>* plan);
 
 // ---- StableNormal (sn_graphs.inc) ----
 void bind_sn(Ctx& c, const UNetCfg& ucfg, const VAECfg& vcfg, const CLIPCfg& dcfg, const std::string& prefix);   // "<prefix>{vae,unet_yoso,controlnet_yoso,unet,controlnet_dino,dino}."

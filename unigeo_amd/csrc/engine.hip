@@ -225,6 +225,7 @@ static void run_gemm(Ctx& c, GemmP p, int batch, const char* tag, float alg = 1.
   int cfg, split;
   gemm_plan(p, batch, &cfg, &split);
   p.cfg_p1 = cfg + 1; p.splitk = split;
+  if (c.plan_log) { c.plan_log->push_back(cfg); c.plan_log->push_back(split); }
   const size_t mk = c.ws.mark();
   if (split > 1) p.partial = c.ws.get<float>((long)split * p.M * p.N);
   {
@@ -1357,6 +1358,20 @@ void test_conv_wide(Ctx& c, const std::string& name, bool bias, const float* x, 
   split_pair(c, x, xp, M, cin);
   conv_w(c, xp, T, H, W, cw, stride, pad_t, pad_l, out, res);
   c.ws.release(mk);
+}
+// one convolution through the product's own binding and launch code on its own (op-level tests; engine.h)
+Conv test_bind_conv(Ctx& c, const std::string& name, int cin, int cout, int kt, int k, bool bias, bool upsampler) {
+  return bind_conv(c, name, cin, cout, kt, k, bias, upsampler);
+}
+void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
+                     const f16* R1, float c0, float c1, int act, f16* out, long ldo, std::vector<int>* plan) {
+  Epi e; e.R1 = R1; e.c0 = c0; e.c1 = c1; e.act = act;
+  struct Log {   // the log leaves the context on every way out
+    Ctx& c;
+    Log(Ctx& c_, std::vector<int>* v) : c(c_) { c.plan_log = v; }
+    ~Log() { c.plan_log = nullptr; }
+  } log(c, plan);
+  conv(c, x0, C0, x1, C1, T, H, W, cv, stride, pad_t, pad_l, ups, out, e, ldo);
 }
 
 static f16* vae_encode_wide(Ctx& c, VAE& v, const f16* x8, int T, int H, int W) {
