@@ -25,6 +25,25 @@ int ug_bench_flash(ug_ctx* ctx, int B, int H, int S, int variant, int iters, flo
 int ug_bench_ff(ug_ctx* ctx, int M, int C, int fused, int iters, float* us_out);
 int ug_op_ff(ug_ctx* ctx, const float* X, int M, int C, const float* W1, const float* b1, const float* W2, const float* b2, const float* R1,
              float c0, float c1, int fused, float* out);
+/* Every launch form of that feed-forward (tests/test_ff_forms_gpu.py): out = c0 * FF(xn) + c1 * r1 + c2 * R2, FF(xn) = GEGLU(xn W1^T + b1) W2^T + b2.
+ *   operands : b2 may be NULL.  The residual r1: none (R1 NULL, r1_is_x 0), the stream itself (r1_is_x != 0, R1 NULL: the device pointer of X) or a
+ *              separate tensor R1 [M,C]; R2 [M,C] may be NULL.  gamma NULL: no pre-norm, xn = X.  Else xn = fp16(LayerNorm(x') * gamma + beta) with
+ *              x' = fp16(X + addvec[row / rows_per_vec]) (addvec NULL: x' = X), and with addvec the stream residual is x' as well; a separate R1 next
+ *              to addvec is the launcher's refusal (an error).
+ *   mode     : 0 / 1 / 2 as ug_op_ln_ff (LayerNorm launch + two GEMMs / LayerNorm launch + fused kernel / all in the fused kernel; without pre-norm 1
+ *              and 2 are the same launch; mode 0 takes no R2).  3: the engine's own ln_ff, called as transformer_forward calls it on a Lin pair and a
+ *              Norm built from these tensors (pre-norm and r1_is_x required): ug_set_ff_fused and M decide between the fused kernel, its in-kernel
+ *              LayerNorm and the whole-rounds row split with its LayerNorm + two-GEMM tail.  The kernel variant is the context's (ug_tune_ff).
+ *   max_wg   : FFusedP::max_wg, a cap on the fused kernel's grid (0 = the launcher's choice, the only value the product uses; modes 1 and 2 only): at
+ *              small M one workgroup then walks several 128-row tiles, as every workgroup of the product's launches does.
+ *   guards   : X, R1 and R2 hold M + in_guard rows and, with in_guard > 0, addvec one vector more than ceil(M / rows_per_vec); all of it goes to the
+ *              device as given while the kernels are told M.  out_inout [M + out_guard, C] is uploaded as given and all of it comes back.
+ *   info_out : [3] (may be NULL) = the grid of the fused launch, the largest number of tiles one of its workgroups walked, the rows it took (M in
+ *              modes 1 and 2, the whole rounds M1 in mode 3); all 0 when no fused kernel ran. */
+int ug_op_ff_ex(ug_ctx* ctx, const float* X, int M, int C, const float* W1, const float* b1, const float* W2, const float* b2,
+                const float* R1, int r1_is_x, const float* R2, float c0, float c1, float c2,
+                const float* gamma, const float* beta, float eps, const float* addvec, int rows_per_vec,
+                int mode, int max_wg, long in_guard, long out_guard, float* out_inout, int* info_out /*[3]*/);
 /* Parity instrumentation (no reference counterpart; the reference would use the pipeline's callback_on_step_end): while
  * host_latents != NULL, ug_dc_run copies the latents after each of the first `steps` Euler steps to
  * host_latents[step][T][h][w][4] (float32, channels-last).  NULL switches it off.  Costs one host sync per step. */

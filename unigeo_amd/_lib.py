@@ -25,7 +25,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
-    "ug_op_bind_conv", "ug_op_conv_bound",
+    "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
@@ -202,6 +202,8 @@ def load_library():
     _set_argtypes(lib, {
         "ug_op_bind_conv": [vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, vp],
         "ug_op_conv_bound": [vp, vp, vp, ip, ip, ip, ip, ip, vp, ip, vp, ip, ip, ip, ip, ip, ip, ip, ip, vp, C.c_float, C.c_float, ip, C.c_long, C.c_long, vp, vp]})
+    _set_argtypes(lib, {"ug_op_ff_ex": [vp, vp, ip, ip, vp, vp, vp, vp, vp, ip, vp, C.c_float, C.c_float, C.c_float, vp, vp, C.c_float, vp, ip,
+                                        ip, ip, C.c_long, C.c_long, vp, vp]})
     lib.ug_bind_stablenormal.argtypes = [vp, C.POINTER(UNetConfigC), C.POINTER(VAEConfigC), C.POINTER(CLIPConfigC)]
     lib.ug_sn_run.argtypes = [vp, vp, ip, ip, ip, vp, C.c_float, ip, vp, vp, vp, vp]
     lib.ug_sn_unet_forward.argtypes = [vp, ip, vp, vp, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]
@@ -495,6 +497,30 @@ class Engine:
         self._ck(self.lib.ug_op_ff(self.ctx, _ptr(X), M, Cc, _ptr(_f32(W1)), _ptr(_f32(b1)), _ptr(_f32(W2)), _ptr(_f32(b2)), _ptr(r),
                                    float(c0), float(c1), int(bool(fused)), _ptr(out)))
         return out
+
+    def op_ff_ex(self, X, W1, b1, W2, b2=None, R1=None, R2=None, c0=1.0, c1=1.0, c2=1.0, gamma=None, beta=None, eps=1e-5, addvec=None, rows_per_vec=1,
+                 mode=2, max_wg=0, in_guard=0, out=None, out_guard=0):
+        """Every launch form of the feed-forward (ug_op_ff_ex in include/unigeo_hip_test.h).  R1: None, the string "x" (the stream X itself) or an
+        array; X, R1 and R2 hold M + in_guard rows and, with in_guard > 0, addvec one vector more than ceil(M / rows_per_vec).  out [M + out_guard, C]
+        (None: zeros) goes to the device as given.  Returns (the whole output buffer as the device holds it, (grid, most tiles walked by one
+        workgroup, rows the fused kernel took))."""
+        X = _f32(X); Cc = X.shape[1]; M = X.shape[0] - in_guard
+        r1_is_x = isinstance(R1, str)
+        assert not r1_is_x or R1 == "x", R1
+        r1 = None if R1 is None or r1_is_x else _f32(R1)
+        r2 = None if R2 is None else _f32(R2)
+        av = None if addvec is None else _f32(addvec)
+        assert M >= 1 and all(a is None or a.shape == X.shape for a in (r1, r2)), (X.shape, in_guard)
+        if av is not None:
+            assert av.shape == ((M + rows_per_vec - 1) // rows_per_vec + (1 if in_guard else 0), Cc), av.shape
+        buf = np.zeros((M + out_guard, Cc), np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+        assert buf.shape == (M + out_guard, Cc), buf.shape
+        opt = lambda a: None if a is None else _f32(a)
+        info = (C.c_int * 3)()
+        self._ck(self.lib.ug_op_ff_ex(self.ctx, _ptr(X), M, Cc, _ptr(_f32(W1)), _ptr(_f32(b1)), _ptr(_f32(W2)), _ptr(opt(b2)), _ptr(r1), int(r1_is_x), _ptr(r2),
+                                      float(c0), float(c1), float(c2), _ptr(opt(gamma)), _ptr(opt(beta)), float(eps), _ptr(av), int(rows_per_vec),
+                                      int(mode), int(max_wg), int(in_guard), int(out_guard), _ptr(buf), info))
+        return buf, tuple(info)
 
     def set_fp8_linears(self, on=True):
         """MX-fp8 matrix instructions for the UNet transformers' linear layers (BASELINE configs[4]); reduced precision, default off."""

@@ -455,6 +455,63 @@ int ug_op_ff(ug_ctx* x, const float* X, int M, int C, const float* W1, const flo
   });
 }
 
+// Every launch form of the feed-forward (tests/test_ff_forms_gpu.py; the contract stands in include/unigeo_hip_test.h).  X, R1 and R2 go to the device
+// with their in_guard rows and addvec with its extra vector, the kernels are told M; out_inout goes up as given and all of it comes back.
+int ug_op_ff_ex(ug_ctx* x, const float* X, int M, int C, const float* W1, const float* b1, const float* W2, const float* b2,
+                const float* R1, int r1_is_x, const float* R2, float c0, float c1, float c2,
+                const float* gamma, const float* beta, float eps, const float* addvec, int rows_per_vec,
+                int mode, int max_wg, long in_guard, long out_guard, float* out_inout, int* info_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const bool pre = gamma != nullptr;
+    UG_REQUIRE(X && W1 && b1 && W2 && out_inout && M >= 1 && C >= 1 && mode >= 0 && mode <= 3 && max_wg >= 0 && in_guard >= 0 && out_guard >= 0 && !(R1 && r1_is_x),
+               "ug_op_ff_ex: arguments");
+    UG_REQUIRE(!addvec || (pre && rows_per_vec >= 1), "ug_op_ff_ex: addvec belongs to the pre-norm, rows_per_vec >= 1");
+    const int I = 4 * C;
+    const long rows_in = M + in_guard;
+    std::vector<float> w1, bb1;
+    pack_geglu(W1, b1, 2 * I, C, w1, bb1);
+    f16* dX = up16(c, X, rows_in * C);
+    f16* dR1 = r1_is_x ? dX : up16_opt(c, R1, rows_in * C);
+    f16* dR2 = up16_opt(c, R2, rows_in * C);
+    f16* dW1 = up16(c, w1.data(), (long)2 * I * C); f16* db1 = up16(c, bb1.data(), 2 * I);
+    f16* dW2 = up16(c, W2, (long)C * I); f16* db2 = up16_opt(c, b2, C);
+    f16* dg = up16_opt(c, gamma, C); f16* dbt = up16_opt(c, beta, C);
+    const long nvec = addvec ? (M + rows_per_vec - 1) / rows_per_vec + (in_guard > 0 ? 1 : 0) : 0;
+    f16* dav = up16_opt(c, addvec, nvec * C);
+    f16* dO = up16(c, out_inout, (M + out_guard) * C);
+    int grid = 0; long m1 = 0;
+    if (mode == 3) {
+      UG_REQUIRE(pre && beta && r1_is_x && max_wg == 0, "ug_op_ff_ex mode 3: the engine's ln_ff takes a pre-norm, the stream as residual and its own grid");
+      m1 = test_ln_ff(c, dX, M, C, dg, dbt, eps, dav, rows_per_vec, dW1, db1, dW2, db2, dR2, c0, c1, c2, dO);
+      if (m1 > 0) grid = ff_fused_grid(ff_fused(c, dX, (int)m1, C, dW1, db1, dW2, db2, dX, c0, c1, dO));
+    } else {
+      const f16* xin = dX; const f16* res = dR1;
+      if (pre && mode != 2) {   // the LayerNorm launch the in-kernel form replaces: it writes the normalised rows and the stream x'
+        UG_REQUIRE(beta && (!dav || !dR1 || dR1 == dX), "ug_op_ff_ex pre-norm: beta missing / residual is not the normalised stream");
+        f16* t1 = c.ws.get<f16>((long)M * C); f16* xo = dav ? c.ws.get<f16>((long)M * C) : nullptr;
+        LayerNormP l; memset(&l, 0, sizeof(l));
+        l.X = dX; l.Y = t1; l.M = M; l.C = C; l.eps = eps; l.gamma = dg; l.beta = dbt; l.addvec = dav; l.rows_per_vec = rows_per_vec; l.Xout = xo;
+        launch_layernorm(l, c.stream);
+        xin = t1;
+        if (dav && dR1) res = xo;
+      }
+      if (mode == 0) {
+        UG_REQUIRE(!R2 && max_wg == 0, "ug_op_ff_ex mode 0: the two-launch path takes one residual and has no grid cap");
+        ff_two_launch(c, xin, M, C, dW1, db1, dW2, db2, res, c0, c1, c.ws.get<f16>((long)M * I), dO);
+      } else {
+        FFusedP p = ff_fused(c, xin, M, C, dW1, db1, dW2, db2, res, c0, c1, dO);
+        p.R2 = dR2; p.c2 = c2; p.max_wg = max_wg;
+        if (pre && mode == 2) { p.ln_g = dg; p.ln_b = dbt; p.ln_eps = eps; p.addvec = dav; p.rows_per_vec = rows_per_vec; }
+        launch_ff_fused(p, c.stream);
+        grid = ff_fused_grid(p); m1 = M;
+      }
+    }
+    down16(c, dO, out_inout, (M + out_guard) * C);
+    if (info_out) { info_out[0] = grid; info_out[1] = grid ? (int)(((m1 + 127) / 128 + grid - 1) / grid) : 0; info_out[2] = (int)m1; }
+  });
+}
+
 int ug_op_linear_mx8(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, int geglu, float* out,
                      unsigned char* a8_out, unsigned* sa_out) {
   UG_TRY(x, {

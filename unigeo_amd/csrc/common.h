@@ -109,6 +109,8 @@ void gemm_plan(const GemmP& p, int batch, int* cfg_out, int* split_out);   // he
 struct FFusedP {
   const f16* X; const f16* W1; const f16* b1; const f16* W2; const f16* b2;
   const f16* R1; const f16* R2; float c0, c1, c2;
+  int max_wg;             // cap on the launch grid, 0 = the launcher's choice (the product; ug_op_ff_ex makes a workgroup walk several tiles at small M).
+                          // It sits in the padding behind c2 and adds nothing to the kernels' argument block
   f16* Out; int M, C; const f16* zero;
   // optional pre-norm, done on the X tile in LDS (what launch_layernorm would have written, same roundings):
   //   x' = fp16(X + addvec[row / rows_per_vec]) (addvec optional), X_used = fp16(LayerNorm(x') * ln_g + ln_b);
@@ -116,7 +118,9 @@ struct FFusedP {
   const f16* ln_g; const f16* ln_b; float ln_eps; const f16* addvec; int rows_per_vec;
   int variant;            // 0 = default (cross-tile prefetch), 1 = without it (A/B; Ctx::ff_variant, ug_tune_ff)
 };
+static_assert(sizeof(FFusedP) == 136, "FFusedP: max_wg must stay in the padding behind c2");
 bool ff_fused_supported(int C);
+int ff_fused_grid(const FFusedP& p);   // workgroups launch_ff_fused launches for p (each walks tiles blockIdx, + grid, ...)
 void launch_ff_fused(const FFusedP& p, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------

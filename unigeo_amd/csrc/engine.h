@@ -222,6 +222,12 @@ void test_conv_wide(Ctx& c, const std::string& name, bool bias, const float* x, 
 Conv test_bind_conv(Ctx& c, const std::string& name, int cin, int cout, int kt, int k, bool bias, bool upsampler);
 void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
                      const f16* R1, float c0, float c1, int act, f16* out, long ldo, std::vector<int>* plan);
+// the pre-norm feed-forward of one transformer block on its own (op-level tests): the engine's ln_ff() called as transformer_forward calls it - a Lin pair
+// (W1 [8C][C] / b1 in the bound GEGLU row order, W2 [C][4C] / b2) and a Norm built from device tensors, the residual stream x' = fp16(x + addvec[row /
+// rows_per_vec]) (addvec NULL: x) as R1, optionally R2: out = c0 * FF(LayerNorm(x')) + c1 * x' + c2 * R2, through whichever of the fused kernel, its
+// in-kernel LayerNorm and the whole-rounds row split the context's switches and M select.  Returns the rows the fused kernel took (0: none).
+long test_ln_ff(Ctx& c, const f16* x, long M, int C, const f16* gamma, const f16* beta, float eps, const f16* addvec, long rows_per_vec,
+                const f16* W1, const f16* b1, const f16* W2, const f16* b2, const f16* R2, float c0, float c1, float c2, f16* out);
 
 // ---- StableNormal (sn_graphs.inc) ----
 void bind_sn(Ctx& c, const UNetCfg& ucfg, const VAECfg& vcfg, const CLIPCfg& dcfg, const std::string& prefix);   // "<prefix>{vae,unet_yoso,controlnet_yoso,unet,controlnet_dino,dino}."

@@ -1373,6 +1373,22 @@ void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x
   } log(c, plan);
   conv(c, x0, C0, x1, C1, T, H, W, cv, stride, pad_t, pad_l, ups, out, e, ldo);
 }
+// the pre-norm feed-forward of a transformer block on its own (op-level tests; engine.h): ln_ff() with the residual stream as transformer_forward hands it over
+long test_ln_ff(Ctx& c, const f16* x, long M, int C, const f16* gamma, const f16* beta, float eps, const f16* addvec, long rows_per_vec,
+                const f16* W1, const f16* b1, const f16* W2, const f16* b2, const f16* R2, float c0, float c1, float c2, f16* out) {
+  Lin f1, f2; Norm ln;
+  f1.w = W1; f1.b = b1; f1.in = C; f1.out = 8 * C;
+  f2.w = W2; f2.b = b2; f2.in = 4 * C; f2.out = C;
+  ln.g = gamma; ln.b = beta; ln.c = C; ln.eps = eps;
+  const size_t mk = c.ws.mark();
+  f16* t1 = c.ws.get<f16>(M * C);
+  f16* xout = addvec ? c.ws.get<f16>(M * C) : nullptr;
+  f16* mid = c.ws.get<f16>(M * 4 * C);
+  Epi e; e.R1 = addvec ? xout : x; e.c0 = c0; e.c1 = c1; e.R2 = R2; e.c2 = c2;
+  ln_ff(c, x, M, ln, addvec, rows_per_vec, xout, t1, f1, f2, mid, out, e, nullptr);
+  c.ws.release(mk);
+  return ff_pair_fusable(c, M, f1, f2, e) ? ff_fused_rows(c, M) : 0;
+}
 
 static f16* vae_encode_wide(Ctx& c, VAE& v, const f16* x8, int T, int H, int W) {
   UG_REQUIRE(v.wide_bound, "float32-grade VAE encoder weights are not bound");

@@ -360,6 +360,14 @@ __global__ __launch_bounds__(512, 2) void ff_fused_kernel(const FFusedP p) {
   }
 }
 
+// one workgroup per CU and tile round (two where two workgroups' LDS fit a CU: C = 64), capped by FFusedP::max_wg; the same for both variants
+int ff_fused_grid(const FFusedP& p) {
+  const size_t lds = (size_t)(p.C / 64 + 3 + 1) * 128 * 64 * sizeof(f16);
+  const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / lds)));
+  const int grid = std::min((p.M + 127) / 128, per_cu * 256);
+  return p.max_wg > 0 ? std::min(grid, p.max_wg) : grid;
+}
+
 // FFusedP::variant (per launch; the engine passes its context's - ug_tune_ff): 0 = the kernel above with the cross-tile prefetch (default), 1 = without
 // it (the round-2 kernel, A/B); UG_EXPERIMENTS builds: 100 + mask = the timing-only ablations of tools/bench_ff.py (WRONG results)
 template <int KT>
@@ -368,14 +376,14 @@ static void launch_ff_t(const FFusedP& p, hipStream_t s) {
   static bool attr[32] = {};
   bool& at = attr[ug_dev_slot()];
   if (!at) { UG_CHECK(hipFuncSetAttribute((const void*)ff_fused_kernel<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); at = true; }
-  const int ntiles = (p.M + 127) / 128;
   const int variant = p.variant;
+  const int grid = ff_fused_grid(p);
 #ifdef UG_EXPERIMENTS
   if (variant >= 100) {
     if constexpr (KT == 5) {
       auto go = [&](auto kern) {
         UG_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(std::min(ntiles, 256)), dim3(512), lds, s, p);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
       };
       switch (variant - 100) {
         case 1: go(ff_fused_kernel<5, 1>); break;  case 2: go(ff_fused_kernel<5, 2>); break;   case 4: go(ff_fused_kernel<5, 4>); break;
@@ -395,13 +403,10 @@ static void launch_ff_t(const FFusedP& p, hipStream_t s) {
       static bool attrx[32] = {};
       bool& atx = attrx[ug_dev_slot()];
       if (!atx) { UG_CHECK(hipFuncSetAttribute((const void*)ff_fused_kernel<KT, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); atx = true; }
-      const int per_cu_x = std::max(1, std::min(2, (int)((160 * 1024) / lds)));
-      hipLaunchKernelGGL((ff_fused_kernel<KT, 0, true>), dim3(std::min(ntiles, per_cu_x * 256)), dim3(512), lds, s, p);
+      hipLaunchKernelGGL((ff_fused_kernel<KT, 0, true>), dim3(grid), dim3(512), lds, s, p);
       return;
     }
   }
-  const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / lds)));
-  const int grid = std::min(ntiles, per_cu * 256);
   hipLaunchKernelGGL(ff_fused_kernel<KT>, dim3(grid), dim3(512), lds, s, p);
 }
 
