@@ -167,7 +167,9 @@ int ug_normals_from_depth(ug_ctx* ctx, const float* depth_thw, const float* intr
  * (depth [T,H,W] / normals [T,H,W,3]); gt / mask are host arrays (mask: 1 byte per pixel, may be NULL).
  *   ug_eval_depth  : replaces depth_evaluation(..., custom_mask, align_with_lstsq=True) (metrics/eval_depth.py:6-246,
  *                    metrics/alignment.py:150-167) -> out[11] = AbsRel, SqRel, RMSE, LogRMSE, d<1, d<1.25, d<1.25^2,
- *                    d<1.25^3, valid_pixels, scale, shift
+ *                    d<1.25^3, valid_pixels, scale, shift.  mask1 = 0 < gt < max_depth (a NaN or non-positive max_depth selects no
+ *                    pixel).  In every ug_eval_depth* call the prediction must be free of NaN on mask1: such a pixel is read as -inf
+ *                    (s comes out NaN here, UG_ALIGN_L1 rejects it)
  *   ug_eval_normal : replaces normal_evaluation (metrics/eval_normal.py:4-72) -> out[8] = mean, median, rmse,
  *                    %<5, %<7.5, %<11.25, %<22.5, %<30 */
 int ug_eval_depth(ug_ctx* ctx, const float* pred_depth, const float* gt_depth, const unsigned char* custom_mask, long n,
@@ -225,7 +227,7 @@ int ug_eval_depth_l1_info(ug_ctx* ctx, long* out_info /*[4]*/);
  * pred_disp == NULL with the flag: the resident DISPARITY of the last ug_dc_run / ug_dc_run_windows - x = (m - lo) / (hi - lo), m the channel
  * mean of the resident decoded frames and (lo, hi) its min and max over the clip, the value the resident depth 1 / (x + 0.1f) was made from -
  * produced at evaluation time from the resident frames; ug_dc_get_disparity copies the same array to the host ([T*H*W], min 0, max 1).  Without
- * the flag pred == NULL is the resident depth, and with flags == 0 and the floor off the call is ug_eval_depth_ex: its launches, its bytes.
+ * the flag pred == NULL is the resident depth, and with flags == 0 and the floor off the call is ug_eval_depth_ex: one shared body, its bytes.
  * ug_eval_depth_l1_info reports the last UG_ALIGN_L1 fit of either call.  Errors (ug_last_error; the context stays usable): an unknown flag bit;
  * a disp_clip_min that is not NaN and is <= 0 or infinite; a disp_clip_min without the flag; pred == NULL without a resident output of that
  * size (for the disparity: before any run); everything ug_eval_depth_ex rejects.  Scratch: 4 bytes per pixel more than ug_eval_depth_ex (8 with

@@ -86,6 +86,12 @@ DEPTH_ALIGN_DISPARITY = 1                                                # UG_DE
 PREP_DEPTH_F64, PREP_ZOOMED = 1, 2                                       # UG_PREP_* of include/unigeo_hip.h
 REG_DROP_SENTINEL = 1                                                    # UG_REG_* of include/unigeo_hip.h
 
+
+def _depth_opts(alignment, max_depth, clips):
+    """``ug_depth_eval_opts``: ``None`` (no depth bound, a clip that is off) travels as NaN."""
+    return DepthEvalOptsC(DEPTH_ALIGNMENTS[alignment], *[float("nan") if v is None else float(v) for v in (max_depth, *clips)])
+
+
 _lib = None
 
 
@@ -642,8 +648,7 @@ class Engine:
         if space == "depth" and alignment == "lstsq" and max_depth is not None and not return_error_map and all(c is None for c in clips):
             self._ck(self.lib.ug_eval_depth(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, float(max_depth), _ptr(out)))
         else:
-            o = DepthEvalOptsC(DEPTH_ALIGNMENTS[alignment], float("nan") if max_depth is None else float(max_depth),
-                               *[float("nan") if c is None else float(c) for c in clips])
+            o = _depth_opts(alignment, max_depth, clips)
             emap = np.empty(g.shape, np.float32) if return_error_map else None
             if space == "depth":
                 self._ck(self.lib.ug_eval_depth_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), n, C.byref(o), _ptr(out), _ptr(emap)))
@@ -677,8 +682,7 @@ class Engine:
         pose, k = _f32(cam2world).reshape(T, 4, 4), _f32(intrinsics).reshape(T, 3, 3)
         p = None if pred is None else _f32(pred).reshape(T, H, W)
         m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8)).reshape(T, H, W)
-        o = DepthEvalOptsC(DEPTH_ALIGNMENTS["lstsq"], float("nan") if max_depth is None else float(max_depth),
-                           *[float("nan") if c is None else float(c) for c in (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)])
+        o = _depth_opts("lstsq", max_depth, (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max))
         out = np.zeros(13, np.float64)
         rmap = np.empty(g.shape, np.float32) if return_radius_map else None
         self._ck(self.lib.ug_eval_depth_global(self.ctx, _ptr(p), _ptr(g), _ptr(gr), _ptr(pose), _ptr(k), _ptr(m), T, H, W, C.byref(o), _ptr(out),
@@ -701,8 +705,7 @@ class Engine:
         T, H, W = g.shape
         pose, k = _f32(cam2world).reshape(T, 4, 4), _f32(intrinsics).reshape(T, 3, 3)
         p = None if pred is None else _f32(pred).reshape(T, H, W)
-        o = DepthEvalOptsC(DEPTH_ALIGNMENTS["lstsq"], float("nan") if max_depth is None else float(max_depth),
-                           *[float("nan") if c is None else float(c) for c in (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max)])
+        o = _depth_opts("lstsq", max_depth, (pre_clip_min, pre_clip_max, post_clip_min, post_clip_max))
         fit = np.zeros(2, np.float32)
         pts = np.empty((T, H, W, 3), np.float32) if return_points else None
         self._ck(self.lib.ug_pcd_world_points(self.ctx, _ptr(p), _ptr(g), _ptr(pose), _ptr(k), T, H, W, C.byref(o), _ptr(fit), _ptr(pts)))

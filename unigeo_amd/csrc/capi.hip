@@ -239,13 +239,19 @@ static void lstsq_solve(const double* a, double& s_, double& t_) {
     else { const double cm = a[1] / a[0], gm = a[3] / a[0]; s_ = cm * gm / (cm * cm + 1.0); t_ = gm / (cm * cm + 1.0); }
   }
 }
-// host half of the least-squares alignment (waits for the stream), after launch_depth_fit / launch_depth_fit_ex left their nb partial sums in `part`
+// host half of the least-squares alignment (waits for the stream), after a fit launch left its nb partial sums in `part`
 static void fetch_lstsq(Ctx& c, const double* part, int nb, double& s_, double& t_) {
   double a[5];
   fetch_partial_sums(c, part, nb, a);
   lstsq_solve(a, s_, t_);
 }
-// host half of the metrics pass, after launch_depth_metrics / launch_depth_metrics_ex (waits for the stream): out[11] as include/unigeo_hip.h documents it
+// the least-squares alignment of the pre-clipped prediction against fit_g on its mask1: launch, fetch, solve (part: EVAL_MAXB * 5 doubles)
+static void fit_lstsq(Ctx& c, const DepthEvalBufs& d, const float* fit_g, const DepthBounds& b, double* part, double& s_, double& t_) {
+  int nb = 0;
+  launch_depth_fit(d.dp, fit_g, d.n, b.md, b.lo, b.hi, part, &nb, c.stream);
+  fetch_lstsq(c, part, nb, s_, t_);
+}
+// host half of the metrics pass, after launch_depth_metrics / launch_radius_metrics (waits for the stream): out[11] as include/unigeo_hip.h documents it
 static void fetch_depth_metrics(Ctx& c, const double* part, int nb, double s_, double t_, double* out) {
   double m[9];
   fetch_partial_sums(c, part, nb, m);
@@ -255,16 +261,6 @@ static void fetch_depth_metrics(Ctx& c, const double* part, int nb, double s_, d
     for (int k = 0; k < 4; ++k) out[4 + k] = m[5 + k] / cnt;
   } else { for (int k = 0; k < 8; ++k) out[k] = 0; }
   out[8] = cnt; out[9] = s_; out[10] = t_;
-}
-static void eval_depth_lstsq(Ctx& c, const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, double* out) {
-  const DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
-  double* part = c.ws.get<double>(1024 * 9);
-  int nb = 0;
-  launch_depth_fit(d.dp, d.dg, n, max_depth, part, &nb, c.stream);
-  double s_, t_;
-  fetch_lstsq(c, part, nb, s_, t_);
-  launch_depth_metrics(d.dp, d.dg, d.dm, n, max_depth, (float)s_, (float)t_, part, &nb, c.stream);
-  fetch_depth_metrics(c, part, nb, s_, t_, out);
 }
 
 // the camera table of k_world_radius / k_world_points on the device: per frame fx, fy, cx, cy, R row-major, t, widened from float32
@@ -278,6 +274,24 @@ static const double* upload_cam_table(Ctx& c, const float* cam2world, const floa
   double* dcam = c.ws.get<double>((long)T * 16); UG_CHECK(hipMemcpy(dcam, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
   return dcam;
 }
+// what ug_eval_depth_global and ug_pcd_world_points share once their own pointers are checked: the shape checks (fewer than pixel_cap pixels), the
+// uploads (gt_radius may be NULL), the camera table and the first fit (s, t) of the depth; part holds EVAL_MAXB * 9 doubles for the launches that follow
+struct WorldFit { long n; DepthBounds b; DepthEvalBufs d; float* dgr; const double* dcam; double* part; double s, t; };
+static WorldFit world_first_fit(Ctx& c, const float* pred, const float* gt, const float* gt_radius, const unsigned char* cmask, const float* cam2world,
+                                const float* K, int T, int H, int W, const ug_depth_eval_opts* o, long pixel_cap) {
+  UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
+  WorldFit f{};
+  f.n = (long)T * H * W;
+  UG_REQUIRE(f.n < pixel_cap, "pixel count");
+  UG_REQUIRE(pred || (c.io_ready && T == c.T && H == c.H && W == c.W), "no resident depth of that shape");
+  f.b = depth_bounds(o);
+  f.d = depth_eval_upload(c, pred, gt, cmask, f.n);
+  if (gt_radius) { f.dgr = c.ws.get<float>(f.n); UG_CHECK(hipMemcpy(f.dgr, gt_radius, f.n * 4, hipMemcpyHostToDevice)); }
+  f.dcam = upload_cam_table(c, cam2world, K, T);
+  f.part = c.ws.get<double>(EVAL_MAXB * 9);
+  fit_lstsq(c, f.d, f.d.dg, f.b, f.part, f.s, f.t);
+  return f;
+}
 
 // ---------------------------------------------------------------- point-cloud evaluation (kernels/pcd.hip)
 // mean and np.median of n doubles on the device: a fixed-order sum, and the one or two middle order statistics by exact selection
@@ -288,13 +302,11 @@ static void pcd_mean_median(Ctx& c, const double* v, long n, unsigned* sel, unsi
   launch_pcd_select(v, 1, n, 1, 0, (unsigned long long)(n / 2), sel, res, 1, c.stream);
   UG_CHECK(hipGetLastError());
   UG_CHECK(hipStreamSynchronize(c.stream));
-  std::vector<double> h((size_t)nb);
-  UG_CHECK(hipMemcpy(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost));
+  double s[1];
+  fetch_partial_sums(c, part, nb, s);
   unsigned long long k[2];
   UG_CHECK(hipMemcpy(k, res, sizeof(k), hipMemcpyDeviceToHost));
-  double s = 0;
-  for (int b = 0; b < nb; ++b) s += h[b];
-  mean = s / (double)n;
+  mean = s[0] / (double)n;
   med = (pcd_unkey_f64(k[0]) + pcd_unkey_f64(k[1])) / 2.0;
 }
 
@@ -483,25 +495,19 @@ static void prep_upload_taps(Ctx& c, const int* idx, const double* w, int n_out,
   *didx = di; *dw = dwt;
 }
 
-// ug_eval_depth_ex and ug_eval_depth_ex2 (DESIGN.md sections 13, 23, 24).  disparity: the prediction (NULL: the resident disparity of the last run,
-// made here from the resident frames and min-max) is fitted against gfit = mask1 ? 1 / (gt + 1e-8f) : 0 by the same fit kernels with the depth bound
-// off, and k_disp_metrics inverts the aligned disparity; floor_ = NaN: no floor.  Without it: the launches and the bits of ug_eval_depth_ex.
-static void eval_depth_modes(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, const ug_depth_eval_opts* o,
+// ug_eval_depth, ug_eval_depth_ex and ug_eval_depth_ex2 (DESIGN.md sections 13, 23, 24): one path, the callers resolve their options into `b`.
+// disparity: the prediction (NULL: the resident disparity of the last run, made here from the resident frames and min-max) is fitted against
+// gfit = mask1 ? 1 / (gt + 1e-8f) : 0 by the same fit kernels with the depth bound off, and the metric kernel inverts the aligned disparity;
+// floor_ = NaN: no floor.
+static void eval_depth_modes(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, int alignment, const DepthBounds& b,
                              bool disparity, float floor_, double* out, float* emap_out) {
   Ctx& c = x->c;
-  UG_REQUIRE(o->alignment >= UG_ALIGN_LSTSQ && o->alignment <= UG_ALIGN_L1, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC / L1)");
+  UG_REQUIRE(alignment >= UG_ALIGN_LSTSQ && alignment <= UG_ALIGN_L1, "unknown depth alignment (UG_ALIGN_LSTSQ / MEDIAN / SCALE / METRIC / L1)");
   UG_REQUIRE(n >= 0 && n < (1L << 32), "pixel count");
-  const bool clips = !std::isnan(o->pre_clip_min) || !std::isnan(o->pre_clip_max) || !std::isnan(o->post_clip_min) || !std::isnan(o->post_clip_max);
-  if (!disparity && o->alignment == UG_ALIGN_LSTSQ && !clips && !emap_out && o->max_depth > 0.f) {   // what ug_eval_depth computes: its launches, its bits
-    eval_depth_lstsq(c, pred, gt, cmask, n, o->max_depth, out);
-    return;
-  }
-  const float md = depth_bound(o->max_depth);
-  const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
   if (disparity && !pred) UG_REQUIRE(c.io_ready && c.out_ready && n == (long)c.T * c.H * c.W, "no resident disparity of that size (run a clip first)");
   DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
-  const float* fit_g = d.dg;      // the target of the fit and its depth bound
-  float fit_md = md;
+  const float* fit_g = d.dg;      // the target of the fit and its bounds
+  DepthBounds fb = b;
   if (disparity) {
     if (!pred) {
       float* dx = c.ws.get<float>(n);
@@ -509,36 +515,34 @@ static void eval_depth_modes(ug_ctx* x, const float* pred, const float* gt, cons
       d.dp = dx;
     }
     float* gfit = c.ws.get<float>(n);
-    launch_disp_target(d.dg, n, md, gfit, c.stream);
-    fit_g = gfit; fit_md = NAN;
+    launch_disp_target(d.dg, n, b.md, gfit, c.stream);
+    fit_g = gfit; fb.md = NAN;
   }
-  double* part = c.ws.get<double>(1024 * 9);
-  int nb = 0;
+  double* part = c.ws.get<double>(EVAL_MAXB * 9);
   double s_ = 0.0, t_ = 0.0;
-  if (o->alignment == UG_ALIGN_LSTSQ) {
-    launch_depth_fit_ex(d.dp, fit_g, n, fit_md, lo, hi, part, &nb, c.stream);
-    fetch_lstsq(c, part, nb, s_, t_);
-  } else if (o->alignment == UG_ALIGN_MEDIAN) {
+  if (alignment == UG_ALIGN_LSTSQ) fit_lstsq(c, d, fit_g, fb, part, s_, t_);
+  else if (alignment == UG_ALIGN_MEDIAN) {
     unsigned* sel = (unsigned*)c.ws.alloc(SEL_WORDS * 4);
-    launch_masked_median(d.dp, fit_g, n, fit_md, lo, hi, sel, c.stream);
+    launch_masked_median(d.dp, fit_g, n, fb.md, fb.lo, fb.hi, sel, c.stream);
     unsigned cnt; float mp, mg;
     read_masked_median(c, sel, cnt, mp, mg);
     if (cnt > 0) { const float sf = mg / mp; s_ = sf; }
-  } else if (o->alignment == UG_ALIGN_SCALE) {
+  } else if (alignment == UG_ALIGN_SCALE) {
     double* wz = c.ws.get<double>(2);
-    launch_weiszfeld_scale(d.dp, fit_g, n, fit_md, lo, hi, 10, wz, part, c.stream);
+    launch_weiszfeld_scale(d.dp, fit_g, n, fb.md, fb.lo, fb.hi, 10, wz, part, c.stream);
     UG_CHECK(hipStreamSynchronize(c.stream));
     double r[2];
     UG_CHECK(hipMemcpy(r, wz, sizeof(r), hipMemcpyDeviceToHost));
     if (r[1] >= 1) s_ = r[0] < 1e-3 ? 1e-3 : r[0];
-  } else if (o->alignment == UG_ALIGN_L1) {
+  } else if (alignment == UG_ALIGN_L1) {
     double st[2];
-    l1_fit_device(c, d.dp, fit_g, n, fit_md, lo, hi, st, x->l1_info);
+    l1_fit_device(c, d.dp, fit_g, n, fb.md, fb.lo, fb.hi, st, x->l1_info);
     s_ = (float)st[0]; t_ = (float)st[1];      // rounded once to float32, as least squares returns them
   } else s_ = 1.0;
   float* dmap = emap_out ? c.ws.get<float>(n) : nullptr;
-  if (disparity) launch_disp_metrics(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, floor_, (float)s_, (float)t_, part, dmap, &nb, c.stream);
-  else launch_depth_metrics_ex(d.dp, d.dg, d.dm, n, md, lo, hi, plo, phi, (float)s_, (float)t_, part, dmap, &nb, c.stream, o->alignment == UG_ALIGN_L1);
+  int nb = 0;
+  launch_depth_metrics(d.dp, d.dg, d.dm, n, b.md, b.lo, b.hi, b.plo, b.phi, floor_, (float)s_, (float)t_, part, dmap, &nb, c.stream,
+                       alignment == UG_ALIGN_L1, disparity);
   fetch_depth_metrics(c, part, nb, s_, t_, out);
   if (emap_out) UG_CHECK(hipMemcpy(emap_out, dmap, n * 4, hipMemcpyDeviceToHost));
 }
@@ -547,8 +551,12 @@ extern "C" {
 
 int ug_eval_depth(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, double* out) {
   UG_TRY(x, {
-    Ctx& c = x->c; Scope sc(c);
-    eval_depth_lstsq(c, pred, gt, cmask, n, max_depth, out);
+    Scope sc(x->c);
+    ug_depth_eval_opts o;
+    ug_depth_eval_opts_default(&o);
+    DepthBounds b = depth_bounds(&o);
+    b.md = max_depth > 0.f ? max_depth : 0.f;      // this entry point tests gt < max_depth: a NaN or non-positive bound selects no pixel
+    eval_depth_modes(x, pred, gt, cmask, n, o.alignment, b, false, NAN, out, nullptr);
   });
 }
 
@@ -562,7 +570,7 @@ int ug_eval_depth_ex(ug_ctx* x, const float* pred, const float* gt, const unsign
   UG_TRY(x, {
     Scope sc(x->c);
     UG_REQUIRE(o != nullptr, "options must not be NULL");
-    eval_depth_modes(x, pred, gt, cmask, n, o, false, NAN, out, emap_out);
+    eval_depth_modes(x, pred, gt, cmask, n, o->alignment, depth_bounds(o), false, NAN, out, emap_out);
   });
 }
 
@@ -581,7 +589,7 @@ int ug_eval_depth_ex2(ug_ctx* x, const float* pred, const float* gt, const unsig
     const float fl = o->disp_clip_min;
     UG_REQUIRE(std::isnan(fl) || (fl > 0.f && std::isfinite(fl)), "disp_clip_min must be finite and positive (NaN: off)");
     UG_REQUIRE(std::isnan(fl) || disparity, "disp_clip_min needs UG_DEPTH_ALIGN_DISPARITY");
-    eval_depth_modes(x, pred, gt, cmask, n, &o->base, disparity, fl, out, emap_out);
+    eval_depth_modes(x, pred, gt, cmask, n, o->base.alignment, depth_bounds(&o->base), disparity, fl, out, emap_out);
   });
 }
 
@@ -613,27 +621,17 @@ int ug_eval_depth_global(ug_ctx* x, const float* pred, const float* gt, const fl
     UG_REQUIRE(o != nullptr, "options must not be NULL");
     UG_REQUIRE(o->alignment == UG_ALIGN_LSTSQ, "depth alignment in global coordinates must be UG_ALIGN_LSTSQ (the reference asserts least squares)");
     UG_REQUIRE(gt && gt_radius && cam2world && K && out, "gt_depth, gt_radius, cam2world, intrinsics and out13 must not be NULL");
-    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
-    const long n = (long)T * H * W;
-    UG_REQUIRE(n < (1L << 32), "pixel count");
-    UG_REQUIRE(pred || (c.io_ready && T == c.T && H == c.H && W == c.W), "no resident depth of that shape");
-    const float md = depth_bound(o->max_depth);
-    const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
-    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, cmask, n);
-    float* dgr = c.ws.get<float>(n); UG_CHECK(hipMemcpy(dgr, gt_radius, n * 4, hipMemcpyHostToDevice));
-    const double* dcam = upload_cam_table(c, cam2world, K, T);
+    const WorldFit f = world_first_fit(c, pred, gt, gt_radius, cmask, cam2world, K, T, H, W, o, 1L << 32);
+    const long n = f.n;
     float* dr = c.ws.get<float>(n);
-    double* part = c.ws.get<double>(1024 * 9);
     int nb = 0;
-    double sd = 0.0, td = 0.0, sr = 0.0, tr = 0.0;
-    launch_depth_fit_ex(d.dp, d.dg, n, md, lo, hi, part, &nb, c.stream);
-    fetch_lstsq(c, part, nb, sd, td);
-    launch_world_radius(d.dp, d.dg, dgr, dcam, n, H, W, md, plo, phi, (float)sd, (float)td, dr, part, &nb, c.stream);
-    fetch_lstsq(c, part, nb, sr, tr);
+    double sr = 0.0, tr = 0.0;
+    launch_world_radius(f.d.dp, f.d.dg, f.dgr, f.dcam, n, H, W, f.b.md, f.b.plo, f.b.phi, (float)f.s, (float)f.t, dr, f.part, &nb, c.stream);
+    fetch_lstsq(c, f.part, nb, sr, tr);
     float* dmap = rmap_out ? c.ws.get<float>(n) : nullptr;
-    launch_radius_metrics(dr, d.dg, dgr, d.dm, n, md, (float)sr, (float)tr, part, dmap, &nb, c.stream);
-    fetch_depth_metrics(c, part, nb, sr, tr, out);
-    out[11] = sd; out[12] = td;
+    launch_radius_metrics(dr, f.d.dg, f.dgr, f.d.dm, n, f.b.md, (float)sr, (float)tr, f.part, dmap, &nb, c.stream);
+    fetch_depth_metrics(c, f.part, nb, sr, tr, out);
+    out[11] = f.s; out[12] = f.t;
     if (rmap_out) UG_CHECK(hipMemcpy(rmap_out, dmap, n * 4, hipMemcpyDeviceToHost));
   });
 }
@@ -647,30 +645,19 @@ int ug_pcd_world_points(ug_ctx* x, const float* pred, const float* gt, const flo
     UG_REQUIRE(o != nullptr, "options must not be NULL");
     UG_REQUIRE(o->alignment == UG_ALIGN_LSTSQ, "the world points align the depth with UG_ALIGN_LSTSQ (as ug_eval_depth_global)");
     UG_REQUIRE(gt && cam2world && K && out_fit, "gt_depth, cam2world, intrinsics and out_fit2 must not be NULL");
-    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
-    const long n = (long)T * H * W;
-    UG_REQUIRE(n < (1L << 31), "pixel count");
-    UG_REQUIRE(pred || (c.io_ready && T == c.T && H == c.H && W == c.W), "no resident depth of that shape");
-    const float md = depth_bound(o->max_depth);
-    const float lo = clip_lo(o->pre_clip_min), hi = clip_hi(o->pre_clip_max), plo = clip_lo(o->post_clip_min), phi = clip_hi(o->post_clip_max);
-    const DepthEvalBufs d = depth_eval_upload(c, pred, gt, nullptr, n);
-    const double* dcam = upload_cam_table(c, cam2world, K, T);
-    double* part = c.ws.get<double>(1024 * 9);
-    int nb = 0;
-    double sd = 0.0, td = 0.0;
-    launch_depth_fit_ex(d.dp, d.dg, n, md, lo, hi, part, &nb, c.stream);
-    fetch_lstsq(c, part, nb, sd, td);
+    const WorldFit f = world_first_fit(c, pred, gt, nullptr, nullptr, cam2world, K, T, H, W, o, 1L << 31);
+    const long n = f.n;
     c.pcd_pixels = 0;
     if (c.pcd_cap < n) {
       if (c.d_pcd_pts) { (void)hipFree(c.d_pcd_pts); c.d_pcd_pts = nullptr; c.pcd_cap = 0; }
       UG_CHECK(hipMalloc((void**)&c.d_pcd_pts, (size_t)n * 12));
       c.pcd_cap = n;
     }
-    launch_world_points(d.dp, dcam, n, H, W, plo, phi, (float)sd, (float)td, c.d_pcd_pts, c.stream);
+    launch_world_points(f.d.dp, f.dcam, n, H, W, f.b.plo, f.b.phi, (float)f.s, (float)f.t, c.d_pcd_pts, c.stream);
     UG_CHECK(hipGetLastError());
     UG_CHECK(hipStreamSynchronize(c.stream));
     c.pcd_pixels = n;
-    out_fit[0] = (float)sd; out_fit[1] = (float)td;
+    out_fit[0] = (float)f.s; out_fit[1] = (float)f.t;
     if (out_pts) UG_CHECK(hipMemcpy(out_pts, c.d_pcd_pts, (size_t)n * 12, hipMemcpyDeviceToHost));
   });
 }
@@ -845,7 +832,7 @@ int ug_eval_normal(ug_ctx* x, const float* pred, const float* gt, const unsigned
     unsigned char* dm = nullptr;
     if (mask) { dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(dm, mask, n, hipMemcpyHostToDevice)); }
     float* err = c.ws.get<float>(n);
-    double* part = c.ws.get<double>(1024 * 8);
+    double* part = c.ws.get<double>(EVAL_MAXB * 8);
     unsigned* hist = (unsigned*)c.ws.alloc(4097 * 4);
     UG_CHECK(hipMemsetAsync(hist, 0, 4097 * 4, c.stream));
     int nb = 0;

@@ -12,6 +12,7 @@
 #include "../../include/unigeo_hip.h"
 #include "../../include/unigeo_hip_test.h"
 #include "engine.h"
+#include "kernels/eval_reduce.h"   // EVAL_MAXB: the rows of every `part` buffer
 
 using namespace ug;
 
@@ -72,9 +73,14 @@ static inline void down_nchw(Ctx& c, const f16* d, float* h, int T, int C, int H
 static inline float clip_lo(float v) { return std::isnan(v) ? -INFINITY : v; }
 static inline float clip_hi(float v) { return std::isnan(v) ? INFINITY : v; }
 static inline float depth_bound(float v) { return (std::isnan(v) || v <= 0.f) ? NAN : v; }   // NaN: the kernels test gt > 0 only
-struct DepthEvalBufs { const float* dp; float* dg; unsigned char* dm; };
+// the option fields as the kernels take them: the depth bound of mask1, the clamps before and after the alignment
+struct DepthBounds { float md, lo, hi, plo, phi; };
+static inline DepthBounds depth_bounds(const ug_depth_eval_opts* o) {
+  return {depth_bound(o->max_depth), clip_lo(o->pre_clip_min), clip_hi(o->pre_clip_max), clip_lo(o->post_clip_min), clip_hi(o->post_clip_max)};
+}
+struct DepthEvalBufs { const float* dp; float* dg; unsigned char* dm; long n; };
 static inline DepthEvalBufs depth_eval_upload(Ctx& c, const float* pred, const float* gt, const unsigned char* cmask, long n) {
-  DepthEvalBufs b{nullptr, nullptr, nullptr};
+  DepthEvalBufs b{nullptr, nullptr, nullptr, n};
   if (pred) { float* d = c.ws.get<float>(n); UG_CHECK(hipMemcpy(d, pred, n * 4, hipMemcpyHostToDevice)); b.dp = d; }
   else { UG_REQUIRE(c.io_ready && n == (long)c.T * c.H * c.W, "no resident depth of that size"); b.dp = c.d_depth; }
   b.dg = c.ws.get<float>(n); UG_CHECK(hipMemcpy(b.dg, gt, n * 4, hipMemcpyHostToDevice));

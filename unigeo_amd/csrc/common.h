@@ -274,11 +274,19 @@ void launch_softmax_pair(const float* in, long ld_in, f16* out, int Spad, long r
 float bench_mfma_peak(float* scratch, int iters, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
-// Evaluation metrics on device (kernels/metrics.hip)
+// Evaluation metrics on device (kernels/metrics.hip).  Every `part` array below holds EVAL_MAXB rows of block partials (kernels/eval_reduce.h,
+// which the host units include for the constant); *nb returns how many rows the launch filled.
 // ---------------------------------------------------------------------------------------
-void launch_depth_fit(const float* pred, const float* gt, long n, float max_depth, double* part, int* nb, hipStream_t s);
-void launch_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float sc,
-                          float sh, double* part, int* nb, hipStream_t s);
+// Depth: one fit and one metric launch for every entry point.  mask1 = gt > 0 && !(gt >= max_depth) (NaN: no upper bound); lo / hi clamp the
+// prediction before the alignment, plo / phi after it, -inf / +inf where a mode has none.  A NaN prediction on mask1 is outside the contract:
+// the clamp turns it into -inf.
+void launch_depth_fit(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part /*[EVAL_MAXB * 5]*/, int* nb,
+                      hipStream_t s);
+// unfused: s * p + t in two roundings (the L1 alignment).  disparity: the aligned value is a disparity, inverted before the metrics (floor_ = NaN: no
+// floor; always unfused).  emap: optional per-pixel relative error of the ORIGINAL prediction.
+void launch_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi, float plo,
+                          float phi, float floor_, float sc, float sh, double* part /*[EVAL_MAXB * 9]*/, float* emap, int* nb, hipStream_t s,
+                          bool unfused, bool disparity);
 void launch_normal_err(const float* pn, const float* gn, const unsigned char* mask, long n, float* err, double* part,
                        unsigned* hist, int* nb, hipStream_t s);
 void launch_collect_bin(const float* err, long n, int bin, float* out, unsigned* count, unsigned cap, hipStream_t s);
@@ -291,14 +299,9 @@ void launch_collect_bin(const float* err, long n, int bin, float* out, unsigned*
 void launch_masked_median(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* sel, hipStream_t s);
 void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, int iters, double* wz,
                             double* part, hipStream_t s);
-void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s);
-void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
-                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s, bool unfused = false);
 // alignment in disparity space (kernels/metrics.hip): gfit = mask1 ? 1 / (gt + 1e-8f) : 0, the target the fit kernels above take
-// with the depth bound off; then the metrics of the inverted aligned disparity against the real gt (floor_ = NaN: no floor)
+// with the depth bound off; launch_depth_metrics then inverts the aligned disparity against the real gt
 void launch_disp_target(const float* gt, long n, float max_depth, float* gfit, hipStream_t s);
-void launch_disp_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi, float plo,
-                         float phi, float floor_, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s);
 // exact L1 scale-and-shift alignment (kernels/metrics.hip): state words (unsigned 64-bit) and caps
 #define L1_BITS 36            // q = rint(p * 2^(L1_BITS - E))
 #define L1_MAX_STEPS 64
@@ -312,7 +315,7 @@ void launch_disp_metrics(const float* pred, const float* gt, const unsigned char
 #define L1_TIE_CNT 2052
 #define L1_CHK 2053           // L1_CHK_SLOTS x (below, above, total)
 #define L1_WORDS 2080
-#define L1_AUX_WORDS (1024 + 2)   // unsigned words: the bits of max |p|, j0, one count per block
+#define L1_AUX_WORDS (EVAL_MAXB + 2)   // unsigned words: the bits of max |p|, j0, one count per block
 void launch_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, hipStream_t s);
 void launch_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, double up, float med,
                        unsigned cap, long long* qc, float* gc, hipStream_t s);
@@ -328,7 +331,7 @@ void launch_radius_metrics(const float* radius, const float* gt, const float* gt
                            float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s);
 // point-cloud evaluation (kernels/pcd.hip).  Clouds are [n,3]; idx / dist are per query.  All launches are stream-ordered and
 // deterministic: fixed-order fp64 reductions, integer atomics only in the selection histograms.
-#define PCD_MAXB 1024         // most blocks of a compaction / reduction launch: `counts` / `part` arrays are sized by it
+#define PCD_MAXB EVAL_MAXB    // most blocks of a compaction / reduction launch: `counts` / `part` arrays are sized by it
 #define PCD_SEL_WORDS 264     // select state (unsigned words): 256 histogram words, then prefix (2 words), rank (2 words), padding
 // order-preserving 64-bit key of a float32 (in the upper word) / float64: negative values have all bits flipped, the others only the sign bit
 __host__ __device__ inline unsigned long long pcd_key(double f) {
@@ -401,7 +404,7 @@ void launch_pcd_gather64(const double* src, const int* list, long nl, double* ou
 void launch_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist, hipStream_t s);
 // focal, poses and depth from world point maps (kernels/pointmap.hip): the arithmetic of harness/pointmap.py.  A frame is
 // n = H * W pixels of pts [n,3]; every sum is per-block fp64 partials (part: PM_MAXB rows) that the caller adds in block order.
-#define PM_MAXB 1024
+#define PM_MAXB EVAL_MAXB
 struct PmCam { double f, cx, cy; int W; };           // K = [[f, 0, cx], [0, f, cy], [0, 0, 1]], pixel i = (row i / W, column i % W)
 struct PmPose { double R[9], t[3]; };                // world to camera, R row-major
 // the Weiszfeld chain on the device: fz[0] = the focal after the closed-form start and `steps` reweighting steps; part [PM_MAXB * 2]

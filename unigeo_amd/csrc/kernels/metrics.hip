@@ -4,26 +4,13 @@
 //           custom mask)
 //   normal: /root/reference/metrics/eval_normal.py:4-34 (angular error in degrees; mean / median / rmse / % under
 //           5, 7.5, 11.25, 22.5, 30 degrees)
-// All reductions are two-stage with a fixed order (per-block fp64 partials, summed by the host in block order), the
+// All reductions are two-stage with a fixed order (eval_reduce.h: per-block fp64 partials, summed by the host in block order), the
 // median is an exact two-pass histogram selection with integer atomics: results are deterministic.
+// Depth has ONE least-squares fit kernel (k_depth_fit) and ONE metric kernel template (k_depth_metrics<UNFUSED, DISPARITY>): every entry point
+// and every alignment mode goes through them, with clip bounds of -inf / +inf where a mode has none.
 #include "../common.h"
+#include "eval_reduce.h"
 #include <utility>
-
-#define MB 256   // threads per block
-#define MAXB 1024
-
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = MB / 2; o > 0; o >>= 1) {
-    if (tid < o) sh[tid] += sh[tid + o];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
 
 // one selected pixel's terms of the nine metric sums: n, absrel, sqrel, sq, logsq, d1, d125, d125^2, d125^3 (prediction p, target g > 0)
 __device__ __forceinline__ void metric_terms(float p, float g, double* a) {
@@ -36,48 +23,13 @@ __device__ __forceinline__ void metric_terms(float p, float g, double* a) {
   a[5] += r < 1.0f; a[6] += r < 1.25f; a[7] += r < 1.5625f; a[8] += r < 1.953125f;
 }
 
-// pass 1: normal-equation sums over mask1 = (0 < gt < max_depth): n, sum p, sum p^2, sum g, sum p*g
-__global__ __launch_bounds__(MB) void k_depth_fit(const float* pred, const float* gt, long n, float max_depth, double* part) {
-  __shared__ double sh[MB];
-  double a[5] = {0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
-    const float g = gt[i];
-    if (g > 0.f && g < max_depth) {
-      const double p = pred[i];
-      a[0] += 1.0; a[1] += p; a[2] += p * p; a[3] += g; a[4] += p * (double)g;
-    }
-  }
-  for (int k = 0; k < 5; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + k] = r;
-  }
-}
-
-// pass 2: metrics of p' = s*p + t on mask1 & custom mask
-__global__ __launch_bounds__(MB) void k_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n,
-                                                      float max_depth, float s, float t, double* part) {
-  __shared__ double sh[MB];
-  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
-    const float g = gt[i];
-    if (g > 0.f && g < max_depth && (!cmask || cmask[i])) {
-      const float p = s * pred[i] + t;
-      metric_terms(p, g, a);
-    }
-  }
-  for (int k = 0; k < 9; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
-  }
-}
-
 // angular error per pixel (degrees), -1 for masked pixels; partial sums n, sum e, sum e^2, counts under 5 thresholds;
 // coarse histogram (4096 bins over [0,180]) for the median
-__global__ __launch_bounds__(MB) void k_normal_err(const float* pn, const float* gn, const unsigned char* mask, long n, float* err,
+__global__ __launch_bounds__(EVAL_NT) void k_normal_err(const float* pn, const float* gn, const unsigned char* mask, long n, float* err,
                                                    double* part, unsigned* hist) {
-  __shared__ double sh[MB];
+  __shared__ double sh[EVAL_NT];
   double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     float e = -1.f;
     if (!mask || mask[i]) {
       const float px = pn[i * 3], py = pn[i * 3 + 1], pz = pn[i * 3 + 2];
@@ -94,10 +46,7 @@ __global__ __launch_bounds__(MB) void k_normal_err(const float* pn, const float*
     }
     err[i] = e;
   }
-  for (int k = 0; k < 8; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 8 + k] = r;
-  }
+  eval_store_sums<8>(a, sh, part);
 }
 
 // collect the errors that fall into one histogram bin (the bin holding the median)
@@ -128,7 +77,7 @@ __device__ __forceinline__ float key_f32(unsigned k) { return __uint_as_float(k 
 // (offsets in common.h.)  Counts are integers: the result does not depend on the order in which workgroups arrive.
 
 template <int PASS>
-__global__ __launch_bounds__(MB) void k_select_hist(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
+__global__ __launch_bounds__(EVAL_NT) void k_select_hist(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
                                                     unsigned* sel) {
   __shared__ unsigned h[2][256];
   const int tid = threadIdx.x;
@@ -136,7 +85,7 @@ __global__ __launch_bounds__(MB) void k_select_hist(const float* pred, const flo
   __syncthreads();
   constexpr int shift = 24 - 8 * PASS;
   const unsigned pp = sel[SEL_PREFIX], pg = sel[SEL_PREFIX + 1];
-  for (long i = (long)blockIdx.x * MB + tid; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + tid; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float g = gt[i];
     if (!depth_valid(g, max_depth)) continue;
     const unsigned kp = f32_key(clipf(pred[i], lo, hi)), kg = f32_key(g);
@@ -187,29 +136,26 @@ __global__ __launch_bounds__(256) void k_select_scan(unsigned* sel) {
 // Weiszfeld chain for the L1 scale: wz[0] = s, wz[1] = mask1 count.  INIT: partials of n, sum p, sum g -> s0 = mean(g) / mean(p);
 // otherwise w = 1 / (|s p - g| + 1e-8), partials of sum(w p g), sum(w p p) -> s.  fp64 throughout, fixed grid, fixed order.
 template <bool INIT>
-__global__ __launch_bounds__(MB) void k_wz_pass(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
+__global__ __launch_bounds__(EVAL_NT) void k_wz_pass(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
                                                 const double* wz, double* part) {
-  __shared__ double sh[MB];
+  __shared__ double sh[EVAL_NT];
   const double s = INIT ? 0.0 : wz[0];
   double a[3] = {0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float gf = gt[i];
     if (!depth_valid(gf, max_depth)) continue;
     const double p = clipf(pred[i], lo, hi), g = gf;
     if (INIT) { a[0] += 1.0; a[1] += p; a[2] += g; }
     else { const double w = 1.0 / (fabs(s * p - g) + 1e-8); a[0] += w * p * g; a[1] += w * p * p; }
   }
-  for (int k = 0; k < 3; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 3 + k] = r;
-  }
+  eval_store_sums<3>(a, sh, part);
 }
 
 // one workgroup: the partials summed in block order by one thread, the next s written for the next pass
 template <bool INIT>
-__global__ __launch_bounds__(MB) void k_wz_reduce(const double* part, int nb, double* wz) {
-  __shared__ double sh[MAXB * 3];
-  for (int i = threadIdx.x; i < nb * 3; i += MB) sh[i] = part[i];
+__global__ __launch_bounds__(EVAL_NT) void k_wz_reduce(const double* part, int nb, double* wz) {
+  __shared__ double sh[EVAL_MAXB * 3];
+  for (int i = threadIdx.x; i < nb * 3; i += EVAL_NT) sh[i] = part[i];
   __syncthreads();
   if (threadIdx.x == 0) {
     double a[3] = {0, 0, 0};
@@ -219,56 +165,18 @@ __global__ __launch_bounds__(MB) void k_wz_reduce(const double* part, int nb, do
   }
 }
 
-// k_depth_fit on the pre-clipped prediction
-__global__ __launch_bounds__(MB) void k_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi,
-                                                     double* part) {
-  __shared__ double sh[MB];
+// normal-equation sums of the least-squares fit over mask1, on the pre-clipped prediction: n, sum p, sum p^2, sum g, sum p*g
+__global__ __launch_bounds__(EVAL_NT) void k_depth_fit(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part) {
+  __shared__ double sh[EVAL_NT];
   double a[5] = {0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float g = gt[i];
     if (depth_valid(g, max_depth)) {
       const double p = clipf(pred[i], lo, hi);
       a[0] += 1.0; a[1] += p; a[2] += p * p; a[3] += g; a[4] += p * (double)g;
     }
   }
-  for (int k = 0; k < 5; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + k] = r;
-  }
-}
-
-// k_depth_metrics of p' = clamp(s * clamp(p, lo, hi) + t, plo, phi); optional error map |s * pred + t - gt| / gt on mask1 (0 elsewhere) from
-// the ORIGINAL prediction.  The reference's tensor expressions round the product and the sum separately; a fused multiply-add moves the map
-// by more than its tolerance where the residual is small.
-// UNFUSED: in this toolchain __fmul_rn / __fadd_rn are plain operators, and the default instantiation's s * p + t does come out as one fused
-// operation (see world_point below).  With t = 0 (median, scale, metric) that changes no bit, and least squares is compared within a tolerance; the
-// L1 alignment's line passes through two of the pixels, where the residual is a rounding error and the fused form differs from the host's in every
-// digit.  It instantiates the kernel with contraction off; the other modes keep the code, and the bytes, they had.
-__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
-#pragma clang fp contract(off)
-  const float m = a * b;
-  return m + c;
-}
-template <bool UNFUSED>
-__global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n,
-                                                         float max_depth, float lo, float hi, float plo, float phi, float s, float t,
-                                                         double* part, float* emap) {
-  __shared__ double sh[MB];
-  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
-    const float g = gt[i];
-    const bool v1 = depth_valid(g, max_depth);
-    const float p0 = pred[i];
-    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(UNFUSED ? mul_add_unfused(p0, s, t) : __fadd_rn(__fmul_rn(p0, s), t), g)) / g : 0.f;
-    if (v1 && (!cmask || cmask[i])) {
-      const float p = clipf(UNFUSED ? mul_add_unfused(s, clipf(p0, lo, hi), t) : __fadd_rn(__fmul_rn(s, clipf(p0, lo, hi)), t), plo, phi);
-      metric_terms(p, g, a);
-    }
-  }
-  for (int k = 0; k < 9; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
-  }
+  eval_store_sums<5>(a, sh, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -277,8 +185,8 @@ __global__ __launch_bounds__(MB) void k_depth_metrics_ex(const float* pred, cons
 // against gd = 1 / (gt + 1e-8f) on mask1, the aligned disparity is inverted, and the metrics are taken against the real gt.
 // Target pass: gfit = mask1 ? gd : 0.  gd > 0 on mask1, so the fit kernels above, launched with gfit in the place of gt and the depth bound off, see
 // mask1 through their own test g > 0.
-__global__ __launch_bounds__(MB) void k_disp_target(const float* gt, long n, float max_depth, float* gfit) {
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+__global__ __launch_bounds__(EVAL_NT) void k_disp_target(const float* gt, long n, float max_depth, float* gfit) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float g = gt[i];
     gfit[i] = depth_valid(g, max_depth) ? 1.0f / (g + 1e-8f) : 0.f;
   }
@@ -289,33 +197,50 @@ __device__ __forceinline__ float disp_to_depth(float a, float floor_) {
   if (a < floor_) a = floor_;
   return a > 0.f ? 1.0f / a : 0.f;
 }
-// The counterpart of k_depth_metrics_ex: p' = clamp(disp_to_depth(s * clamp(p, lo, hi) + t), plo, phi) against the real gt on mask1 & custom mask;
-// optional error map |disp_to_depth(pred * s + t) - gt| / gt on mask1 (0 elsewhere) from the ORIGINAL prediction.  s * p + t is unfused in every
-// mode: the inversion carries a rounding of the aligned disparity into the depth, and the depth is compared with the host's byte for byte.
-__global__ __launch_bounds__(MB) void k_disp_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth,
-                                                     float lo, float hi, float plo, float phi, float floor_, float s, float t, double* part,
-                                                     float* emap) {
-  __shared__ double sh[MB];
+
+// The nine metric sums of p' = clamp(A(s, clamp(p, lo, hi)), plo, phi) on mask1 & custom mask; optional error map |A(pred, s) - gt| / gt on mask1
+// (0 elsewhere) from the ORIGINAL prediction.  A(a, b) is the aligned value a * b + t, in disparity space inverted by disp_to_depth (floor_ = NaN:
+// no floor) before it meets the real gt.  The reference's tensor expressions round the product and the sum separately; a fused multiply-add
+// moves the map by more than its tolerance where the residual is small.
+// UNFUSED: in this toolchain __fmul_rn / __fadd_rn are plain operators, and the default instantiation's s * p + t does come out as one fused
+// operation (see world_point below).  With t = 0 (median, scale, metric) that changes no bit, and least squares is compared within a tolerance; the
+// L1 alignment's line passes through two of the pixels, where the residual is a rounding error and the fused form differs from the host's in every
+// digit.  It instantiates the kernel with contraction off; the other modes keep the code, and the bytes, they had.
+// DISPARITY implies UNFUSED in every mode: the inversion carries a rounding of the aligned disparity into the depth, and the depth is compared
+// with the host's byte for byte.
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float m = a * b;
+  return m + c;
+}
+template <bool UNFUSED, bool DISPARITY>
+__device__ __forceinline__ float aligned_depth(float a, float b, float t, float floor_) {
+  const float v = UNFUSED ? mul_add_unfused(a, b, t) : __fadd_rn(__fmul_rn(a, b), t);
+  return DISPARITY ? disp_to_depth(v, floor_) : v;
+}
+template <bool UNFUSED, bool DISPARITY>
+__global__ __launch_bounds__(EVAL_NT) void k_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth,
+                                                           float lo, float hi, float plo, float phi, float floor_, float s, float t, double* part,
+                                                           float* emap) {
+  static_assert(UNFUSED || !DISPARITY, "the disparity form is unfused");
+  __shared__ double sh[EVAL_NT];
   double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float g = gt[i];
     const bool v1 = depth_valid(g, max_depth);
     const float p0 = pred[i];
-    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(disp_to_depth(mul_add_unfused(p0, s, t), floor_), g)) / g : 0.f;
+    if (emap) emap[i] = v1 ? fabsf(__fsub_rn(aligned_depth<UNFUSED, DISPARITY>(p0, s, t, floor_), g)) / g : 0.f;
     if (v1 && (!cmask || cmask[i])) {
-      const float p = clipf(disp_to_depth(mul_add_unfused(s, clipf(p0, lo, hi), t), floor_), plo, phi);
+      const float p = clipf(aligned_depth<UNFUSED, DISPARITY>(s, clipf(p0, lo, hi), t, floor_), plo, phi);
       metric_terms(p, g, a);
     }
   }
-  for (int k = 0; k < 9; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
-  }
+  eval_store_sums<9>(a, sh, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Depth evaluation in global coordinates (restated from /root/reference/metrics/eval_depth.py:250-441 and
-// utils/geometry_utils.py:246-253).  After the first fit (k_depth_fit_ex) gave (s, t): the aligned, post-clipped depth
+// utils/geometry_utils.py:246-253).  After the first fit (k_depth_fit) gave (s, t): the aligned, post-clipped depth
 // d = clamp(s * pred + t, plo, phi) of EVERY pixel from the ORIGINAL prediction, float32 with the product and the sum rounded separately;
 // then in fp64 from that float32 d: x = (col - cx) * d / fx, y = (row - cy) * d / fy, z = d (integer pixel indices), world = R (x, y, z) + t
 // with the frame's pose, r = |world| rounded once to float32 and written out.  The same pass accumulates the normal-equation sums of the
@@ -341,13 +266,13 @@ __device__ __forceinline__ void world_point(const float* pred, const double* cam
   wz = ((q[10] * x + q[11] * y) + q[12] * z) + q[15];
 }
 
-__global__ __launch_bounds__(MB) void k_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n,
+__global__ __launch_bounds__(EVAL_NT) void k_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n,
                                                      int H, int W, float max_depth, float plo, float phi, float s, float t, float* radius,
                                                      double* part) {
-  __shared__ double sh[MB];
+  __shared__ double sh[EVAL_NT];
   double a[5] = {0, 0, 0, 0, 0};
   const long hw = (long)H * W;
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     double wx, wy, wz;
     world_point(pred, cam, i, hw, W, plo, phi, s, t, wx, wy, wz);
     const float rf = (float)sqrt(__dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz)));
@@ -357,17 +282,14 @@ __global__ __launch_bounds__(MB) void k_world_radius(const float* pred, const fl
       a[0] += 1.0; a[1] += r; a[2] += r * r; a[3] += g; a[4] += r * g;
     }
   }
-  for (int k = 0; k < 5; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 5 + k] = r;
-  }
+  eval_store_sums<5>(a, sh, part);
 }
 
 // the world points themselves, each coordinate rounded once to float32 (ug_pcd_world_points)
-__global__ __launch_bounds__(MB) void k_world_points(const float* pred, const double* cam, long n, int H, int W, float plo, float phi, float s,
+__global__ __launch_bounds__(EVAL_NT) void k_world_points(const float* pred, const double* cam, long n, int H, int W, float plo, float phi, float s,
                                                      float t, float* pts) {
   const long hw = (long)H * W;
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     double wx, wy, wz;
     world_point(pred, cam, i, hw, W, plo, phi, s, t, wx, wy, wz);
     pts[i * 3] = (float)wx; pts[i * 3 + 1] = (float)wy; pts[i * 3 + 2] = (float)wz;
@@ -376,45 +298,31 @@ __global__ __launch_bounds__(MB) void k_world_points(const float* pred, const do
 
 // the nine metric sums of p' = s * r + t (two roundings, no clamp) against the ground-truth radius on mask1 of the ground-truth DEPTH & custom
 // mask; p' of every pixel goes to rmap when one is asked for
-__global__ __launch_bounds__(MB) void k_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask,
+__global__ __launch_bounds__(EVAL_NT) void k_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask,
                                                        long n, float max_depth, float s, float t, double* part, float* rmap) {
-  __shared__ double sh[MB];
+  __shared__ double sh[EVAL_NT];
   double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < n; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float p = __fadd_rn(__fmul_rn(s, radius[i]), t);
     if (rmap) rmap[i] = p;
     if (depth_valid(gt[i], max_depth) && (!cmask || cmask[i])) metric_terms(p, gt_radius[i], a);
   }
-  for (int k = 0; k < 9; ++k) {
-    const double r = block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 9 + k] = r;
-  }
+  eval_store_sums<9>(a, sh, part);
 }
 
-static int nblocks(long n) { long b = (n + MB - 1) / MB; return (int)(b > MAXB ? MAXB : (b < 1 ? 1 : b)); }
-
-void launch_depth_fit(const float* pred, const float* gt, long n, float max_depth, double* part, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_depth_fit, dim3(*nb), dim3(MB), 0, s, pred, gt, n, max_depth, part);
-}
-void launch_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float sc,
-                          float sh, double* part, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_depth_metrics, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, sc, sh, part);
-}
 void launch_normal_err(const float* pn, const float* gn, const unsigned char* mask, long n, float* err, double* part,
                        unsigned* hist, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_normal_err, dim3(*nb), dim3(MB), 0, s, pn, gn, mask, n, err, part, hist);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_normal_err, dim3(*nb), dim3(EVAL_NT), 0, s, pn, gn, mask, n, err, part, hist);
 }
 void launch_collect_bin(const float* err, long n, int bin, float* out, unsigned* count, unsigned cap, hipStream_t s) {
-  hipLaunchKernelGGL(k_collect_bin, dim3(nblocks(n)), dim3(MB), 0, s, err, n, bin, out, count, cap);
+  hipLaunchKernelGGL(k_collect_bin, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, err, n, bin, out, count, cap);
 }
 
 // the four histogram / scan pairs back to back on one stream: sel (SEL_WORDS unsigned words) ends with the count and the two medians
 void launch_masked_median(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* sel, hipStream_t s) {
   (void)hipMemsetAsync(sel, 0, SEL_WORDS * sizeof(unsigned), s);
-  const dim3 g(nblocks(n)), b(MB);
+  const dim3 g(eval_nblocks(n)), b(EVAL_NT);
   hipLaunchKernelGGL(k_select_hist<0>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
   hipLaunchKernelGGL(k_select_scan<0>, dim3(1), dim3(256), 0, s, sel);
   hipLaunchKernelGGL(k_select_hist<1>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
@@ -424,48 +332,44 @@ void launch_masked_median(const float* pred, const float* gt, long n, float max_
   hipLaunchKernelGGL(k_select_hist<3>, g, b, 0, s, pred, gt, n, max_depth, lo, hi, sel);
   hipLaunchKernelGGL(k_select_scan<3>, dim3(1), dim3(256), 0, s, sel);
 }
-// initial means + iters Weiszfeld steps, no host synchronisation in between: wz[0] = s, wz[1] = mask1 count; part holds MAXB * 3 doubles
+// initial means + iters Weiszfeld steps, no host synchronisation in between: wz[0] = s, wz[1] = mask1 count; part holds EVAL_MAXB * 3 doubles
 void launch_weiszfeld_scale(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, int iters, double* wz,
                             double* part, hipStream_t s) {
-  const int nb = nblocks(n);
-  hipLaunchKernelGGL(k_wz_pass<true>, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, wz, part);
-  hipLaunchKernelGGL(k_wz_reduce<true>, dim3(1), dim3(MB), 0, s, part, nb, wz);
+  const int nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_wz_pass<true>, dim3(nb), dim3(EVAL_NT), 0, s, pred, gt, n, max_depth, lo, hi, wz, part);
+  hipLaunchKernelGGL(k_wz_reduce<true>, dim3(1), dim3(EVAL_NT), 0, s, part, nb, wz);
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(k_wz_pass<false>, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, wz, part);
-    hipLaunchKernelGGL(k_wz_reduce<false>, dim3(1), dim3(MB), 0, s, part, nb, wz);
+    hipLaunchKernelGGL(k_wz_pass<false>, dim3(nb), dim3(EVAL_NT), 0, s, pred, gt, n, max_depth, lo, hi, wz, part);
+    hipLaunchKernelGGL(k_wz_reduce<false>, dim3(1), dim3(EVAL_NT), 0, s, part, nb, wz);
   }
 }
-void launch_depth_fit_ex(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_depth_fit_ex, dim3(*nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, part);
+void launch_depth_fit(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, double* part, int* nb, hipStream_t s) {
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_depth_fit, dim3(*nb), dim3(EVAL_NT), 0, s, pred, gt, n, max_depth, lo, hi, part);
 }
-void launch_depth_metrics_ex(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi,
-                             float plo, float phi, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s, bool unfused) {
-  *nb = nblocks(n);
-  if (unfused) hipLaunchKernelGGL(k_depth_metrics_ex<true>, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
-  else hipLaunchKernelGGL(k_depth_metrics_ex<false>, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, sc, sh, part, emap);
+void launch_depth_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi, float plo,
+                          float phi, float floor_, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s, bool unfused,
+                          bool disparity) {
+  *nb = eval_nblocks(n);
+  const auto k = disparity ? k_depth_metrics<true, true> : (unfused ? k_depth_metrics<true, false> : k_depth_metrics<false, false>);
+  hipLaunchKernelGGL(k, dim3(*nb), dim3(EVAL_NT), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, floor_, sc, sh, part, emap);
 }
 void launch_disp_target(const float* gt, long n, float max_depth, float* gfit, hipStream_t s) {
-  hipLaunchKernelGGL(k_disp_target, dim3(nblocks(n)), dim3(MB), 0, s, gt, n, max_depth, gfit);
-}
-void launch_disp_metrics(const float* pred, const float* gt, const unsigned char* cmask, long n, float max_depth, float lo, float hi, float plo,
-                         float phi, float floor_, float sc, float sh, double* part, float* emap, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_disp_metrics, dim3(*nb), dim3(MB), 0, s, pred, gt, cmask, n, max_depth, lo, hi, plo, phi, floor_, sc, sh, part, emap);
+  hipLaunchKernelGGL(k_disp_target, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, gt, n, max_depth, gfit);
 }
 void launch_world_radius(const float* pred, const float* gt, const float* gt_radius, const double* cam, long n, int H, int W, float max_depth,
                          float plo, float phi, float sc, float sh, float* radius, double* part, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_world_radius, dim3(*nb), dim3(MB), 0, s, pred, gt, gt_radius, cam, n, H, W, max_depth, plo, phi, sc, sh, radius, part);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_world_radius, dim3(*nb), dim3(EVAL_NT), 0, s, pred, gt, gt_radius, cam, n, H, W, max_depth, plo, phi, sc, sh, radius, part);
 }
 void launch_world_points(const float* pred, const double* cam, long n, int H, int W, float plo, float phi, float sc, float sh, float* pts,
                          hipStream_t s) {
-  hipLaunchKernelGGL(k_world_points, dim3(nblocks(n)), dim3(MB), 0, s, pred, cam, n, H, W, plo, phi, sc, sh, pts);
+  hipLaunchKernelGGL(k_world_points, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, pred, cam, n, H, W, plo, phi, sc, sh, pts);
 }
 void launch_radius_metrics(const float* radius, const float* gt, const float* gt_radius, const unsigned char* cmask, long n, float max_depth,
                            float sc, float sh, double* part, float* rmap, int* nb, hipStream_t s) {
-  *nb = nblocks(n);
-  hipLaunchKernelGGL(k_radius_metrics, dim3(*nb), dim3(MB), 0, s, radius, gt, gt_radius, cmask, n, max_depth, sc, sh, part, rmap);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_radius_metrics, dim3(*nb), dim3(EVAL_NT), 0, s, radius, gt, gt_radius, cmask, n, max_depth, sc, sh, part, rmap);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -481,7 +385,7 @@ void launch_radius_metrics(const float* radius, const float* gt, const float* gt
 typedef unsigned long long u64;
 
 // the valid pixels are compacted in pixel order: block b owns the pixels [b * chunk, (b + 1) * chunk), chunk a multiple of the block size
-static long l1_chunk(long n, int nb) { const long c = (n + nb - 1) / nb; return (c + MB - 1) / MB * MB; }
+static long l1_chunk(long n, int nb) { const long c = (n + nb - 1) / nb; return (c + EVAL_NT - 1) / EVAL_NT * EVAL_NT; }
 
 __device__ __forceinline__ double l1_slope(long long dq, float gi, double gj, double down) {
 #pragma clang fp contract(off)
@@ -490,20 +394,20 @@ __device__ __forceinline__ double l1_slope(long long dq, float gi, double gj, do
 }
 
 // the bits of max |clamp(pred)| over mask1 (integer atomicMax: non-negative floats order as their bits do) and every block's count of valid pixels
-__global__ __launch_bounds__(MB) void k_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, long chunk,
+__global__ __launch_bounds__(EVAL_NT) void k_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, long chunk,
                                                   unsigned* maxbits, unsigned* bcount) {
-  __shared__ unsigned sm[MB], sc[MB];
+  __shared__ unsigned sm[EVAL_NT], sc[EVAL_NT];
   const int tid = threadIdx.x;
   const long beg = (long)blockIdx.x * chunk, end = beg + chunk < n ? beg + chunk : n;
   unsigned mx = 0, cnt = 0;
-  for (long i = beg + tid; i < end; i += MB) {
+  for (long i = beg + tid; i < end; i += EVAL_NT) {
     if (!depth_valid(gt[i], max_depth)) continue;
     const unsigned b = __float_as_uint(fabsf(clipf(pred[i], lo, hi)));
     mx = b > mx ? b : mx; ++cnt;
   }
   sm[tid] = mx; sc[tid] = cnt;
   __syncthreads();
-  for (int o = MB / 2; o > 0; o >>= 1) {
+  for (int o = EVAL_NT / 2; o > 0; o >>= 1) {
     if (tid < o) { sm[tid] = sm[tid + o] > sm[tid] ? sm[tid + o] : sm[tid]; sc[tid] += sc[tid + o]; }
     __syncthreads();
   }
@@ -514,36 +418,36 @@ __global__ __launch_bounds__(MB) void k_l1_maxabs(const float* pred, const float
 // it and scans each of its 256-pixel tiles.  *j0 = the lowest compacted index whose clamped prediction equals med.  cap = the compacted length.
 // launch_pcd_compact (kernels/pcd.hip) keeps the same order but copies float32 pairs on the custom mask; this one selects on mask1, clamps and
 // quantises as it writes and finds j0 in the same trip, and the block counts come from k_l1_maxabs, which reads the pixels anyway.
-__global__ __launch_bounds__(MB) void k_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, long chunk,
+__global__ __launch_bounds__(EVAL_NT) void k_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, long chunk,
                                                    const unsigned* bcount, double up, float med, unsigned cap, long long* qc, float* gc,
                                                    unsigned* j0) {
-  __shared__ unsigned sc[MB];
+  __shared__ unsigned sc[EVAL_NT];
   const int tid = threadIdx.x;
   unsigned part = 0;
-  for (int b = tid; b < (int)blockIdx.x; b += MB) part += bcount[b];
+  for (int b = tid; b < (int)blockIdx.x; b += EVAL_NT) part += bcount[b];
   sc[tid] = part;
   __syncthreads();
-  for (int o = MB / 2; o > 0; o >>= 1) {
+  for (int o = EVAL_NT / 2; o > 0; o >>= 1) {
     if (tid < o) sc[tid] += sc[tid + o];
     __syncthreads();
   }
   unsigned running = sc[0];
   __syncthreads();
   const long beg = (long)blockIdx.x * chunk, end = beg + chunk < n ? beg + chunk : n;
-  for (long t0 = beg; t0 < end; t0 += MB) {
+  for (long t0 = beg; t0 < end; t0 += EVAL_NT) {
     const long i = t0 + tid;
     const float g = i < end ? gt[i] : 0.f;
     const bool v = i < end && depth_valid(g, max_depth);
     sc[tid] = v;
     __syncthreads();
-    for (int o = 1; o < MB; o <<= 1) {
+    for (int o = 1; o < EVAL_NT; o <<= 1) {
       const unsigned a = tid >= o ? sc[tid - o] : 0u;
       __syncthreads();
       sc[tid] += a;
       __syncthreads();
     }
     const unsigned pos = running + sc[tid] - 1u;
-    running += sc[MB - 1];
+    running += sc[EVAL_NT - 1];
     if (v && pos < cap) {
       const float p = clipf(pred[i], lo, hi);
       qc[pos] = __double2ll_rn((double)p * up);
@@ -559,7 +463,7 @@ __global__ __launch_bounds__(MB) void k_l1_compact(const float* pred, const floa
 // in the first passes (sign and exponent bits) nearly every slope shares a bin, and one atomic per point would serialise on that address.
 // The sums are integers, so the grouping changes no bit.
 template <int PASS>
-__global__ __launch_bounds__(MB) void k_l1_hist(const long long* qc, const float* gc, long nv, long j, double down, u64* st) {
+__global__ __launch_bounds__(EVAL_NT) void k_l1_hist(const long long* qc, const float* gc, long nv, long j, double down, u64* st) {
   __shared__ u64 h[256];
   const int tid = threadIdx.x;
   h[tid] = 0;
@@ -570,7 +474,7 @@ __global__ __launch_bounds__(MB) void k_l1_hist(const long long* qc, const float
   const u64 prefix = st[L1_PREFIX];
   unsigned bin = 0;
   u64 run = 0;
-  for (long i = (long)blockIdx.x * MB + tid; i < nv; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + tid; i < nv; i += (long)gridDim.x * EVAL_NT) {
     const long long dq = qc[i] - qj;
     if (dq == 0) continue;
     const u64 key = pcd_key(l1_slope(dq, gc[i], gj, down));
@@ -614,12 +518,12 @@ __global__ __launch_bounds__(256) void k_l1_scan(u64* st) {
 }
 
 // the points whose slope through j has the selected key: the lowest index, how many, and the first L1_MAX_TIES of them (index and q, any order)
-__global__ __launch_bounds__(MB) void k_l1_tie(const long long* qc, const float* gc, long nv, long j, double down, u64* st, unsigned* tie_idx,
+__global__ __launch_bounds__(EVAL_NT) void k_l1_tie(const long long* qc, const float* gc, long nv, long j, double down, u64* st, unsigned* tie_idx,
                                                long long* tie_q) {
   const long long qj = qc[j];
   const double gj = gc[j];
   const u64 want = st[L1_PREFIX];
-  for (long i = (long)blockIdx.x * MB + threadIdx.x; i < nv; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < nv; i += (long)gridDim.x * EVAL_NT) {
     const long long qi = qc[i], dq = qi - qj;
     if (dq == 0 || pcd_key(l1_slope(dq, gc[i], gj, down)) != want) continue;
     atomicMin(&st[L1_TIE_MIN], (u64)i);
@@ -629,13 +533,13 @@ __global__ __launch_bounds__(MB) void k_l1_tie(const long long* qc, const float*
 }
 
 // with pivot z: the weight of the slopes below S, above S, and the total weight -> out3 (one 64-bit integer atomicAdd per block and sum)
-__global__ __launch_bounds__(MB) void k_l1_check(const long long* qc, const float* gc, long nv, long z, double S, double down, u64* out3) {
-  __shared__ u64 sh[3][MB];
+__global__ __launch_bounds__(EVAL_NT) void k_l1_check(const long long* qc, const float* gc, long nv, long z, double S, double down, u64* out3) {
+  __shared__ u64 sh[3][EVAL_NT];
   const int tid = threadIdx.x;
   const long long qz = qc[z];
   const double gz = gc[z];
   u64 a[3] = {0, 0, 0};
-  for (long i = (long)blockIdx.x * MB + tid; i < nv; i += (long)gridDim.x * MB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + tid; i < nv; i += (long)gridDim.x * EVAL_NT) {
     const long long dq = qc[i] - qz;
     if (dq == 0) continue;
     const double r = l1_slope(dq, gc[i], gz, down);
@@ -646,30 +550,30 @@ __global__ __launch_bounds__(MB) void k_l1_check(const long long* qc, const floa
   }
   for (int k = 0; k < 3; ++k) sh[k][tid] = a[k];
   __syncthreads();
-  for (int o = MB / 2; o > 0; o >>= 1) {
+  for (int o = EVAL_NT / 2; o > 0; o >>= 1) {
     if (tid < o) for (int k = 0; k < 3; ++k) sh[k][tid] += sh[k][tid + o];
     __syncthreads();
   }
   if (tid < 3 && sh[tid][0]) atomicAdd(&out3[tid], sh[tid][0]);
 }
 
-// aux: [0] the bits of max |p|, [1] j0, [2 ..] MAXB block counts.  Counts the valid pixels per block and finds max |p|.
+// aux: [0] the bits of max |p|, [1] j0, [2 ..] EVAL_MAXB block counts.  Counts the valid pixels per block and finds max |p|.
 void launch_l1_maxabs(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, hipStream_t s) {
-  const int nb = nblocks(n);
+  const int nb = eval_nblocks(n);
   (void)hipMemsetAsync(aux, 0, 4, s);
   (void)hipMemsetAsync(aux + 1, 0xff, 4, s);
-  hipLaunchKernelGGL(k_l1_maxabs, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, l1_chunk(n, nb), aux, aux + 2);
+  hipLaunchKernelGGL(k_l1_maxabs, dim3(nb), dim3(EVAL_NT), 0, s, pred, gt, n, max_depth, lo, hi, l1_chunk(n, nb), aux, aux + 2);
 }
 void launch_l1_compact(const float* pred, const float* gt, long n, float max_depth, float lo, float hi, unsigned* aux, double up, float med,
                        unsigned cap, long long* qc, float* gc, hipStream_t s) {
-  const int nb = nblocks(n);
-  hipLaunchKernelGGL(k_l1_compact, dim3(nb), dim3(MB), 0, s, pred, gt, n, max_depth, lo, hi, l1_chunk(n, nb), aux + 2, up, med, cap, qc, gc,
+  const int nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_l1_compact, dim3(nb), dim3(EVAL_NT), 0, s, pred, gt, n, max_depth, lo, hi, l1_chunk(n, nb), aux + 2, up, med, cap, qc, gc,
                      aux + 1);
 }
 // one hist / scan pair of the weighted select, and the eight of them from the top byte of the key down
 template <int PASS>
 static void l1_select_pass(dim3 g, hipStream_t s, const long long* qc, const float* gc, long nv, long j, double down, u64* st) {
-  hipLaunchKernelGGL(k_l1_hist<PASS>, g, dim3(MB), 0, s, qc, gc, nv, j, down, st);
+  hipLaunchKernelGGL(k_l1_hist<PASS>, g, dim3(EVAL_NT), 0, s, qc, gc, nv, j, down, st);
   hipLaunchKernelGGL(k_l1_scan<PASS>, dim3(1), dim3(256), 0, s, st);
 }
 template <int... PASS>
@@ -682,11 +586,11 @@ static void l1_select_passes(std::integer_sequence<int, PASS...>, dim3 g, hipStr
 void launch_l1_step(const long long* qc, const float* gc, long nv, long j, double down, u64* st, unsigned* tie_idx, long long* tie_q,
                     hipStream_t s) {
   (void)hipMemsetAsync(st, 0, L1_WORDS * sizeof(u64), s);
-  const dim3 g(nblocks(nv)), b(MB);
+  const dim3 g(eval_nblocks(nv)), b(EVAL_NT);
   l1_select_passes(std::make_integer_sequence<int, 8>{}, g, s, qc, gc, nv, j, down, st);
   hipLaunchKernelGGL(k_l1_tie, g, b, 0, s, qc, gc, nv, j, down, st, tie_idx, tie_q);
 }
 // out3 must be zero before the launch
 void launch_l1_check(const long long* qc, const float* gc, long nv, long z, double S, double down, u64* out3, hipStream_t s) {
-  hipLaunchKernelGGL(k_l1_check, dim3(nblocks(nv)), dim3(MB), 0, s, qc, gc, nv, z, S, down, out3);
+  hipLaunchKernelGGL(k_l1_check, dim3(eval_nblocks(nv)), dim3(EVAL_NT), 0, s, qc, gc, nv, z, S, down, out3);
 }

@@ -8,12 +8,12 @@
 // section 20) finds the same neighbours without visiting every pair; its atomics are integer counts and list lengths.
 #include "../common.h"
 #include "../pcd_host.h"
+#include "eval_reduce.h"
 
 // No contraction anywhere in this file: every product and every sum below rounds on its own, as the numpy mirror's do.  (The __dmul_rn /
 // __dadd_rn intrinsics are plain operators in this toolchain and would fuse; the pragma is what keeps a * b + c two roundings.)
 #pragma clang fp contract(off)
 
-#define PB 256          // threads per block of the streaming kernels
 #define NN_TILE 256     // target points staged in LDS per step
 #define KNN_B 128       // threads per block of the neighbour-list kernel: 128 x 32 x 12 B of lists + the tile = 51 KiB of LDS
 #define KNN_MAX 32      // = UG_PCD_MAX_KNN
@@ -27,48 +27,48 @@ __device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned* sc, un
   const int tid = threadIdx.x;
   sc[tid] = v;
   __syncthreads();
-  for (int o = 1; o < PB; o <<= 1) {
+  for (int o = 1; o < EVAL_NT; o <<= 1) {
     const unsigned a = tid >= o ? sc[tid - o] : 0u;
     __syncthreads();
     sc[tid] += a;
     __syncthreads();
   }
   const unsigned incl = sc[tid];
-  *total = sc[PB - 1];
+  *total = sc[EVAL_NT - 1];
   __syncthreads();
   return incl - v;
 }
 
-__global__ __launch_bounds__(PB) void k_pcd_count(const unsigned char* mask, long n, long chunk, unsigned* counts) {
-  __shared__ unsigned sc[PB];
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_count(const unsigned char* mask, long n, long chunk, unsigned* counts) {
+  __shared__ unsigned sc[EVAL_NT];
   const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
   unsigned cnt = 0;
-  for (long i = b0 + threadIdx.x; i < b1; i += PB) cnt += mask[i] > 0;
+  for (long i = b0 + threadIdx.x; i < b1; i += EVAL_NT) cnt += mask[i] > 0;
   unsigned total;
   block_scan_excl(cnt, sc, &total);
   if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
-// one workgroup: counts[0 .. nb) -> exclusive offsets in place, counts[PCD_MAXB] = the total
-__global__ __launch_bounds__(PB) void k_pcd_offsets(unsigned* counts, int nb) {
-  __shared__ unsigned sh[PCD_MAXB];
-  for (int i = threadIdx.x; i < nb; i += PB) sh[i] = counts[i];
+// one workgroup: counts[0 .. nb) -> exclusive offsets in place, counts[EVAL_MAXB] = the total
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_offsets(unsigned* counts, int nb) {
+  __shared__ unsigned sh[EVAL_MAXB];
+  for (int i = threadIdx.x; i < nb; i += EVAL_NT) sh[i] = counts[i];
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned acc = 0;
     for (int b = 0; b < nb; ++b) { const unsigned v = sh[b]; sh[b] = acc; acc += v; }
-    counts[PCD_MAXB] = acc;
+    counts[EVAL_MAXB] = acc;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < nb; i += PB) counts[i] = sh[i];
+  for (int i = threadIdx.x; i < nb; i += EVAL_NT) counts[i] = sh[i];
 }
 
-__global__ __launch_bounds__(PB) void k_pcd_scatter(const float* pred, const float* gt, const unsigned char* mask, long n, long chunk,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_scatter(const float* pred, const float* gt, const unsigned char* mask, long n, long chunk,
                                                     const unsigned* counts, float* p_out, float* g_out) {
-  __shared__ unsigned sc[PB];
+  __shared__ unsigned sc[EVAL_NT];
   const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
   unsigned long base = counts[blockIdx.x];
-  for (long s0 = b0; s0 < b1; s0 += PB) {      // chunk is a multiple of PB: every thread of the block takes every step
+  for (long s0 = b0; s0 < b1; s0 += EVAL_NT) {      // chunk is a multiple of EVAL_NT: every thread of the block takes every step
     const long i = s0 + threadIdx.x;
     const unsigned keep = i < b1 && mask[i] > 0;
     unsigned total;
@@ -87,14 +87,14 @@ __global__ __launch_bounds__(PB) void k_pcd_scatter(const float* pred, const flo
 // four passes finish it.  State in device memory (unsigned words): sel[0 .. 256) the histogram of the pass, sel[256 .. 258) the key bits fixed
 // so far, sel[258 .. 260) the rank still to find inside that prefix.  Counts are integers: the result does not depend on workgroup order.
 template <typename T>
-__global__ __launch_bounds__(PB) void k_pcd_sel_hist(const T* v, long n, int stride, int offset, int shift, int first, const unsigned* sel,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_sel_hist(const T* v, long n, int stride, int offset, int shift, int first, const unsigned* sel,
                                                      unsigned* hist) {
   __shared__ unsigned h[256];
   const int tid = threadIdx.x;
   h[tid] = 0;
   __syncthreads();
   const u64 prefix = ((u64)sel[257] << 32) | sel[256];
-  for (long i = (long)blockIdx.x * PB + tid; i < n; i += (long)gridDim.x * PB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + tid; i < n; i += (long)gridDim.x * EVAL_NT) {
     const u64 key = pcd_key(v[i * stride + offset]);
     if (first || ((key ^ prefix) >> (shift + 8)) == 0) atomicAdd(&h[(unsigned)(key >> shift) & 255u], 1u);
   }
@@ -122,17 +122,17 @@ __global__ __launch_bounds__(256) void k_pcd_sel_scan(unsigned* sel, int shift, 
 
 // ------------------------------------------------------------------------------------------------------------- alignment
 // p.z -= median(p.z), g.z -= median(g.z): float32, as the reference's in-place tensor updates
-__global__ __launch_bounds__(PB) void k_pcd_shift_z(float* p, float* g, long n, const u64* res, int slot_p, int slot_g) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_shift_z(float* p, float* g, long n, const u64* res, int slot_p, int slot_g) {
   const float pz = pcd_unkey_f32(res[slot_p]), gz = pcd_unkey_f32(res[slot_g]);
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     p[i * 3 + 2] = p[i * 3 + 2] - pz;
     g[i * 3 + 2] = g[i * 3 + 2] - gz;
   }
 }
 // |p - c| with the float32 differences widened: the fp64 products are exact, two sums and one square root round, then once to float32
-__global__ __launch_bounds__(PB) void k_pcd_center_norm(const float* p, long n, const u64* res, int slot_c, float* norm) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_center_norm(const float* p, long n, const u64* res, int slot_c, float* norm) {
   const float cx = pcd_unkey_f32(res[slot_c]), cy = pcd_unkey_f32(res[slot_c + 1]), cz = pcd_unkey_f32(res[slot_c + 2]);
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const float fx = p[i * 3] - cx, fy = p[i * 3 + 1] - cy, fz = p[i * 3 + 2] - cz;      // float32 differences
     const double dx = fx, dy = fy, dz = fz;
     norm[i] = (float)__dsqrt_rn((dx * dx + dy * dy) + dz * dz);
@@ -140,9 +140,9 @@ __global__ __launch_bounds__(PB) void k_pcd_center_norm(const float* p, long n, 
 }
 // gather the sampled points (idx NULL: all), pred *= gt_scale / pred_scale, both z += gt_shift_z; float32 clouds and their fp64 copies (p64 and
 // g64 both NULL: none)
-__global__ __launch_bounds__(PB) void k_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32,
                                                   float* g32, double* p64, double* g64) {
-  for (long j = (long)blockIdx.x * PB + threadIdx.x; j < ns; j += (long)gridDim.x * PB) {
+  for (long j = (long)blockIdx.x * EVAL_NT + threadIdx.x; j < ns; j += (long)gridDim.x * EVAL_NT) {
     const long i = idx ? idx[j] : j;
     const float px = p[i * 3] * ratio, py = p[i * 3 + 1] * ratio, pz = p[i * 3 + 2] * ratio + gz;
     const float gx = g[i * 3], gy = g[i * 3 + 1], gzz = g[i * 3 + 2] + gz;
@@ -170,10 +170,10 @@ __device__ __forceinline__ double pcd_d2(double x, double y, double z, const dou
 
 // One query per thread; blockIdx.y owns the targets [y * slice, (y + 1) * slice), staged through LDS NN_TILE at a time and read by broadcast.
 // Targets are visited in index order and only a strictly smaller squared distance replaces the best: ties stay with the lowest index.
-__global__ __launch_bounds__(PB) void k_pcd_nn(const double* q, long nq, const double* t, long nt, const double* T44, long slice, int* pidx,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_nn(const double* q, long nq, const double* t, long nt, const double* T44, long slice, int* pidx,
                                                double* pdist) {
   __shared__ double tile[NN_TILE * 3];
-  const long i = (long)blockIdx.x * PB + threadIdx.x;
+  const long i = (long)blockIdx.x * EVAL_NT + threadIdx.x;
   const bool live = i < nq;
   double x = 0, y = 0, z = 0;
   if (live) { x = q[i * 3]; y = q[i * 3 + 1]; z = q[i * 3 + 2]; pcd_move(T44, x, y, z); }
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(PB) void k_pcd_nn(const double* q, long nq, const d
   long bi = t0;
   for (long base = t0; base < t1; base += NN_TILE) {
     const int cnt = (int)(t1 - base < NN_TILE ? t1 - base : NN_TILE);
-    for (int e = threadIdx.x; e < cnt * 3; e += PB) tile[e] = t[base * 3 + e];
+    for (int e = threadIdx.x; e < cnt * 3; e += EVAL_NT) tile[e] = t[base * 3 + e];
     __syncthreads();
     if (live)
       for (int j = 0; j < cnt; ++j) {
@@ -194,8 +194,8 @@ __global__ __launch_bounds__(PB) void k_pcd_nn(const double* q, long nq, const d
   if (live) { pdist[(long)blockIdx.y * nq + i] = best; pidx[(long)blockIdx.y * nq + i] = (int)bi; }
 }
 // the slices in slice order, again only a strictly smaller value wins; the distance is the square root of the winner
-__global__ __launch_bounds__(PB) void k_pcd_nn_combine(const int* pidx, const double* pdist, long nq, int ny, int* idx, double* dist) {
-  const long i = (long)blockIdx.x * PB + threadIdx.x;
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_nn_combine(const int* pidx, const double* pdist, long nq, int ny, int* idx, double* dist) {
+  const long i = (long)blockIdx.x * EVAL_NT + threadIdx.x;
   if (i >= nq) return;
   double best = pdist[i];
   int bi = pidx[i];
@@ -207,26 +207,13 @@ __global__ __launch_bounds__(PB) void k_pcd_nn_combine(const int* pidx, const do
 }
 
 // ------------------------------------------------------------------------------------------------------------- fixed-order reductions
-__device__ __forceinline__ double pcd_block_sum(double v, double* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = PB / 2; o > 0; o >>= 1) {
-    if (tid < o) sh[tid] += sh[tid + o];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
-
 // Kabsch sums over the correspondences (dist < threshold): n, sum s (3), sum d (3), sum d s^T (9, row = d), sum dist^2; s = the moved query
-__global__ __launch_bounds__(PB) void k_pcd_kabsch(const double* q, const double* t, long nq, const double* T44, const int* idx, const double* dist,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_kabsch(const double* q, const double* t, long nq, const double* T44, const int* idx, const double* dist,
                                                    double threshold, double* part) {
-  __shared__ double sh[PB];
+  __shared__ double sh[EVAL_NT];
   double a[17];
   for (int k = 0; k < 17; ++k) a[k] = 0;
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < nq; i += (long)gridDim.x * PB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < nq; i += (long)gridDim.x * EVAL_NT) {
     const double d = dist[i];
     if (!(d < threshold)) continue;
     double s[3] = {q[i * 3], q[i * 3 + 1], q[i * 3 + 2]};
@@ -237,28 +224,24 @@ __global__ __launch_bounds__(PB) void k_pcd_kabsch(const double* q, const double
     for (int r = 0; r < 3; ++r) for (int cc = 0; cc < 3; ++cc) a[7 + r * 3 + cc] += g[r] * s[cc];
     a[16] += d * d;
   }
-  for (int k = 0; k < 17; ++k) {
-    const double r = pcd_block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * 17 + k] = r;
-  }
+  eval_store_sums<17>(a, sh, part);
 }
-__global__ __launch_bounds__(PB) void k_pcd_sum(const double* v, long n, double* part) {
-  __shared__ double sh[PB];
-  double a = 0;
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) a += v[i];
-  const double r = pcd_block_sum(a, sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = r;
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_sum(const double* v, long n, double* part) {
+  __shared__ double sh[EVAL_NT];
+  double a[1] = {0};
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) a[0] += v[i];
+  eval_store_sums<1>(a, sh, part);
 }
-__global__ __launch_bounds__(PB) void k_pcd_move(const double* q, long n, const double* T44, double* out) {
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_move(const double* q, long n, const double* T44, double* out) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
     pcd_move(T44, x, y, z);
     out[i * 3] = x; out[i * 3 + 1] = y; out[i * 3 + 2] = z;
   }
 }
 // |n_t[idx] . n_q| per query
-__global__ __launch_bounds__(PB) void k_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot) {
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const double* a = nt + (long)idx[i] * 3;
     const double* b = nq + i * 3;
     dot[i] = fabs((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]);
@@ -359,7 +342,7 @@ __device__ __forceinline__ void fps_block_best(float& bm, int& bi, float* sm, in
   const int tid = threadIdx.x;
   sm[tid] = bm; si[tid] = bi;
   __syncthreads();
-  for (int o = PB / 2; o > 0; o >>= 1) {
+  for (int o = EVAL_NT / 2; o > 0; o >>= 1) {
     if (tid < o) {
       float m = sm[tid]; int i = si[tid];
       fps_better(m, i, sm[tid + o], si[tid + o]);
@@ -373,24 +356,24 @@ __device__ __forceinline__ void fps_block_best(float& bm, int& bi, float* sm, in
 #define FPS_NONE_M (-2.f)          // below every m (m >= -1): a thread or slot without a point never wins
 #define FPS_NONE_I 0x7fffffff
 
-__global__ __launch_bounds__(PB) void k_pcd_fps(const float* p, long n, float* m, long launch, int nprev, int last, float* pm, int* pi, long* idx,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_fps(const float* p, long n, float* m, long launch, int nprev, int last, float* pm, int* pi, long* idx,
                                                 float* sel_dist) {
-  __shared__ float sm[PB];
-  __shared__ int si[PB];
+  __shared__ float sm[EVAL_NT];
+  __shared__ int si[EVAL_NT];
   const int tid = threadIdx.x;
-  const float* pm_in = pm + ((launch & 1) ^ 1) * PCD_MAXB; const int* pi_in = pi + ((launch & 1) ^ 1) * PCD_MAXB;
-  float* pm_out = pm + (launch & 1) * PCD_MAXB; int* pi_out = pi + (launch & 1) * PCD_MAXB;
+  const float* pm_in = pm + ((launch & 1) ^ 1) * EVAL_MAXB; const int* pi_in = pi + ((launch & 1) ^ 1) * EVAL_MAXB;
+  float* pm_out = pm + (launch & 1) * EVAL_MAXB; int* pi_out = pi + (launch & 1) * EVAL_MAXB;
   float bm = FPS_NONE_M; int bi = FPS_NONE_I;
   float sx = 0.f, sy = 0.f, sz = 0.f;
   if (launch > 0) {
-    for (int b = tid; b < nprev; b += PB) fps_better(bm, bi, pm_in[b], pi_in[b]);
+    for (int b = tid; b < nprev; b += EVAL_NT) fps_better(bm, bi, pm_in[b], pi_in[b]);
     fps_block_best(bm, bi, sm, si);
     if (blockIdx.x == 0 && tid == 0) { idx[launch - 1] = bi; sel_dist[launch - 1] = bm; }
     if (last) return;
     sx = p[(long)bi * 3]; sy = p[(long)bi * 3 + 1]; sz = p[(long)bi * 3 + 2];
     bm = FPS_NONE_M; bi = FPS_NONE_I;
   }
-  for (long j = (long)blockIdx.x * PB + tid; j < n; j += (long)gridDim.x * PB) {      // ascending j: a strictly larger m keeps the lowest index
+  for (long j = (long)blockIdx.x * EVAL_NT + tid; j < n; j += (long)gridDim.x * EVAL_NT) {      // ascending j: a strictly larger m keeps the lowest index
     const float x = p[j * 3], y = p[j * 3 + 1], z = p[j * 3 + 2];
     float mj;
     if (launch == 0) {
@@ -408,8 +391,8 @@ __global__ __launch_bounds__(PB) void k_pcd_fps(const float* p, long n, float* m
   if (tid == 0) { pm_out[blockIdx.x] = bm; pi_out[blockIdx.x] = bi; }
 }
 
-__global__ __launch_bounds__(PB) void k_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64) {
-  for (long j = (long)blockIdx.x * PB + threadIdx.x; j < ns; j += (long)gridDim.x * PB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64) {
+  for (long j = (long)blockIdx.x * EVAL_NT + threadIdx.x; j < ns; j += (long)gridDim.x * EVAL_NT) {
     const long i = idx[j];
     const float x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
     if (out32) { out32[j * 3] = x; out32[j * 3 + 1] = y; out32[j * 3 + 2] = z; }
@@ -437,27 +420,12 @@ __device__ __forceinline__ int pcd_cell_axis(double x, double mn, double inv_h, 
   return !(f >= 0.0) ? 0 : (f > (double)(G - 1) ? G - 1 : (int)f);
 }
 
-template <int OP> __device__ __forceinline__ double pcd_block_reduce(double v, double* sh) {      // OP 0: sum, 1: min, 2: max; fixed order
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = PB / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      const double a = sh[tid], b = sh[tid + o];
-      sh[tid] = OP == 0 ? a + b : (OP == 1 ? (b < a ? b : a) : (b > a ? b : a));
-    }
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
 // stage 1 (final = 0): per workgroup min xyz, max xyz and the count of the finite points of t -> out[b * 7 ..]; stage 2 (final = 1, one workgroup):
 // the same over the nb rows of stage 1 -> out[0 .. 7)
-__global__ __launch_bounds__(PB) void k_pcd_grid_bbox(const double* in, long n, int final, double* out) {
-  __shared__ double sh[PB];
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_grid_bbox(const double* in, long n, int final, double* out) {
+  __shared__ double sh[EVAL_NT];
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, cnt = 0;
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     if (final) {
       for (int a = 0; a < 3; ++a) { const double l = in[i * 7 + a], h = in[i * 7 + 3 + a]; lo[a] = l < lo[a] ? l : lo[a]; hi[a] = h > hi[a] ? h : hi[a]; }
       cnt += in[i * 7 + 6];
@@ -469,14 +437,14 @@ __global__ __launch_bounds__(PB) void k_pcd_grid_bbox(const double* in, long n, 
     }
   }
   double r[7];
-  for (int a = 0; a < 3; ++a) { r[a] = pcd_block_reduce<1>(lo[a], sh); r[3 + a] = pcd_block_reduce<2>(hi[a], sh); }
-  r[6] = pcd_block_reduce<0>(cnt, sh);
+  for (int a = 0; a < 3; ++a) { r[a] = eval_block_reduce<1>(lo[a], sh); r[3 + a] = eval_block_reduce<2>(hi[a], sh); }
+  r[6] = eval_block_reduce<0>(cnt, sh);
   if (threadIdx.x == 0) for (int k = 0; k < 7; ++k) out[(long)blockIdx.x * 7 + k] = r[k];
 }
 
 // cell of every target (-1: a non-finite coordinate, in no cell) and the integer count per cell
-__global__ __launch_bounds__(PB) void k_pcd_grid_count(const double* t, long n, GridDev g, unsigned* counts, int* cell) {
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_grid_count(const double* t, long n, GridDev g, unsigned* counts, int* cell) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const double x = t[i * 3], y = t[i * 3 + 1], z = t[i * 3 + 2];
     int c = -1;
     if (pcd_finite3(x, y, z)) {
@@ -489,21 +457,21 @@ __global__ __launch_bounds__(PB) void k_pcd_grid_count(const double* t, long n, 
   }
 }
 // exclusive scan of the counts, as the masked compaction does it: workgroup b owns the cells [b * chunk, (b + 1) * chunk)
-__global__ __launch_bounds__(PB) void k_pcd_grid_scan_sums(const unsigned* counts, long cells, long chunk, unsigned* bsum) {
-  __shared__ unsigned sc[PB];
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_grid_scan_sums(const unsigned* counts, long cells, long chunk, unsigned* bsum) {
+  __shared__ unsigned sc[EVAL_NT];
   const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < cells ? b0 + chunk : cells;
   unsigned cnt = 0, mx = 0;
-  for (long i = b0 + threadIdx.x; i < b1; i += PB) { const unsigned v = counts[i]; cnt += v; mx = v > mx ? v : mx; }
+  for (long i = b0 + threadIdx.x; i < b1; i += EVAL_NT) { const unsigned v = counts[i]; cnt += v; mx = v > mx ? v : mx; }
   unsigned total;
   block_scan_excl(cnt, sc, &total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-  if (mx) atomicMax(&bsum[PCD_MAXB + 1], mx);      // the fullest cell: an integer maximum, the same in any order
+  if (mx) atomicMax(&bsum[EVAL_MAXB + 1], mx);      // the fullest cell: an integer maximum, the same in any order
 }
-__global__ __launch_bounds__(PB) void k_pcd_grid_scan_cells(const unsigned* counts, long cells, long chunk, const unsigned* bsum, unsigned* start) {
-  __shared__ unsigned sc[PB];
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_grid_scan_cells(const unsigned* counts, long cells, long chunk, const unsigned* bsum, unsigned* start) {
+  __shared__ unsigned sc[EVAL_NT];
   const long b0 = (long)blockIdx.x * chunk, b1 = b0 + chunk < cells ? b0 + chunk : cells;
   unsigned base = bsum[blockIdx.x];
-  for (long s0 = b0; s0 < b1; s0 += PB) {      // chunk is a multiple of PB: every thread of the block takes every step
+  for (long s0 = b0; s0 < b1; s0 += EVAL_NT) {      // chunk is a multiple of EVAL_NT: every thread of the block takes every step
     const long i = s0 + threadIdx.x;
     const unsigned v = i < b1 ? counts[i] : 0u;
     unsigned total;
@@ -511,12 +479,12 @@ __global__ __launch_bounds__(PB) void k_pcd_grid_scan_cells(const unsigned* coun
     if (i < b1) start[i] = base + pos;
     base += total;
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) start[cells] = bsum[PCD_MAXB];
+  if (blockIdx.x == 0 && threadIdx.x == 0) start[cells] = bsum[EVAL_MAXB];
 }
 // the sorted points and their original indices; counts runs down to zero, so position start + count - 1 is taken exactly once
-__global__ __launch_bounds__(PB) void k_pcd_grid_scatter(const double* t, long n, const int* cell, const unsigned* start, unsigned* counts,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_grid_scatter(const double* t, long n, const int* cell, const unsigned* start, unsigned* counts,
                                                          double* sorted, int* orig) {
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < n; i += (long)gridDim.x * PB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const int c = cell[i];
     if (c < 0) continue;
     const unsigned long pos = (unsigned long)start[c] + (atomicSub(&counts[c], 1u) - 1u);
@@ -551,9 +519,9 @@ __device__ __forceinline__ double pcd_ring_bound2(const GridDev& g, int r) {
 
 // One query per thread, moved by T44 as k_pcd_nn moves it.  The winner is the lexicographic minimum of (squared distance, original index): cells
 // are not visited in index order.  A query is settled when a target was found and either the ring bound or the whole grid is behind it.
-__global__ __launch_bounds__(PB) void k_pcd_nn_grid(const double* q, long nq, const double* T44, GridDev g, long n_in, int* idx, double* dist,
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_nn_grid(const double* q, long nq, const double* T44, GridDev g, long n_in, int* idx, double* dist,
                                                     int* left, unsigned* n_left) {
-  const long i = (long)blockIdx.x * PB + threadIdx.x;
+  const long i = (long)blockIdx.x * EVAL_NT + threadIdx.x;
   if (i >= nq) return;
   double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
   pcd_move(T44, x, y, z);
@@ -618,56 +586,54 @@ __global__ __launch_bounds__(KNN_B) void k_pcd_knn_grid(const double* pts, long 
   pcd_list_normal(pts, li, tid, k, normals + i * 3);
 }
 
-__global__ __launch_bounds__(PB) void k_pcd_gather64(const double* src, const int* list, long nl, double* out) {
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < nl; i += (long)gridDim.x * PB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_gather64(const double* src, const int* list, long nl, double* out) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < nl; i += (long)gridDim.x * EVAL_NT) {
     const long j = list[i];
     out[i * 3] = src[j * 3]; out[i * 3 + 1] = src[j * 3 + 1]; out[i * 3 + 2] = src[j * 3 + 2];
   }
 }
-__global__ __launch_bounds__(PB) void k_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist) {
-  for (long i = (long)blockIdx.x * PB + threadIdx.x; i < nl; i += (long)gridDim.x * PB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < nl; i += (long)gridDim.x * EVAL_NT) {
     const long j = list[i];
     idx[j] = idx_l[i]; dist[j] = dist_l[i];
   }
 }
 
 // ------------------------------------------------------------------------------------------------------------- launchers
-static int pcd_blocks(long n) { long b = (n + PB - 1) / PB; return (int)(b > PCD_MAXB ? PCD_MAXB : (b < 1 ? 1 : b)); }
-
 void launch_pcd_compact(const float* pred, const float* gt, const unsigned char* mask, long n, unsigned* counts, float* p_out, float* g_out,
                         hipStream_t s) {
-  const int nb = pcd_blocks(n);
-  const long chunk = ((n + nb - 1) / nb + PB - 1) / PB * PB;      // a multiple of PB; nb * chunk >= n
-  hipLaunchKernelGGL(k_pcd_count, dim3(nb), dim3(PB), 0, s, mask, n, chunk, counts);
-  hipLaunchKernelGGL(k_pcd_offsets, dim3(1), dim3(PB), 0, s, counts, nb);
-  hipLaunchKernelGGL(k_pcd_scatter, dim3(nb), dim3(PB), 0, s, pred, gt, mask, n, chunk, counts, p_out, g_out);
+  const int nb = eval_nblocks(n);
+  const long chunk = ((n + nb - 1) / nb + EVAL_NT - 1) / EVAL_NT * EVAL_NT;      // a multiple of EVAL_NT; nb * chunk >= n
+  hipLaunchKernelGGL(k_pcd_count, dim3(nb), dim3(EVAL_NT), 0, s, mask, n, chunk, counts);
+  hipLaunchKernelGGL(k_pcd_offsets, dim3(1), dim3(EVAL_NT), 0, s, counts, nb);
+  hipLaunchKernelGGL(k_pcd_scatter, dim3(nb), dim3(EVAL_NT), 0, s, pred, gt, mask, n, chunk, counts, p_out, g_out);
 }
 
 void launch_pcd_select(const void* v, int is_f64, long n, int stride, int offset, unsigned long long k, unsigned* sel, unsigned long long* res,
                        int slot, hipStream_t s) {
   (void)hipMemsetAsync(sel, 0, PCD_SEL_WORDS * sizeof(unsigned), s);
-  const int passes = is_f64 ? 8 : 4, nb = pcd_blocks(n);
+  const int passes = is_f64 ? 8 : 4, nb = eval_nblocks(n);
   for (int p = 0; p < passes; ++p) {
     const int shift = 56 - 8 * p;
-    if (is_f64) hipLaunchKernelGGL(k_pcd_sel_hist<double>, dim3(nb), dim3(PB), 0, s, (const double*)v, n, stride, offset, shift, p == 0, sel, sel);
-    else hipLaunchKernelGGL(k_pcd_sel_hist<float>, dim3(nb), dim3(PB), 0, s, (const float*)v, n, stride, offset, shift, p == 0, sel, sel);
+    if (is_f64) hipLaunchKernelGGL(k_pcd_sel_hist<double>, dim3(nb), dim3(EVAL_NT), 0, s, (const double*)v, n, stride, offset, shift, p == 0, sel, sel);
+    else hipLaunchKernelGGL(k_pcd_sel_hist<float>, dim3(nb), dim3(EVAL_NT), 0, s, (const float*)v, n, stride, offset, shift, p == 0, sel, sel);
     hipLaunchKernelGGL(k_pcd_sel_scan, dim3(1), dim3(256), 0, s, sel, shift, p == 0, p == passes - 1, (u64)k, (u64*)res, slot);
   }
 }
 void launch_pcd_shift_z(float* p, float* g, long n, const unsigned long long* res, int slot_p, int slot_g, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_shift_z, dim3(pcd_blocks(n)), dim3(PB), 0, s, p, g, n, (const u64*)res, slot_p, slot_g);
+  hipLaunchKernelGGL(k_pcd_shift_z, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, p, g, n, (const u64*)res, slot_p, slot_g);
 }
 void launch_pcd_center_norm(const float* p, long n, const unsigned long long* res, int slot_c, float* norm, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_center_norm, dim3(pcd_blocks(n)), dim3(PB), 0, s, p, n, (const u64*)res, slot_c, norm);
+  hipLaunchKernelGGL(k_pcd_center_norm, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, p, n, (const u64*)res, slot_c, norm);
 }
 void launch_pcd_align(const float* p, const float* g, const long* idx, long ns, float ratio, float gz, float* p32, float* g32, double* p64, double* g64,
                       hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_align, dim3(pcd_blocks(ns)), dim3(PB), 0, s, p, g, idx, ns, ratio, gz, p32, g32, p64, g64);
+  hipLaunchKernelGGL(k_pcd_align, dim3(eval_nblocks(ns)), dim3(EVAL_NT), 0, s, p, g, idx, ns, ratio, gz, p32, g32, p64, g64);
 }
 
 // how the targets are split over blockIdx.y: enough slices that about 2048 workgroups are in flight, whole tiles per slice, at most 64 slices
 static long pcd_nn_slice(long nq, long nt, int* ny) {
-  const long bx = (nq + PB - 1) / PB, tiles = (nt + NN_TILE - 1) / NN_TILE;
+  const long bx = (nq + EVAL_NT - 1) / EVAL_NT, tiles = (nt + NN_TILE - 1) / NN_TILE;
   long want = 2048 / (bx < 1 ? 1 : bx);
   want = want < 1 ? 1 : (want > 64 ? 64 : want);
   if (want > tiles) want = tiles;
@@ -683,46 +649,46 @@ void launch_pcd_nn(const double* q, long nq, const double* t, long nt, const dou
                    hipStream_t s) {
   int ny;
   const long slice = pcd_nn_slice(nq, nt, &ny);
-  const int bx = (int)((nq + PB - 1) / PB);
-  hipLaunchKernelGGL(k_pcd_nn, dim3(bx, ny), dim3(PB), 0, s, q, nq, t, nt, T44, slice, pidx, pdist);
-  hipLaunchKernelGGL(k_pcd_nn_combine, dim3(bx), dim3(PB), 0, s, pidx, pdist, nq, ny, idx, dist);
+  const int bx = (int)((nq + EVAL_NT - 1) / EVAL_NT);
+  hipLaunchKernelGGL(k_pcd_nn, dim3(bx, ny), dim3(EVAL_NT), 0, s, q, nq, t, nt, T44, slice, pidx, pdist);
+  hipLaunchKernelGGL(k_pcd_nn_combine, dim3(bx), dim3(EVAL_NT), 0, s, pidx, pdist, nq, ny, idx, dist);
 }
 void launch_pcd_kabsch(const double* q, const double* t, long nq, const double* T44, const int* idx, const double* dist, double threshold,
                        double* part, int* nb, hipStream_t s) {
-  *nb = pcd_blocks(nq);
-  hipLaunchKernelGGL(k_pcd_kabsch, dim3(*nb), dim3(PB), 0, s, q, t, nq, T44, idx, dist, threshold, part);
+  *nb = eval_nblocks(nq);
+  hipLaunchKernelGGL(k_pcd_kabsch, dim3(*nb), dim3(EVAL_NT), 0, s, q, t, nq, T44, idx, dist, threshold, part);
 }
 void launch_pcd_move(const double* q, long n, const double* T44, double* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_move, dim3(pcd_blocks(n)), dim3(PB), 0, s, q, n, T44, out);
+  hipLaunchKernelGGL(k_pcd_move, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, q, n, T44, out);
 }
 void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr, double* normals, hipStream_t s) {
   const int k = (int)(n < knn ? n : knn);
   hipLaunchKernelGGL(k_pcd_knn, dim3((unsigned)((n + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, pts, n, k, (const int*)nullptr, n, nbr, normals);
 }
 void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_normal_dot, dim3(pcd_blocks(n)), dim3(PB), 0, s, nq, nt, idx, n, dot);
+  hipLaunchKernelGGL(k_pcd_normal_dot, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, nq, nt, idx, n, dot);
 }
 // k picks in k + 1 plain launches: launch 0 initialises m, launch L writes pick L - 1; the last one has nothing left to update and is one workgroup
 void launch_pcd_fps(const float* p, long n, long k, float* m, float* pm, int* pi, long* idx, float* sel_dist, hipStream_t s) {
-  const int nb = pcd_blocks(n);
+  const int nb = eval_nblocks(n);
   for (long L = 0; L <= k; ++L) {
     const int last = L == k;
-    hipLaunchKernelGGL(k_pcd_fps, dim3(last ? 1 : nb), dim3(PB), 0, s, p, n, m, L, nb, last, pm, pi, idx, sel_dist);
+    hipLaunchKernelGGL(k_pcd_fps, dim3(last ? 1 : nb), dim3(EVAL_NT), 0, s, p, n, m, L, nb, last, pm, pi, idx, sel_dist);
   }
 }
 void launch_pcd_gather(const float* src, const long* idx, long ns, float* out32, double* out64, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_gather, dim3(pcd_blocks(ns)), dim3(PB), 0, s, src, idx, ns, out32, out64);
+  hipLaunchKernelGGL(k_pcd_gather, dim3(eval_nblocks(ns)), dim3(EVAL_NT), 0, s, src, idx, ns, out32, out64);
 }
 void launch_pcd_sum(const double* v, long n, double* part, int* nb, hipStream_t s) {
-  *nb = pcd_blocks(n);
-  hipLaunchKernelGGL(k_pcd_sum, dim3(*nb), dim3(PB), 0, s, v, n, part);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pcd_sum, dim3(*nb), dim3(EVAL_NT), 0, s, v, n, part);
 }
 
 // ------------------------------------------------------------------------------------------------------------- grid launchers
 void launch_pcd_grid_bbox(const double* t, long n, double* part, double* box, hipStream_t s) {
-  const int nb = pcd_blocks(n);
-  hipLaunchKernelGGL(k_pcd_grid_bbox, dim3(nb), dim3(PB), 0, s, t, n, 0, part);
-  hipLaunchKernelGGL(k_pcd_grid_bbox, dim3(1), dim3(PB), 0, s, (const double*)part, (long)nb, 1, box);
+  const int nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pcd_grid_bbox, dim3(nb), dim3(EVAL_NT), 0, s, t, n, 0, part);
+  hipLaunchKernelGGL(k_pcd_grid_bbox, dim3(1), dim3(EVAL_NT), 0, s, (const double*)part, (long)nb, 1, box);
 }
 
 // host: the rule for h lives in pcd_host.h (plain C++, tested under sanitizers on the host)
@@ -736,19 +702,19 @@ void launch_pcd_grid_build(const double* t, long n, const PcdGrid& g, unsigned* 
                            int* orig, hipStream_t s) {
   const GridDev d = grid_dev(g);
   (void)hipMemsetAsync(counts, 0, (size_t)g.cells * sizeof(unsigned), s);
-  (void)hipMemsetAsync(bsum, 0, (PCD_MAXB + 2) * sizeof(unsigned), s);
-  hipLaunchKernelGGL(k_pcd_grid_count, dim3(pcd_blocks(n)), dim3(PB), 0, s, t, n, d, counts, cell);
-  const int nb = pcd_blocks(g.cells);
-  const long chunk = ((g.cells + nb - 1) / nb + PB - 1) / PB * PB;      // a multiple of PB; nb * chunk >= cells
-  hipLaunchKernelGGL(k_pcd_grid_scan_sums, dim3(nb), dim3(PB), 0, s, (const unsigned*)counts, g.cells, chunk, bsum);
-  hipLaunchKernelGGL(k_pcd_offsets, dim3(1), dim3(PB), 0, s, bsum, nb);
-  hipLaunchKernelGGL(k_pcd_grid_scan_cells, dim3(nb), dim3(PB), 0, s, (const unsigned*)counts, g.cells, chunk, (const unsigned*)bsum, start);
-  hipLaunchKernelGGL(k_pcd_grid_scatter, dim3(pcd_blocks(n)), dim3(PB), 0, s, t, n, (const int*)cell, (const unsigned*)start, counts, sorted, orig);
+  (void)hipMemsetAsync(bsum, 0, (EVAL_MAXB + 2) * sizeof(unsigned), s);
+  hipLaunchKernelGGL(k_pcd_grid_count, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, t, n, d, counts, cell);
+  const int nb = eval_nblocks(g.cells);
+  const long chunk = ((g.cells + nb - 1) / nb + EVAL_NT - 1) / EVAL_NT * EVAL_NT;      // a multiple of EVAL_NT; nb * chunk >= cells
+  hipLaunchKernelGGL(k_pcd_grid_scan_sums, dim3(nb), dim3(EVAL_NT), 0, s, (const unsigned*)counts, g.cells, chunk, bsum);
+  hipLaunchKernelGGL(k_pcd_offsets, dim3(1), dim3(EVAL_NT), 0, s, bsum, nb);
+  hipLaunchKernelGGL(k_pcd_grid_scan_cells, dim3(nb), dim3(EVAL_NT), 0, s, (const unsigned*)counts, g.cells, chunk, (const unsigned*)bsum, start);
+  hipLaunchKernelGGL(k_pcd_grid_scatter, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, t, n, (const int*)cell, (const unsigned*)start, counts, sorted, orig);
 }
 void launch_pcd_nn_grid(const double* q, long nq, const double* T44, const PcdGrid& g, int* idx, double* dist, int* left, unsigned* n_left,
                         hipStream_t s) {
   (void)hipMemsetAsync(n_left, 0, sizeof(unsigned), s);
-  hipLaunchKernelGGL(k_pcd_nn_grid, dim3((unsigned)((nq + PB - 1) / PB)), dim3(PB), 0, s, q, nq, T44, grid_dev(g), g.n_in, idx, dist, left, n_left);
+  hipLaunchKernelGGL(k_pcd_nn_grid, dim3((unsigned)((nq + EVAL_NT - 1) / EVAL_NT)), dim3(EVAL_NT), 0, s, q, nq, T44, grid_dev(g), g.n_in, idx, dist, left, n_left);
 }
 void launch_pcd_knn_grid(const PcdGrid& g, int knn, int* nbr, double* normals, int* left, unsigned* n_left, hipStream_t s) {
   const int k = (int)(g.n < knn ? g.n : knn);
@@ -761,8 +727,8 @@ void launch_pcd_knn_normals_list(const double* pts, long n, int knn, const int* 
   hipLaunchKernelGGL(k_pcd_knn, dim3((unsigned)((nl + KNN_B - 1) / KNN_B)), dim3(KNN_B), 0, s, pts, n, k, list, nl, nbr, normals);
 }
 void launch_pcd_gather64(const double* src, const int* list, long nl, double* out, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_gather64, dim3(pcd_blocks(nl)), dim3(PB), 0, s, src, list, nl, out);
+  hipLaunchKernelGGL(k_pcd_gather64, dim3(eval_nblocks(nl)), dim3(EVAL_NT), 0, s, src, list, nl, out);
 }
 void launch_pcd_nn_scatter(const int* list, long nl, const int* idx_l, const double* dist_l, int* idx, double* dist, hipStream_t s) {
-  hipLaunchKernelGGL(k_pcd_nn_scatter, dim3(pcd_blocks(nl)), dim3(PB), 0, s, list, nl, idx_l, dist_l, idx, dist);
+  hipLaunchKernelGGL(k_pcd_nn_scatter, dim3(eval_nblocks(nl)), dim3(EVAL_NT), 0, s, list, nl, idx_l, dist_l, idx, dist);
 }

@@ -6,29 +6,9 @@
 // in LDS - that the caller adds in block order.  No atomics, no cooperative launch, no inline assembly: the result does not depend on the
 // order in which workgroups arrive.  The 3x3 inverse and the SVD of every iteration are done on the host (pcd_host.h).
 #include "../common.h"
+#include "eval_reduce.h"
 
 #pragma clang fp contract(off)
-
-#define PMB 256          // threads per block
-
-__device__ __forceinline__ double pm_block_sum(double v, double* sh) {
-  const int tid = threadIdx.x;
-  sh[tid] = v;
-  __syncthreads();
-  for (int o = PMB / 2; o > 0; o >>= 1) {
-    if (tid < o) sh[tid] += sh[tid + o];
-    __syncthreads();
-  }
-  const double r = sh[0];
-  __syncthreads();
-  return r;
-}
-template <int K> __device__ __forceinline__ void pm_store_sums(const double (&a)[K], double* sh, double* part) {
-  for (int k = 0; k < K; ++k) {
-    const double r = pm_block_sum(a[k], sh);
-    if (threadIdx.x == 0) part[(long)blockIdx.x * K + k] = r;
-  }
-}
 
 __device__ __forceinline__ void pm_pixel(const PmCam& cam, long i, double& col, double& row) {
   const long r = i / cam.W;
@@ -54,11 +34,11 @@ __device__ __forceinline__ double pm_dot(const double* a, const double* b) { ret
 // INIT: partials of sum xy.px and sum xy.xy (the closed-form start); otherwise the same two weighted by w = 1 / max(|px - f xy|, 1e-8).
 // xy = (x / z, y / z) with a non-finite quotient set to 0.
 template <bool INIT>
-__global__ __launch_bounds__(PMB) void k_pm_focal_pass(const float* pts, long n, PmCam cam, const double* fz, double* part) {
-  __shared__ double sh[PMB];
+__global__ __launch_bounds__(EVAL_NT) void k_pm_focal_pass(const float* pts, long n, PmCam cam, const double* fz, double* part) {
+  __shared__ double sh[EVAL_NT];
   const double f = INIT ? 0.0 : fz[0];
   double acc[2] = {0, 0};
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     double X[3], col, row;
     pm_load(pts, i, X);
     pm_pixel(cam, i, col, row);
@@ -75,12 +55,12 @@ __global__ __launch_bounds__(PMB) void k_pm_focal_pass(const float* pts, long n,
       acc[0] += w * dpx; acc[1] += w * dxx;
     }
   }
-  pm_store_sums<2>(acc, sh, part);
+  eval_store_sums<2>(acc, sh, part);
 }
 // one workgroup: the partials added in block order by one thread, the next focal = mean / mean
-__global__ __launch_bounds__(PMB) void k_pm_focal_reduce(const double* part, int nb, double npix, double* fz) {
-  __shared__ double sh[PM_MAXB * 2];
-  for (int i = threadIdx.x; i < nb * 2; i += PMB) sh[i] = part[i];
+__global__ __launch_bounds__(EVAL_NT) void k_pm_focal_reduce(const double* part, int nb, double npix, double* fz) {
+  __shared__ double sh[EVAL_MAXB * 2];
+  for (int i = threadIdx.x; i < nb * 2; i += EVAL_NT) sh[i] = part[i];
   __syncthreads();
   if (threadIdx.x == 0) {
     double a[2] = {0, 0};
@@ -90,17 +70,17 @@ __global__ __launch_bounds__(PMB) void k_pm_focal_reduce(const double* part, int
 }
 
 // ------------------------------------------------------------------------------------------------------------- poses
-__global__ __launch_bounds__(PMB) void k_pm_valid(const float* pts, const unsigned char* mask, long n, unsigned char* valid) {
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pm_valid(const float* pts, const unsigned char* mask, long n, unsigned char* valid) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     const bool fin = isfinite(pts[i * 3]) && isfinite(pts[i * 3 + 1]) && isfinite(pts[i * 3 + 2]);
     valid[i] = fin && (!mask || mask[i] > 0);
   }
 }
 
-__global__ __launch_bounds__(PMB) void k_pm_pass0(const float* pts, const unsigned char* keep, long n, PmCam cam, double* part) {
-  __shared__ double sh[PMB];
+__global__ __launch_bounds__(EVAL_NT) void k_pm_pass0(const float* pts, const unsigned char* keep, long n, PmCam cam, double* part) {
+  __shared__ double sh[EVAL_NT];
   double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     if (!keep[i]) continue;
     double X[3], b[3];
     pm_load(pts, i, X);
@@ -109,13 +89,13 @@ __global__ __launch_bounds__(PMB) void k_pm_pass0(const float* pts, const unsign
     a[1] += b[0] * b[0]; a[2] += b[0] * b[1]; a[3] += b[0] * b[2]; a[4] += b[1] * b[1]; a[5] += b[1] * b[2]; a[6] += b[2] * b[2];
     a[7] += pm_dot(X, X);
   }
-  pm_store_sums<8>(a, sh, part);
+  eval_store_sums<8>(a, sh, part);
 }
 
-__global__ __launch_bounds__(PMB) void k_pm_pass1(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part) {
-  __shared__ double sh[PMB];
+__global__ __launch_bounds__(EVAL_NT) void k_pm_pass1(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part) {
+  __shared__ double sh[EVAL_NT];
   double a[3] = {0, 0, 0};
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     if (!keep[i]) continue;
     double X[3], b[3], p[3];
     pm_load(pts, i, X);
@@ -124,14 +104,14 @@ __global__ __launch_bounds__(PMB) void k_pm_pass1(const float* pts, const unsign
     const double bp = pm_dot(b, p);
     for (int r = 0; r < 3; ++r) a[r] += b[r] * bp - p[r];
   }
-  pm_store_sums<3>(a, sh, part);
+  eval_store_sums<3>(a, sh, part);
 }
 
-__global__ __launch_bounds__(PMB) void k_pm_pass2(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part) {
-  __shared__ double sh[PMB];
+__global__ __launch_bounds__(EVAL_NT) void k_pm_pass2(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part) {
+  __shared__ double sh[EVAL_NT];
   double a[17];
   for (int k = 0; k < 17; ++k) a[k] = 0;
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     if (!keep[i]) continue;
     double X[3], b[3], c[3], q[3], d[3];
     pm_load(pts, i, X);
@@ -145,14 +125,14 @@ __global__ __launch_bounds__(PMB) void k_pm_pass2(const float* pts, const unsign
     for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) a[7 + r * 3 + k] += q[r] * X[k];
     a[16] += (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
   }
-  pm_store_sums<17>(a, sh, part);
+  eval_store_sums<17>(a, sh, part);
 }
 
-__global__ __launch_bounds__(PMB) void k_pm_inliers(const float* pts, const unsigned char* valid, const unsigned char* keep, long n, PmCam cam,
+__global__ __launch_bounds__(EVAL_NT) void k_pm_inliers(const float* pts, const unsigned char* valid, const unsigned char* keep, long n, PmCam cam,
                                                     PmPose pose, double thr2, unsigned char* keep_new, double* part) {
-  __shared__ double sh[PMB];
+  __shared__ double sh[EVAL_NT];
   double a[3] = {0, 0, 0};
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     bool in = false;
     double e2 = 0.0;
     if (valid[i]) {
@@ -169,11 +149,11 @@ __global__ __launch_bounds__(PMB) void k_pm_inliers(const float* pts, const unsi
     if (in) { a[0] += 1.0; a[2] += e2; }
     if (in != (keep[i] != 0)) a[1] += 1.0;
   }
-  pm_store_sums<3>(a, sh, part);
+  eval_store_sums<3>(a, sh, part);
 }
 
-__global__ __launch_bounds__(PMB) void k_pm_depth(const float* pts, const unsigned char* valid, long n, PmPose pose, float* depth) {
-  for (long i = (long)blockIdx.x * PMB + threadIdx.x; i < n; i += (long)gridDim.x * PMB) {
+__global__ __launch_bounds__(EVAL_NT) void k_pm_depth(const float* pts, const unsigned char* valid, long n, PmPose pose, float* depth) {
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     float z = 0.f;
     if (valid[i]) {
       double X[3];
@@ -185,37 +165,35 @@ __global__ __launch_bounds__(PMB) void k_pm_depth(const float* pts, const unsign
 }
 
 // ------------------------------------------------------------------------------------------------------------- launchers
-static int pm_blocks(long n) { long b = (n + PMB - 1) / PMB; return (int)(b > PM_MAXB ? PM_MAXB : (b < 1 ? 1 : b)); }
-
 void launch_pm_focal(const float* pts, long n, PmCam cam, int steps, double* part, double* fz, hipStream_t s) {
-  const int nb = pm_blocks(n);
-  hipLaunchKernelGGL(k_pm_focal_pass<true>, dim3(nb), dim3(PMB), 0, s, pts, n, cam, (const double*)fz, part);
-  hipLaunchKernelGGL(k_pm_focal_reduce, dim3(1), dim3(PMB), 0, s, (const double*)part, nb, (double)n, fz);
+  const int nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pm_focal_pass<true>, dim3(nb), dim3(EVAL_NT), 0, s, pts, n, cam, (const double*)fz, part);
+  hipLaunchKernelGGL(k_pm_focal_reduce, dim3(1), dim3(EVAL_NT), 0, s, (const double*)part, nb, (double)n, fz);
   for (int it = 0; it < steps; ++it) {
-    hipLaunchKernelGGL(k_pm_focal_pass<false>, dim3(nb), dim3(PMB), 0, s, pts, n, cam, (const double*)fz, part);
-    hipLaunchKernelGGL(k_pm_focal_reduce, dim3(1), dim3(PMB), 0, s, (const double*)part, nb, (double)n, fz);
+    hipLaunchKernelGGL(k_pm_focal_pass<false>, dim3(nb), dim3(EVAL_NT), 0, s, pts, n, cam, (const double*)fz, part);
+    hipLaunchKernelGGL(k_pm_focal_reduce, dim3(1), dim3(EVAL_NT), 0, s, (const double*)part, nb, (double)n, fz);
   }
 }
 void launch_pm_valid(const float* pts, const unsigned char* mask, long n, unsigned char* valid, hipStream_t s) {
-  hipLaunchKernelGGL(k_pm_valid, dim3(pm_blocks(n)), dim3(PMB), 0, s, pts, mask, n, valid);
+  hipLaunchKernelGGL(k_pm_valid, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, pts, mask, n, valid);
 }
 void launch_pm_pass0(const float* pts, const unsigned char* keep, long n, PmCam cam, double* part, int* nb, hipStream_t s) {
-  *nb = pm_blocks(n);
-  hipLaunchKernelGGL(k_pm_pass0, dim3(*nb), dim3(PMB), 0, s, pts, keep, n, cam, part);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pm_pass0, dim3(*nb), dim3(EVAL_NT), 0, s, pts, keep, n, cam, part);
 }
 void launch_pm_pass1(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part, int* nb, hipStream_t s) {
-  *nb = pm_blocks(n);
-  hipLaunchKernelGGL(k_pm_pass1, dim3(*nb), dim3(PMB), 0, s, pts, keep, n, cam, pose, part);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pm_pass1, dim3(*nb), dim3(EVAL_NT), 0, s, pts, keep, n, cam, pose, part);
 }
 void launch_pm_pass2(const float* pts, const unsigned char* keep, long n, PmCam cam, PmPose pose, double* part, int* nb, hipStream_t s) {
-  *nb = pm_blocks(n);
-  hipLaunchKernelGGL(k_pm_pass2, dim3(*nb), dim3(PMB), 0, s, pts, keep, n, cam, pose, part);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pm_pass2, dim3(*nb), dim3(EVAL_NT), 0, s, pts, keep, n, cam, pose, part);
 }
 void launch_pm_inliers(const float* pts, const unsigned char* valid, const unsigned char* keep, long n, PmCam cam, PmPose pose, double thr2,
                        unsigned char* keep_new, double* part, int* nb, hipStream_t s) {
-  *nb = pm_blocks(n);
-  hipLaunchKernelGGL(k_pm_inliers, dim3(*nb), dim3(PMB), 0, s, pts, valid, keep, n, cam, pose, thr2, keep_new, part);
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pm_inliers, dim3(*nb), dim3(EVAL_NT), 0, s, pts, valid, keep, n, cam, pose, thr2, keep_new, part);
 }
 void launch_pm_depth(const float* pts, const unsigned char* valid, long n, PmPose pose, float* depth, hipStream_t s) {
-  hipLaunchKernelGGL(k_pm_depth, dim3(pm_blocks(n)), dim3(PMB), 0, s, pts, valid, n, pose, depth);
+  hipLaunchKernelGGL(k_pm_depth, dim3(eval_nblocks(n)), dim3(EVAL_NT), 0, s, pts, valid, n, pose, depth);
 }
