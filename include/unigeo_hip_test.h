@@ -111,6 +111,38 @@ int ug_op_temporal_attn_nv(ug_ctx* ctx, const float* qkv, int nv, int T, int HW,
 int ug_op_attention_generic(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);
 int ug_op_flash_attn_dh(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);   /* fused self-attention, head dim d in {32,48,80,96,112,128}: the CLIP tower's 16 x 80 heads */
 int ug_op_euler_step(ug_ctx* ctx, const float* v, float* latents_inout, long n, float sigma, float sigma_next);
+/* The pipeline glue of kernels/misc.hip one launch at a time (tests/test_glue_gpu.py).  Each entry calls the product's own
+ * launcher on the context's stream and nothing else.  Host in / host out in float32; what the device holds as fp16 is rounded on the way in (the tests
+ * pass fp16-representable values) and widened on the way out.  Every *_inout buffer has `guard` extra rows (or elements), goes to the device as the
+ * caller gives it and comes back whole: the guard, and whatever else the kernel must not write, returns unchanged.
+ *   ug_op_clip_patchify   : video_m11 [T,H,W,3] -> out_inout [T*(S/P)^2 + guard, Kpad]: pre-blur, bicubic resample to S x S, CLIP (imagenet_norm = 0) or
+ *                           ImageNet mean / std, patch column c*P*P + py*P + px; columns [3*P*P, Kpad) are not written
+ *   ug_op_prep_video      : frames [T,H,W,3] and noise [T,3,H,W], both float32 on the device -> clip_src_inout [T*H*W + guard, 3], vae_in_inout [.. , 8]
+ *   ug_op_init_latents    : noise [T,4,hw] float32 on the device -> lat_inout [T*hw + guard, 4] = fp16(fp16(noise) * sigma0)
+ *   ug_op_unet_input      : lat, cond [pixels,4] -> x_inout [pixels + guard, 8] = (lat / den | cond); guided != 0: [2*pixels + guard, 8], the second
+ *                           video (lat / den | 0) stacked under the first (launch_make_unet_input_cfg)
+ *   ug_op_euler_step_cfg  : the guided step on v_u + g (v_c - v_u); lat_inout [n + guard]
+ *   ug_op_window_blend    : the two overlap launches of the latent sliding windows over n = overlap * frame_elems elements.  renoised_inout [n + guard]
+ *                           holds the window's noise on entry and returns prev + coef * noise (launch_axpby_f16, in place as the engine calls it);
+ *                           faded_inout [n + guard] holds the running result on entry and returns the cross-fade with cur (launch_crossfade_f16)
+ *   ug_op_time_conv_out   : x [T,HW,Cs] (Cs >= 3, channels 3.. ignored), w [3 out][3 in][3 taps], b [3] -> out_inout [T*HW + guard, 3] float32
+ *   ug_op_depth_post      : frames [n,3] float32 -> depth_inout [n + guard] (launch_depth_post), disp_inout [n + guard] (launch_disparity_from_frames on
+ *                           the min-max words that launch left), minmax_out [2] = those words decoded to float (min, max)
+ *   ug_op_add_grid_nearest: x_inout [B*h*w + guard, C] += grid [B,g,g,C] at (y*g/h, x*g/w); C % 8 == 0
+ *   ug_op_sn_normals_out  : dec [pixels, ldd] (columns 3.. ignored) -> out_inout [pixels + guard, 3] float32, clipped to [-1,1] and normalised
+ *   ug_op_clip_assemble   : patches [T*np, d], cls [d], pos [np+1, d] -> tok_inout [T*(np+1) + guard, d] */
+int ug_op_clip_patchify(ug_ctx* ctx, const float* video_m11, int T, int H, int W, int S, int P, int Kpad, int imagenet_norm, long guard, float* out_inout);
+int ug_op_prep_video(ug_ctx* ctx, const float* frames, const float* noise, int T, int H, int W, float aug, long guard, float* clip_src_inout, float* vae_in_inout);
+int ug_op_init_latents(ug_ctx* ctx, const float* noise_tchw, int T, long hw, float sigma0, long guard, float* lat_inout);
+int ug_op_unet_input(ug_ctx* ctx, const float* lat, const float* cond, long pixels, float den, int guided, long guard, float* x_inout);
+int ug_op_euler_step_cfg(ug_ctx* ctx, const float* vc, const float* vu, float g, long n, float sigma, float sigma_next, long guard, float* lat_inout);
+int ug_op_window_blend(ug_ctx* ctx, const float* prev, const float* cur, long frame_elems, int overlap, float coef, long guard,
+                       float* renoised_inout, float* faded_inout);
+int ug_op_time_conv_out(ug_ctx* ctx, const float* x, const float* w, const float* b, int T, long HW, int Cs, long guard, float* out_inout);
+int ug_op_depth_post(ug_ctx* ctx, const float* frames, long n, long guard, float* depth_inout, float* disp_inout, float* minmax_out /*[2]*/);
+int ug_op_add_grid_nearest(ug_ctx* ctx, const float* grid, int B, int h, int w, int g, int C, long guard, float* x_inout);
+int ug_op_sn_normals_out(ug_ctx* ctx, const float* dec, int ldd, long pixels, long guard, float* out_inout);
+int ug_op_clip_assemble(ug_ctx* ctx, const float* patches, const float* cls, const float* pos, int T, int np, int d, long guard, float* tok_inout);
 /* The float32-grade VAE encoder's kernels op by op (kernels/wide.hip and the engine's pair convolution / attention; the reference runs the encoder in
  * float32 under force_upcast, inside the un-vendored AutoencoderKL).  float32 in and out, no rounding of the inputs to fp16 (weights, bias, gamma and
  * beta are bound as fp16, as the checkpoint stores them).

@@ -26,6 +26,8 @@ EXPORTS = [
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex",
+    "ug_op_clip_patchify", "ug_op_prep_video", "ug_op_init_latents", "ug_op_unet_input", "ug_op_euler_step_cfg", "ug_op_window_blend",
+    "ug_op_time_conv_out", "ug_op_depth_post", "ug_op_add_grid_nearest", "ug_op_sn_normals_out", "ug_op_clip_assemble",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
@@ -210,6 +212,14 @@ def load_library():
         "ug_op_conv_bound": [vp, vp, vp, ip, ip, ip, ip, ip, vp, ip, vp, ip, ip, ip, ip, ip, ip, ip, ip, vp, C.c_float, C.c_float, ip, C.c_long, C.c_long, vp, vp]})
     _set_argtypes(lib, {"ug_op_ff_ex": [vp, vp, ip, ip, vp, vp, vp, vp, vp, ip, vp, C.c_float, C.c_float, C.c_float, vp, vp, C.c_float, vp, ip,
                                         ip, ip, C.c_long, C.c_long, vp, vp]})
+    lg, fl = C.c_long, C.c_float
+    _set_argtypes(lib, {
+        "ug_op_clip_patchify": [vp, vp, ip, ip, ip, ip, ip, ip, ip, lg, vp], "ug_op_prep_video": [vp, vp, vp, ip, ip, ip, fl, lg, vp, vp],
+        "ug_op_init_latents": [vp, vp, ip, lg, fl, lg, vp], "ug_op_unet_input": [vp, vp, vp, lg, fl, ip, lg, vp],
+        "ug_op_euler_step_cfg": [vp, vp, vp, fl, lg, fl, fl, lg, vp], "ug_op_window_blend": [vp, vp, vp, lg, ip, fl, lg, vp, vp],
+        "ug_op_time_conv_out": [vp, vp, vp, vp, ip, lg, ip, lg, vp], "ug_op_depth_post": [vp, vp, lg, lg, vp, vp, vp],
+        "ug_op_add_grid_nearest": [vp, vp, ip, ip, ip, ip, ip, lg, vp], "ug_op_sn_normals_out": [vp, vp, ip, lg, lg, vp],
+        "ug_op_clip_assemble": [vp, vp, vp, vp, ip, ip, ip, lg, vp]})
     lib.ug_bind_stablenormal.argtypes = [vp, C.POINTER(UNetConfigC), C.POINTER(VAEConfigC), C.POINTER(CLIPConfigC)]
     lib.ug_sn_run.argtypes = [vp, vp, ip, ip, ip, vp, C.c_float, ip, vp, vp, vp, vp]
     lib.ug_sn_unet_forward.argtypes = [vp, ip, vp, vp, ip, ip, ip, C.c_float, C.c_float, vp, vp, ip, vp]
@@ -1209,6 +1219,96 @@ class Engine:
         v = _f32(v); l = _f32(lat).copy()
         self._ck(self.lib.ug_op_euler_step(self.ctx, _ptr(v), _ptr(l), l.size, sigma, sigma_next))
         return l
+
+    # the pipeline glue of kernels/misc.hip one launch at a time (tests/test_glue_gpu.py).  Every output is a new array of the whole device buffer:
+    # guard extra rows (or elements) filled with `fill` before the launch - an fp16-representable value where the buffer is fp16 on the device.
+    @staticmethod
+    def _out(shape, fill):
+        return np.full(shape, fill, np.float32)
+
+    def op_clip_patchify(self, video_m11, S, P, Kpad, imagenet_norm=False, guard=0, fill=-777.0):
+        """video_m11 [T,H,W,3] -> [T*(S/P)^2 + guard, Kpad]; columns [3*P*P, Kpad) keep `fill`."""
+        v = _f32(video_m11); T, H, W, _ = v.shape
+        out = self._out((T * (S // P) ** 2 + guard, Kpad), fill)
+        self._ck(self.lib.ug_op_clip_patchify(self.ctx, _ptr(v), T, H, W, S, P, Kpad, int(bool(imagenet_norm)), int(guard), _ptr(out)))
+        return out
+
+    def op_prep_video(self, frames, noise, aug, guard=0, fill=-777.0):
+        """frames [T,H,W,3], noise [T,3,H,W] -> (clip_src [T*H*W + guard, 3], vae_in [T*H*W + guard, 8])."""
+        f, nz = _f32(frames), _f32(noise); T, H, W, _ = f.shape
+        assert nz.shape == (T, 3, H, W), nz.shape
+        src = self._out((T * H * W + guard, 3), fill); vin = self._out((T * H * W + guard, 8), fill)
+        self._ck(self.lib.ug_op_prep_video(self.ctx, _ptr(f), _ptr(nz), T, H, W, float(aug), int(guard), _ptr(src), _ptr(vin)))
+        return src, vin
+
+    def op_init_latents(self, noise_tchw, sigma0, guard=0, fill=-777.0):
+        """noise [T,4,h,w] -> latents [T*h*w + guard, 4] (channels-last)."""
+        nz = _f32(noise_tchw); T, ch, h, w = nz.shape
+        assert ch == 4, nz.shape
+        lat = self._out((T * h * w + guard, 4), fill)
+        self._ck(self.lib.ug_op_init_latents(self.ctx, _ptr(nz), T, h * w, float(sigma0), int(guard), _ptr(lat)))
+        return lat
+
+    def op_unet_input(self, lat, cond, den, guided=False, guard=0, fill=-777.0):
+        """lat, cond [pixels,4] -> [pixels + guard, 8]; guided: [2*pixels + guard, 8], conditional video first."""
+        l, cn = _f32(lat), _f32(cond); px = l.shape[0]
+        assert l.shape == cn.shape == (px, 4), (l.shape, cn.shape)
+        out = self._out(((2 if guided else 1) * px + guard, 8), fill)
+        self._ck(self.lib.ug_op_unet_input(self.ctx, _ptr(l), _ptr(cn), px, float(den), int(bool(guided)), int(guard), _ptr(out)))
+        return out
+
+    def op_euler_step_cfg(self, vc, vu, g, lat, sigma, sigma_next, guard=0, fill=-777.0):
+        a, b, l = _f32(vc).ravel(), _f32(vu).ravel(), _f32(lat).ravel()
+        assert a.size == b.size == l.size
+        out = np.concatenate([l, self._out(guard, fill)])
+        self._ck(self.lib.ug_op_euler_step_cfg(self.ctx, _ptr(a), _ptr(b), float(g), l.size, float(sigma), float(sigma_next), int(guard), _ptr(out)))
+        return out
+
+    def op_window_blend(self, prev, cur, overlap, coef, guard=0, fill=-777.0):
+        """prev, cur [overlap, frame_elems]: (prev + coef * cur, the cross-fade of cur into prev), each [overlap * frame_elems + guard]."""
+        p, cu = _f32(prev), _f32(cur)
+        assert p.shape == cu.shape and p.shape[0] == overlap, (p.shape, cu.shape)
+        rn = np.concatenate([cu.ravel(), self._out(guard, fill)]); fd = np.concatenate([p.ravel(), self._out(guard, fill)])
+        self._ck(self.lib.ug_op_window_blend(self.ctx, _ptr(p), _ptr(cu), p.shape[1], int(overlap), float(coef), int(guard), _ptr(rn), _ptr(fd)))
+        return rn, fd
+
+    def op_time_conv_out(self, x, w, b, guard=0, fill=-777.0):
+        """x [T,HW,Cs], w [3,3,3] (out, in, tap), b [3] -> [T*HW + guard, 3] float32."""
+        xa, wa, ba = _f32(x), _f32(w), _f32(b); T, HW, Cs = xa.shape
+        assert wa.shape == (3, 3, 3) and ba.shape == (3,)
+        out = self._out((T * HW + guard, 3), fill)
+        self._ck(self.lib.ug_op_time_conv_out(self.ctx, _ptr(xa), _ptr(wa), _ptr(ba), T, HW, Cs, int(guard), _ptr(out)))
+        return out
+
+    def op_depth_post(self, frames, guard=0, fill=-777.0):
+        """frames [n,3] -> (depth [n + guard], disparity [n + guard], (min, max) decoded from the ordered-integer words)."""
+        f = _f32(frames); n = f.shape[0]
+        depth = self._out(n + guard, fill); disp = self._out(n + guard, fill); mm = np.zeros(2, np.float32)
+        self._ck(self.lib.ug_op_depth_post(self.ctx, _ptr(f), n, int(guard), _ptr(depth), _ptr(disp), _ptr(mm)))
+        return depth, disp, mm
+
+    def op_add_grid_nearest(self, x, grid, guard=0, fill=-777.0):
+        """x [B,h,w,C] += grid [B,g,g,C] gathered at (y*g // h, x*g // w) -> [B*h*w + guard, C]."""
+        xa, ga = _f32(x), _f32(grid); B, h, w, Cc = xa.shape; g = ga.shape[1]
+        assert ga.shape == (B, g, g, Cc), ga.shape
+        out = np.concatenate([xa.reshape(-1, Cc), self._out((guard, Cc), fill)])
+        self._ck(self.lib.ug_op_add_grid_nearest(self.ctx, _ptr(ga), B, h, w, g, Cc, int(guard), _ptr(out)))
+        return out
+
+    def op_sn_normals_out(self, dec, guard=0, fill=-777.0):
+        """dec [pixels, ldd] -> [pixels + guard, 3] float32."""
+        d = _f32(dec); px, ldd = d.shape
+        out = self._out((px + guard, 3), fill)
+        self._ck(self.lib.ug_op_sn_normals_out(self.ctx, _ptr(d), ldd, px, int(guard), _ptr(out)))
+        return out
+
+    def op_clip_assemble(self, patches, cls, pos, T, guard=0, fill=-777.0):
+        """patches [T*np, d], cls [d], pos [np+1, d] -> tokens [T*(np+1) + guard, d]."""
+        p, cl, po = _f32(patches), _f32(cls), _f32(pos); d = p.shape[1]; npp = p.shape[0] // T
+        assert p.shape == (T * npp, d) and cl.shape == (d,) and po.shape == (npp + 1, d), (p.shape, cl.shape, po.shape)
+        out = self._out((T * (npp + 1) + guard, d), fill)
+        self._ck(self.lib.ug_op_clip_assemble(self.ctx, _ptr(p), _ptr(cl), _ptr(po), T, npp, d, int(guard), _ptr(out)))
+        return out
 
     def bench_gemm(self, M=0, N=0, K=0, conv=None, cfg=-1, split=0, iters=20):
         """conv = dict(T,H,W,C0,C1,kt,k,stride,ups) or None (dense).  Returns (ms, TFLOP/s, cfg, split)."""

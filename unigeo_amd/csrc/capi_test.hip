@@ -929,6 +929,156 @@ int ug_op_u8_to_frames(ug_ctx* x, const unsigned char* frames_tchw, int T, int H
   });
 }
 
+// ---- the pipeline glue of kernels/misc.hip one launch at a time (tests/test_glue_gpu.py).  Each entry calls the product's launch_* on the context's
+// stream and nothing else; every output buffer goes to the device as the caller gives it, guard rows included, and all of it comes back.
+static float* up32g(Ctx& c, const float* h, long n) {      // float32 host -> float32 device, as given
+  float* d = c.ws.get<float>(n);
+  UG_CHECK(hipMemcpy(d, h, (size_t)n * 4, hipMemcpyHostToDevice));
+  return d;
+}
+static void down32g(Ctx& c, const float* d, float* h, long n) {
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  UG_CHECK(hipMemcpy(h, d, (size_t)n * 4, hipMemcpyDeviceToHost));
+}
+int ug_op_clip_patchify(ug_ctx* x, const float* video_m11, int T, int H, int W, int S, int P, int Kpad, int imagenet_norm, long guard, float* out_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && H >= 1 && W >= 1 && S >= 1 && P >= 1 && S % P == 0 && Kpad >= 3 * P * P && guard >= 0 && video_m11 && out_inout, "clip patchify shape");
+    const long rows = (long)T * (S / P) * (S / P);
+    const f16* src = up16(c, video_m11, (long)T * H * W * 3);
+    f16* out = up16(c, out_inout, (rows + guard) * Kpad);
+    launch_clip_patchify(src, out, T, H, W, S, P, Kpad, c.stream, imagenet_norm);
+    UG_CHECK(hipGetLastError());
+    down16(c, out, out_inout, (rows + guard) * Kpad);
+  });
+}
+int ug_op_prep_video(ug_ctx* x, const float* frames, const float* noise, int T, int H, int W, float aug, long guard, float* clip_src_inout, float* vae_in_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && H >= 1 && W >= 1 && guard >= 0 && frames && noise && clip_src_inout && vae_in_inout, "prep video shape");
+    const long px = (long)T * H * W;
+    const float* df = up32g(c, frames, px * 3); const float* dn = up32g(c, noise, px * 3);
+    f16* src = up16(c, clip_src_inout, (px + guard) * 3); f16* vin = up16(c, vae_in_inout, (px + guard) * 8);
+    launch_prep_video(df, dn, src, vin, T, H, W, aug, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, src, clip_src_inout, (px + guard) * 3); down16(c, vin, vae_in_inout, (px + guard) * 8);
+  });
+}
+int ug_op_init_latents(ug_ctx* x, const float* noise_tchw, int T, long hw, float sigma0, long guard, float* lat_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && hw >= 1 && guard >= 0 && noise_tchw && lat_inout, "init latents shape");
+    const long px = (long)T * hw;
+    const float* dn = up32g(c, noise_tchw, px * 4);
+    f16* lat = up16(c, lat_inout, (px + guard) * 4);
+    launch_init_latents2(dn, lat, sigma0, T, hw, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, lat, lat_inout, (px + guard) * 4);
+  });
+}
+int ug_op_unet_input(ug_ctx* x, const float* lat, const float* cond, long pixels, float den, int guided, long guard, float* x_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pixels >= 1 && guard >= 0 && lat && cond && x_inout, "unet input shape");
+    const long rows = (guided ? 2 : 1) * pixels + guard;
+    const f16* dl = up16(c, lat, pixels * 4); const f16* dc = up16(c, cond, pixels * 4);
+    f16* xin = up16(c, x_inout, rows * 8);
+    if (guided) launch_make_unet_input_cfg(dl, dc, xin, pixels, den, c.stream);
+    else launch_make_unet_input(dl, dc, xin, pixels, den, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, xin, x_inout, rows * 8);
+  });
+}
+int ug_op_euler_step_cfg(ug_ctx* x, const float* vc, const float* vu, float g, long n, float sigma, float sigma_next, long guard, float* lat_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(n >= 1 && guard >= 0 && vc && vu && lat_inout, "guided euler step shape");
+    const f16* dc = up16(c, vc, n); const f16* du = up16(c, vu, n);
+    f16* dl = up16(c, lat_inout, n + guard);
+    launch_euler_step_cfg(dc, du, g, dl, n, sigma, sigma_next, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, dl, lat_inout, n + guard);
+  });
+}
+int ug_op_window_blend(ug_ctx* x, const float* prev, const float* cur, long frame_elems, int overlap, float coef, long guard,
+                       float* renoised_inout, float* faded_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(frame_elems >= 1 && overlap >= 1 && guard >= 0 && prev && cur && renoised_inout && faded_inout, "window blend shape");
+    const long n = frame_elems * overlap;
+    const f16* dp = up16(c, prev, n); const f16* dc = up16(c, cur, n);
+    f16* rn = up16(c, renoised_inout, n + guard); f16* fd = up16(c, faded_inout, n + guard);
+    launch_axpby_f16(dp, 1.f, rn, coef, rn, n, c.stream);
+    launch_crossfade_f16(dc, fd, frame_elems, overlap, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, rn, renoised_inout, n + guard); down16(c, fd, faded_inout, n + guard);
+  });
+}
+int ug_op_time_conv_out(ug_ctx* x, const float* xin, const float* w, const float* b, int T, long HW, int Cs, long guard, float* out_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && HW >= 1 && Cs >= 3 && guard >= 0 && xin && w && b && out_inout, "time conv out shape");
+    const long px = (long)T * HW;
+    const f16* dx = up16(c, xin, px * Cs); const f16* dw = up16(c, w, 27); const f16* db = up16(c, b, 3);
+    float* out = up32g(c, out_inout, (px + guard) * 3);
+    launch_time_conv_out(dx, dw, db, out, T, HW, Cs, c.stream);
+    down32g(c, out, out_inout, (px + guard) * 3);
+  });
+}
+int ug_op_depth_post(ug_ctx* x, const float* frames, long n, long guard, float* depth_inout, float* disp_inout, float* minmax_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(n >= 1 && guard >= 0 && frames && depth_inout && disp_inout && minmax_out, "depth post shape");
+    const float* df = up32g(c, frames, n * 3);
+    float* dd = up32g(c, depth_inout, n + guard); float* dx = up32g(c, disp_inout, n + guard);
+    float* mm = c.ws.get<float>(2);
+    launch_depth_post(df, dd, mm, n, c.stream);
+    launch_disparity_from_frames(df, mm, dx, n, c.stream);
+    down32g(c, dd, depth_inout, n + guard); down32g(c, dx, disp_inout, n + guard);
+    unsigned u[2];
+    UG_CHECK(hipMemcpy(u, mm, 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 2; ++i) {      // the ordered-integer words back to float (ord2f of kernels/misc.hip)
+      const unsigned bits = (u[i] & 0x80000000u) ? (u[i] & 0x7fffffffu) : ~u[i];
+      memcpy(&minmax_out[i], &bits, 4);
+    }
+  });
+}
+int ug_op_add_grid_nearest(ug_ctx* x, const float* grid, int B, int h, int w, int g, int C, long guard, float* x_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(B >= 1 && h >= 1 && w >= 1 && g >= 1 && C >= 8 && C % 8 == 0 && guard >= 0 && grid && x_inout, "add grid shape");
+    const long px = (long)B * h * w;
+    const f16* dg = up16(c, grid, (long)B * g * g * C);
+    f16* dx = up16(c, x_inout, (px + guard) * C);
+    launch_add_grid_nearest(dx, dg, B, h, w, g, C, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, dx, x_inout, (px + guard) * C);
+  });
+}
+int ug_op_sn_normals_out(ug_ctx* x, const float* dec, int ldd, long pixels, long guard, float* out_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(pixels >= 1 && ldd >= 3 && guard >= 0 && dec && out_inout, "normals out shape");
+    const f16* dd = up16(c, dec, pixels * ldd);
+    float* out = up32g(c, out_inout, (pixels + guard) * 3);
+    launch_sn_normals_out(dd, ldd, out, pixels, c.stream);
+    down32g(c, out, out_inout, (pixels + guard) * 3);
+  });
+}
+int ug_op_clip_assemble(ug_ctx* x, const float* patches, const float* cls, const float* pos, int T, int np, int d, long guard, float* tok_inout) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(T >= 1 && np >= 1 && d >= 1 && guard >= 0 && patches && cls && pos && tok_inout, "clip assemble shape");
+    const long rows = (long)T * (np + 1);
+    const f16* dp = up16(c, patches, (long)T * np * d); const f16* dc = up16(c, cls, d); const f16* dq = up16(c, pos, (long)(np + 1) * d);
+    f16* tok = up16(c, tok_inout, (rows + guard) * d);
+    launch_clip_assemble(dp, dc, dq, tok, T, np, d, c.stream);
+    UG_CHECK(hipGetLastError());
+    down16(c, tok, tok_inout, (rows + guard) * d);
+  });
+}
+
 // ------------------------------------------------------------------ micro-benchmarks on device-resident pseudo-random data
 int ug_bench_flash(ug_ctx* x, int B, int H, int S, int variant, int iters, float* us_out) {
   UG_TRY(x, {

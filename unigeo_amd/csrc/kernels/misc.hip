@@ -179,12 +179,13 @@ __device__ __forceinline__ void cubic_w(float t, float (&w)[4]) {
   x = 1.f - t;       w[2] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
   x = 2.f - t;       w[3] = ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
 }
-struct Norm3 { float mean[3], stdv[3]; };
+// mean and 1 / std of the float32 constants, in double: the normalisation is evaluated in double and rounded once, so that without a resize
+// (scale 1, where blur and bicubic are exact) the stored value is the correctly rounded fp16 of ((v + 1) / 2 - mean) / std
+struct Norm3 { double mean[3], istd[3]; };
 __global__ void k_clip_patchify(const f16* src, f16* patches, int T, int H, int W, int S224, int P, int Kpad,
                                 BlurTaps bt, Norm3 nm) {
   const long n = (long)T * S224 * S224;
   const int np = S224 / P;
-  const float* mean = nm.mean; const float* stdv = nm.stdv;
   GS_LOOP(idx, n) {
     const int ox = idx % S224, oy = (idx / S224) % S224;
     const long t = idx / ((long)S224 * S224);
@@ -218,7 +219,7 @@ __global__ void k_clip_patchify(const f16* src, f16* patches, int T, int H, int 
     f16* dst = patches + ((t * np + pr) * np + pcx) * (long)Kpad;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float v = ((acc[c] + 1.0f) * 0.5f - mean[c]) / stdv[c];
+      const double v = (((double)acc[c] + 1.0) * 0.5 - nm.mean[c]) * nm.istd[c];
       dst[c * P * P + py * P + px] = (f16)v;
     }
   }
@@ -235,11 +236,18 @@ static void gauss_taps(int src, int dst, int& ks, float* g) {
 }
 void launch_clip_patchify(const f16* video_m11, f16* patches, int T, int H, int W, int S224, int P, int Kpad,
                           hipStream_t s, int imagenet_norm) {
-  const Norm3 nm = imagenet_norm ? Norm3{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}}
-                                 : Norm3{{0.48145466f, 0.4578275f, 0.40821073f}, {0.26862954f, 0.26130258f, 0.27577711f}};
+  const float in_mean[3] = {0.485f, 0.456f, 0.406f}, in_std[3] = {0.229f, 0.224f, 0.225f};
+  const float cl_mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, cl_std[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+  Norm3 nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.mean[c] = imagenet_norm ? in_mean[c] : cl_mean[c];
+    nm.istd[c] = 1.0 / (double)(imagenet_norm ? in_std[c] : cl_std[c]);
+  }
   BlurTaps bt;
   gauss_taps(H, S224, bt.ky, bt.gy);
   gauss_taps(W, S224, bt.kx, bt.gx);
+  // reflect_idx folds once: a border of ks / 2 pixels needs more than ks / 2 rows and columns (torch refuses reflect padding that large as well)
+  UG_REQUIRE(H > bt.ky / 2 && W > bt.kx / 2, "antialias kernel: the reflect border needs H, W > taps / 2");
   hipLaunchKernelGGL(k_clip_patchify, gs_grid((long)T * S224 * S224), dim3(256), 0, s, video_m11, patches, T, H, W,
                      S224, P, Kpad, bt, nm);
 }
@@ -352,8 +360,10 @@ void launch_make_unet_input(const f16* lat, const f16* cond, f16* x, long pixels
 
 // Euler step, v-prediction (diffusers EulerDiscreteScheduler.step with s_churn = 0):
 //   x0 = v * (-sigma / sqrt(sigma^2+1)) + x / (sigma^2+1);  x <- x + (x - x0)/sigma * (sigma_next - sigma)
-// the product v*c is rounded to fp16 first (v stays fp16 in the reference while x is upcast).
+// the product v*c is rounded to fp16 first (v stays fp16 in the reference while x is upcast).  No contraction: the reference rounds der * dt
+// before the sum, and where x + der * dt cancels a fused multiply-add lands several fp16 steps away from it.
 __global__ void k_euler_step(const f16* v, f16* lat, long n, float sigma, float sigma_next) {
+#pragma clang fp contract(off)
   const float c = -sigma / sqrtf(sigma * sigma + 1.f);
   const float d2 = sigma * sigma + 1.f;
   const float dt = sigma_next - sigma;
@@ -386,15 +396,19 @@ void launch_make_unet_input_cfg(const f16* lat, const f16* cond, f16* x, long pi
   hipLaunchKernelGGL(k_make_unet_input_cfg, gs_grid(pixels), dim3(256), 0, s, lat, cond, x, pixels, den);
 }
 
-// Guided Euler step: v = v_u + g (v_c - v_u) in fp32 registers, rounded to fp16 (the reference's noise_pred is an fp16 tensor), then
-// exactly k_euler_step.  One pass over v_c, v_u and the latents instead of three elementwise launches.
+// Guided Euler step: v = v_u + g (v_c - v_u) with the difference, the product and the sum each rounded to fp16 (the reference forms
+// noise_pred with three fp16 tensor operations; g stays float32, as a Python scalar does on the device), then exactly k_euler_step.
+// One pass over v_c, v_u and the latents instead of three elementwise launches.
 __global__ void k_euler_step_cfg(const f16* vc, const f16* vu, float g, f16* lat, long n, float sigma, float sigma_next) {
+#pragma clang fp contract(off)
   const float c = -sigma / sqrtf(sigma * sigma + 1.f);
   const float d2 = sigma * sigma + 1.f;
   const float dt = sigma_next - sigma;
   GS_LOOP(i, n) {
     const float u = (float)vu[i];
-    const float v = (float)(f16)(u + g * ((float)vc[i] - u));
+    const float dv = (float)(f16)((float)vc[i] - u);
+    const float gd = (float)(f16)(g * dv);
+    const float v = (float)(f16)(u + gd);
     const float x = (float)lat[i];
     const float vcs = (float)(f16)(v * c);
     const float x0 = vcs + x / d2;
