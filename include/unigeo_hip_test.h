@@ -110,6 +110,23 @@ int ug_op_flash_cross_attn(ug_ctx* ctx, const float* q, const float* kv, int B, 
 int ug_op_temporal_attn_nv(ug_ctx* ctx, const float* qkv, int nv, int T, int HW, int H, float* out);
 int ug_op_attention_generic(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);
 int ug_op_flash_attn_dh(ug_ctx* ctx, const float* qkv /*[B*S,3*H*d]*/, int B, int S, int H, int d, float* out);   /* fused self-attention, head dim d in {32,48,80,96,112,128}: the CLIP tower's 16 x 80 heads */
+/* The same two paths with the conventions of ug_op_flash_cross_attn (tests/test_attn_general_gpu.py): qkv [B*S + guard, ld] with
+ * Q | K | V in columns [0, 3*H*d), out_inout [B*S + guard, ldo]; both go to the device as given - guard rows, surplus columns and the caller's contents of
+ * out_inout included - and all of out_inout comes back.  ld >= 3*H*d, ldo >= H*d, ld % 8 == 0, ldo % 4 == 0, a supported d, else an error that leaves
+ * the context usable.  ug_op_flash_attn_dh_ex calls launch_flash_attn_dh; ug_op_attention_generic_ex the four launches of the engine's
+ * unfused_attention (d % 8 == 0), plan_out [4] (may be NULL) = the planner's (tile config, split factor) of the Q K^T and of the P V batched GEMM.
+ * The two entries above are these with tight buffers (ld = 3*H*d, ldo = H*d, no guard). */
+int ug_op_flash_attn_dh_ex(ug_ctx* ctx, const float* qkv, int B, int S, int H, int d, long ld, long ldo, long guard, float* out_inout);
+int ug_op_attention_generic_ex(ug_ctx* ctx, const float* qkv, int B, int S, int H, int d, long ld, long ldo, long guard, float* out_inout, int* plan_out /*[4]*/);
+/* One batched GEMM through the engine's run_gemm with exactly the fields unfused_attention fills: Out[b] = c0 * A[b] W[b]^T for b < batch, no bias;
+ * batch b = (bo, bi) = (b / nb_inner, b % nb_inner) sits at element offset bo * s?_o + bi * s?_i of its buffer.  A [M,K] rows of lda and W [N,K] rows
+ * of ldw are fp16 on the device (a_elems / w_elems floats on the host); the output [M,N] rows of ldo is float32 (out_f32 != 0: UG_F_OUT_F32) or fp16.
+ * out_inout holds o_elems floats, goes to the device as given and comes back whole.  The entry checks on the host that the last element every batch
+ * addresses lies inside the three buffers (else an error) and honours ug_tune_force as run_gemm does; plan_out [2] (may be NULL) = the (tile config,
+ * split factor) launched. */
+int ug_op_gemm_batched(ug_ctx* ctx, const float* A, long lda, long sA_o, long sA_i, const float* W, long ldw, long sW_o, long sW_i, int M, int N, int K,
+                       int batch, int nb_inner, float c0, int out_f32, long ldo, long sO_o, long sO_i, long a_elems, long w_elems, long o_elems,
+                       float* out_inout, int* plan_out /*[2]*/);
 int ug_op_euler_step(ug_ctx* ctx, const float* v, float* latents_inout, long n, float sigma, float sigma_next);
 /* The pipeline glue of kernels/misc.hip one launch at a time (tests/test_glue_gpu.py).  Each entry calls the product's own
  * launcher on the context's stream and nothing else.  Host in / host out in float32; what the device holds as fp16 is rounded on the way in (the tests

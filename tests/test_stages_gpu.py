@@ -44,6 +44,38 @@ def test_clip_embed(tiny):
     assert_close(got, ref, 2.5e-3, "CLIP image embedding")
 
 
+def test_clip_embed_heads_of_80_fused_and_four_launch():
+    """The tiny tower has two heads of 32; this one has the real tower's head dim - hidden 160 = 2 heads of 80, 2 layers, S = 257 tokens, 2 frames - so
+    that flash_attn_dh_kernel<80> runs inside clip_embed, and with UG_CLIP_UNFUSED (read per call) the four-launch path it replaced.  Both against the
+    oracle's tower at test_clip_embed's bound, and against each other."""
+    import os
+    from oracle.clip import clip_preprocess
+    from unigeo_amd import weights as W
+    from unigeo_amd._lib import Engine
+    c = W.CLIPCfg(hidden_size=160, intermediate_size=320, num_hidden_layers=2, num_attention_heads=2, image_size=224, patch_size=14, projection_dim=48)
+    sc = W.random_state(W.clip_manifest(c), 5)
+    frames = h16(np.random.default_rng(5).uniform(0, 1, (2, 64, 96, 3)))
+    with torch.no_grad():
+        ref = oracle_clip(c, sc)(clip_preprocess(torch.from_numpy(frames).permute(0, 3, 1, 2) * 2.0 - 1.0)).numpy()
+    eng = Engine(0, workspace_bytes=1 << 30, persist_bytes=256 << 20)
+    try:
+        eng.load_state("clip.", sc); eng.bind_clip(c)
+        assert "UG_CLIP_UNFUSED" not in os.environ
+        fused = eng.clip_embed(frames)
+        os.environ["UG_CLIP_UNFUSED"] = "1"
+        try:
+            unfused = eng.clip_embed(frames)
+        finally:
+            del os.environ["UG_CLIP_UNFUSED"]
+        assert np.array_equal(eng.clip_embed(frames), fused)      # the variable is read per call, and the kernels are deterministic
+    finally:
+        eng.close()
+    assert_close(fused, ref, 2.5e-3, "CLIP image embedding, 2 heads of 80, fused attention")
+    assert_close(unfused, ref, 2.5e-3, "CLIP image embedding, 2 heads of 80, four-launch attention")
+    assert_close(fused, unfused, 2.5e-3, "CLIP image embedding, 2 heads of 80, fused vs four-launch attention")
+    assert not np.array_equal(fused, unfused)      # really two paths
+
+
 def test_vae_encode(tiny):
     """Default = the reference's float32 encoder (force_upcast): fp32-grade arithmetic on fp16 hi/lo activation pairs
     (kernels/wide.hip); the output is the pipeline's fp16 latent, so the floor is one fp16 rounding (2^-11 = 4.9e-4)."""

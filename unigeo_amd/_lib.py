@@ -23,7 +23,7 @@ EXPORTS = [
     "ug_eval_depth", "ug_eval_normal", "ug_depth_eval_opts_default", "ug_eval_depth_ex", "ug_eval_depth_global", "ug_op_masked_median", "ug_eval_depth_l1_info", "ug_op_l1_fit", "ug_depth_eval_opts2_default", "ug_eval_depth_ex2", "ug_dc_get_disparity", "ug_clip_embed", "ug_vae_encode", "ug_vae_decode", "ug_unet_forward", "ug_normals_from_depth",
     "ug_op_linear", "ug_op_conv", "ug_op_conv_gn", "ug_op_groupnorm", "ug_op_layernorm", "ug_op_flash_attn",
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
-    "ug_op_groupnorm_ex", "ug_op_layernorm_ex",
+    "ug_op_groupnorm_ex", "ug_op_layernorm_ex", "ug_op_flash_attn_dh_ex", "ug_op_attention_generic_ex", "ug_op_gemm_batched",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
     "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex",
     "ug_op_clip_patchify", "ug_op_prep_video", "ug_op_init_latents", "ug_op_unet_input", "ug_op_euler_step_cfg", "ug_op_window_blend",
@@ -202,6 +202,10 @@ def load_library():
     lib.ug_op_euler_step.argtypes = [vp, vp, vp, C.c_long, C.c_float, C.c_float]
     _set_argtypes(lib, {"ug_op_flash_cross_attn": [vp, vp, vp, ip, ip, ip, ip, ip, C.c_long, C.c_long, C.c_long, C.c_long, vp],
                         "ug_op_temporal_attn_nv": [vp, vp, ip, ip, ip, ip, vp]})
+    _set_argtypes(lib, {"ug_op_flash_attn_dh_ex": [vp, vp, ip, ip, ip, ip, C.c_long, C.c_long, C.c_long, vp],
+                        "ug_op_attention_generic_ex": [vp, vp, ip, ip, ip, ip, C.c_long, C.c_long, C.c_long, vp, vp],
+                        "ug_op_gemm_batched": [vp, vp, C.c_long, C.c_long, C.c_long, vp, C.c_long, C.c_long, C.c_long, ip, ip, ip, ip, ip, C.c_float, ip,
+                                               C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, vp, vp]})
     _set_argtypes(lib, {"ug_op_groupnorm_ex": [vp, vp, ip, vp, ip, ip, ip, ip, C.c_float, ip, ip, vp, vp, ip, C.c_long, vp, vp],
                         "ug_op_layernorm_ex": [vp, vp, ip, ip, C.c_float, vp, vp, vp, ip, C.c_long, ip, C.c_long, vp, vp, vp, vp, vp]})
     _set_argtypes(lib, {
@@ -1156,6 +1160,38 @@ class Engine:
         q = _f32(qkv); out = np.empty((B * S, H * d), np.float32)
         self._ck(self.lib.ug_op_flash_attn_dh(self.ctx, _ptr(q), B, S, H, d, _ptr(out)))
         return out
+
+    # the attention paths for head dims other than 64 and the batched GEMMs under the four-launch one (tests/test_attn_general_gpu.py)
+    def _attn_general_buffers(self, qkv, out_inout, B, S, guard):
+        q, out = _f32(qkv), np.array(out_inout, dtype=np.float32, order="C")
+        assert q.ndim == out.ndim == 2 and q.shape[0] == out.shape[0] == B * S + guard, (q.shape, out.shape)
+        return q, out
+
+    def op_flash_attn_dh_ex(self, qkv, out_inout, B, S, H, d, guard=0):
+        """The fused self-attention for head dims other than 64.  qkv [B*S + guard, ld] with Q | K | V in columns [0, 3*H*d), out_inout [B*S + guard, ldo]:
+        both are uploaded as they are (guard rows and surplus columns too) and a new array with the device's whole out_inout is returned."""
+        q, out = self._attn_general_buffers(qkv, out_inout, B, S, guard)
+        self._ck(self.lib.ug_op_flash_attn_dh_ex(self.ctx, _ptr(q), B, S, H, d, q.shape[1], out.shape[1], int(guard), _ptr(out)))
+        return out
+
+    def op_attention_generic_ex(self, qkv, out_inout, B, S, H, d, guard=0):
+        """The four-launch attention (Q K^T batched GEMM, row softmax, V transpose, P V batched GEMM) on the same buffers.  Returns (out as the device
+        holds it, plan) with plan = ((tile config, split factor) of Q K^T, ... of P V)."""
+        q, out = self._attn_general_buffers(qkv, out_inout, B, S, guard)
+        plan = (C.c_int * 4)()
+        self._ck(self.lib.ug_op_attention_generic_ex(self.ctx, _ptr(q), B, S, H, d, q.shape[1], out.shape[1], int(guard), _ptr(out), plan))
+        return out, ((plan[0], plan[1]), (plan[2], plan[3]))
+
+    def op_gemm_batched(self, A, lda, sA, W, ldw, sW, M, N, K, batch, nb_inner, out_inout, ldo, sO, c0=1.0, out_f32=True):
+        """One batched GEMM as the four-launch attention runs its two: Out[b] = c0 * A[b] W[b]^T, batch b at element offset (b // nb_inner) * s[0] +
+        (b % nb_inner) * s[1] of the flat buffers A, W (fp16 on the device) and out_inout (float32 or fp16 on the device; uploaded as given, returned
+        whole).  Returns (out, (tile config, split factor))."""
+        A, W, out = _f32(A).ravel(), _f32(W).ravel(), np.array(out_inout, dtype=np.float32, order="C").ravel()
+        plan = (C.c_int * 2)()
+        self._ck(self.lib.ug_op_gemm_batched(self.ctx, _ptr(A), int(lda), int(sA[0]), int(sA[1]), _ptr(W), int(ldw), int(sW[0]), int(sW[1]), M, N, K,
+                                             batch, nb_inner, c0, int(bool(out_f32)), int(ldo), int(sO[0]), int(sO[1]), A.size, W.size, out.size,
+                                             _ptr(out), plan))
+        return out, (plan[0], plan[1])
 
     # the float32-grade VAE encoder's kernels: float32 in / out, inputs not rounded to fp16 (tests/test_wide_gpu.py)
     def op_split_pair(self, x):

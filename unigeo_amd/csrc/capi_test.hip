@@ -730,25 +730,80 @@ int ug_op_temporal_attn_nv(ug_ctx* x, const float* qkv, int nv, int T, int HW, i
   });
 }
 
-int ug_op_attention_generic(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
+// The two attention paths for head dims other than 64 on packed qkv [B*S + guard, ld] (Q | K | V in columns [0, 3*H*d)) with the conventions of
+// ug_op_flash_cross_attn: everything the caller hands over goes to the device as given and all of out_inout [B*S + guard, ldo] comes back.
+static void attn_general_shape(int B, int S, int H, int d, long ld, long ldo, long guard, const float* qkv, const float* out) {
+  UG_REQUIRE(B >= 1 && S >= 1 && H >= 1 && d >= 1 && guard >= 0 && qkv && out, "attention shape");
+  UG_REQUIRE(ld >= 3L * H * d && ldo >= (long)H * d, "attention: rows narrower than the heads");
+  UG_REQUIRE(ld % 8 == 0 && ldo % 4 == 0, "attention strides");
+}
+
+int ug_op_attention_generic_ex(ug_ctx* x, const float* qkv, int B, int S, int H, int d, long ld, long ldo, long guard, float* out_inout, int* plan_out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
-    const int C = H * d; const long M = (long)B * S;
-    f16* dq = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
-    test_unfused_attention(c, dq, 3 * C, B, S, H, d, o, C);
-    down16(c, o, out, M * C);
+    attn_general_shape(B, S, H, d, ld, ldo, guard, qkv, out_inout);
+    UG_REQUIRE(d % 8 == 0, "unfused attention: head dim a multiple of 8");
+    const long rows = (long)B * S + guard;
+    f16* dq = up16(c, qkv, rows * ld); f16* o = up16(c, out_inout, rows * ldo);
+    std::vector<int> plan;
+    test_unfused_attention(c, dq, ld, B, S, H, d, o, ldo, &plan);
+    down16(c, o, out_inout, rows * ldo);
+    if (plan_out) for (int i = 0; i < 4; ++i) plan_out[i] = i < (int)plan.size() ? plan[i] : -1;
   });
 }
 
-int ug_op_flash_attn_dh(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
+int ug_op_flash_attn_dh_ex(ug_ctx* x, const float* qkv, int B, int S, int H, int d, long ld, long ldo, long guard, float* out_inout) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
-    const int C = H * d; const long M = (long)B * S;
-    f16* dq = up16(c, qkv, M * 3 * C); f16* o = c.ws.get<f16>(M * C);
-    FlashP p; p.variant = c.flash_variant; p.Q = dq; p.K = dq + C; p.V = dq + 2 * C; p.ldq = p.ldk = p.ldv = 3 * C; p.O = o; p.ldo = C; p.B = B; p.H = H; p.S = S;
+    attn_general_shape(B, S, H, d, ld, ldo, guard, qkv, out_inout);
+    const long C = (long)H * d, rows = (long)B * S + guard;
+    f16* dq = up16(c, qkv, rows * ld); f16* o = up16(c, out_inout, rows * ldo);
+    FlashP p; p.variant = c.flash_variant; p.Q = dq; p.K = dq + C; p.V = dq + 2 * C; p.ldq = p.ldk = p.ldv = ld; p.O = o; p.ldo = ldo; p.B = B; p.H = H; p.S = S;
     p.scale = 1.0f / sqrtf((float)d);
     launch_flash_attn_dh(p, d, c.stream);
-    down16(c, o, out, M * C);
+    down16(c, o, out_inout, rows * ldo);
+  });
+}
+
+int ug_op_attention_generic(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
+  return ug_op_attention_generic_ex(x, qkv, B, S, H, d, 3L * H * d, (long)H * d, 0, out, nullptr);
+}
+
+int ug_op_flash_attn_dh(ug_ctx* x, const float* qkv, int B, int S, int H, int d, float* out) {
+  return ug_op_flash_attn_dh_ex(x, qkv, B, S, H, d, 3L * H * d, (long)H * d, 0, out);
+}
+
+// One batched GEMM as unfused_attention launches its two: Out[b] = c0 * A[b] W[b]^T, batch b = (bo, bi) = (b / nb_inner, b % nb_inner) at element offsets
+// bo * s?_o + bi * s?_i of A (rows of lda), W (rows of ldw) and the output (rows of ldo; float32 with out_f32, else fp16).  The buffers have the sizes the
+// caller gives; that the last element every batch addresses lies inside them is checked here, on the host.
+static float* up32g(Ctx& c, const float* h, long n);
+static void down32g(Ctx& c, const float* d, float* h, long n);
+static void batched_extent(const char* what, long rows, long ld, long cols, int batch, int nb_inner, long s_o, long s_i, long elems) {
+  UG_REQUIRE(ld >= 0 && s_o >= 0 && s_i >= 0, what);
+  const long last = (long)((batch - 1) / nb_inner) * s_o + (long)(std::min(batch, nb_inner) - 1) * s_i + (rows - 1) * ld + cols - 1;
+  UG_REQUIRE(last < elems, what);
+}
+
+int ug_op_gemm_batched(ug_ctx* x, const float* A, long lda, long sA_o, long sA_i, const float* W, long ldw, long sW_o, long sW_i, int M, int N, int K,
+                       int batch, int nb_inner, float c0, int out_f32, long ldo, long sO_o, long sO_i, long a_elems, long w_elems, long o_elems,
+                       float* out_inout, int* plan_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(A && W && out_inout && M >= 1 && N >= 1 && K >= 1 && batch >= 1 && nb_inner >= 1 && batch % nb_inner == 0, "batched GEMM shape");
+    UG_REQUIRE(lda <= 0x7fffffffL, "batched GEMM: lda");
+    batched_extent("batched GEMM: A leaves its buffer", M, lda, K, batch, nb_inner, sA_o, sA_i, a_elems);
+    batched_extent("batched GEMM: W leaves its buffer", N, ldw, K, batch, nb_inner, sW_o, sW_i, w_elems);
+    batched_extent("batched GEMM: the output leaves its buffer", M, ldo, N, batch, nb_inner, sO_o, sO_i, o_elems);
+    f16* dA = up16(c, A, a_elems); f16* dW = up16(c, W, w_elems);
+    void* dO = out_f32 ? (void*)up32g(c, out_inout, o_elems) : (void*)up16(c, out_inout, o_elems);
+    GemmP p; memset(&p, 0, sizeof(p));
+    p.A0 = dA; p.C0 = (int)lda; p.M = M; p.N = N; p.K = K; p.W = dW; p.ldw = ldw; p.c0 = c0; p.Out = dO; p.ldo = ldo;
+    p.flags = out_f32 ? UG_F_OUT_F32 : 0;
+    p.nb_inner = nb_inner; p.sA_o = sA_o; p.sA_i = sA_i; p.sW_o = sW_o; p.sW_i = sW_i; p.sO_o = sO_o; p.sO_i = sO_i;
+    std::vector<int> plan;
+    test_run_gemm(c, p, batch, &plan);
+    if (out_f32) down32g(c, (const float*)dO, out_inout, o_elems); else down16(c, (const f16*)dO, out_inout, o_elems);
+    if (plan_out) for (int i = 0; i < 2; ++i) plan_out[i] = i < (int)plan.size() ? plan[i] : -1;
   });
 }
 

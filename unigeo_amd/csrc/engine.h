@@ -207,8 +207,11 @@ void vae_decode(Ctx& c, const f16* z, int T, int h, int w, float* frames_out);  
 f16* clip_embed(Ctx& c, const f16* video_m11, int T, int H, int W);       // [T,H,W,3] -> [T,proj]
 
 f16* vae_encode_v(Ctx& c, VAE& v, const f16* x8, int T, int H, int W, bool fp32_grade);
-// the unfused attention path (scores GEMM, softmax, value GEMM) on its own: exposed for the op-level tests
-void test_unfused_attention(Ctx& c, const f16* qkv, long ld, int B, int S, int H, int d, f16* out, long ldo);
+// the unfused attention path (scores GEMM, softmax, V transpose, value GEMM) on its own: exposed for the op-level tests.  plan (may be NULL): the
+// planner's (tile config, split factor) of the two GEMM launches, in launch order.
+void test_unfused_attention(Ctx& c, const f16* qkv, long ld, int B, int S, int H, int d, f16* out, long ldo, std::vector<int>* plan = nullptr);
+// one batched GEMM through run_gemm, as unfused_attention launches its two (op-level tests); plan as above
+void test_run_gemm(Ctx& c, const GemmP& p, int batch, std::vector<int>* plan);
 // the float32-grade VAE encoder's pieces on their own (kernels/wide.hip): exposed for the op-level tests
 // attention core of the mid block: qkv fp32 [T*S, 3C] -> ao fp32 [T*S, C] (ao may alias qkv)
 void attn_wide_core(Ctx& c, const float* qkv, int T, int S, int C, float* ao);

@@ -864,8 +864,20 @@ static void unfused_attention(Ctx& c, const f16* qkv, long ldqkv, int B, int S, 
   c.ws.release(mk);
 }
 
-void test_unfused_attention(Ctx& c, const f16* qkv, long ld, int B, int S, int H, int d, f16* out, long ldo) {
+namespace {
+struct PlanLog {   // the log leaves the context on every way out
+  Ctx& c;
+  PlanLog(Ctx& c_, std::vector<int>* v) : c(c_) { c.plan_log = v; }
+  ~PlanLog() { c.plan_log = nullptr; }
+};
+}
+void test_unfused_attention(Ctx& c, const f16* qkv, long ld, int B, int S, int H, int d, f16* out, long ldo, std::vector<int>* plan) {
+  PlanLog log(c, plan);
   unfused_attention(c, qkv, ld, B, S, H, d, out, ldo);
+}
+void test_run_gemm(Ctx& c, const GemmP& p, int batch, std::vector<int>* plan) {
+  PlanLog log(c, plan);
+  run_gemm(c, p, batch, "gemm_batched_test");
 }
 
 // ResnetBlock2D over a (virtual concat) input; out [M, cout] must be pre-allocated
@@ -1366,11 +1378,7 @@ Conv test_bind_conv(Ctx& c, const std::string& name, int cin, int cout, int kt, 
 void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
                      const f16* R1, float c0, float c1, int act, f16* out, long ldo, std::vector<int>* plan) {
   Epi e; e.R1 = R1; e.c0 = c0; e.c1 = c1; e.act = act;
-  struct Log {   // the log leaves the context on every way out
-    Ctx& c;
-    Log(Ctx& c_, std::vector<int>* v) : c(c_) { c.plan_log = v; }
-    ~Log() { c.plan_log = nullptr; }
-  } log(c, plan);
+  PlanLog log(c, plan);
   conv(c, x0, C0, x1, C1, T, H, W, cv, stride, pad_t, pad_l, ups, out, e, ldo);
 }
 // the pre-norm feed-forward of a transformer block on its own (op-level tests; engine.h): ln_ff() with the residual stream as transformer_forward hands it over
