@@ -73,6 +73,30 @@ int ug_op_linear(ug_ctx* ctx, const float* A, int M, int K, const float* W, int 
  * the quantised A bytes [M,K] and its scale dwords [K/128][round_up(M,256)] (4 e8m0 per dword) for bit-level checks. */
 int ug_op_linear_mx8(ug_ctx* ctx, const float* A, int M, int K, const float* W, int N, const float* bias, int geglu, float* out,
                      unsigned char* a8_out, unsigned* scales_out);
+/* The MX-fp8 path launch by launch (tests/test_mx8_forms_gpu.py), with the conventions of the other _ex entries: every *_inout
+ * buffer goes to the device as the caller gives it and comes back whole.  A bad call returns an error and leaves the context usable.
+ *   ug_op_quant_mx8_ex : launch_quant_mx8 alone.  x [M + guard, ldx] (fp16-representable), q_inout [M + guard, K] bytes, s_inout [K/128][ld_s] dwords with
+ *                        the caller's ld_s >= M; the bytes of the guard rows and the dwords of rows >= M return unchanged.  K % 128 == 0, ldx % 8 == 0.
+ *   ug_op_linear_mx8_ex: both quantiser launches, then launch_gemm_mx8 with the whole epilogue: out = act(c0 * f(A W^T + bias) + c1 * R1 + c2 * R2), f = GEGLU
+ *                        with geglu != 0 (N % 128 == 0; W / bias in checkpoint order, packed to the bound row order here).  R1 [M, ldr1], R2 [M, ldr2] (may be
+ *                        NULL), out_inout [M + guard, ldo]; scale areas of round_up(M,256) / round_up(N,256) rows as the engine sizes them.  poison != 0:
+ *                        the quantised bytes, both scale areas and the rest of the workspace are filled with 0xFF (e8m0 NaN) before the quantiser launches
+ *                        and nothing is zeroed, so the scale rows >= M / >= N hold what a product launch may find there.  Honours ug_tune_force(100 + pick);
+ *                        plan_out [2] (may be NULL) = (tile pick, group_m) as launched.  a8_out / sa_out as ug_op_linear_mx8, which is this entry with
+ *                        tight rows and no residual (the dwords of rows >= M are then unspecified).
+ *   ug_op_linear_engine: a Lin of W [N,K] and bias goes through the engine's quant_lin() and linear() with lda (>= K), ldo and an Epi of R1, c1, R2, c2, c0,
+ *                        act and the GEGLU flag, over a 0xFF-filled workspace; the caller sets the context's fp8_linears (ug_set_fp8_linears).  gamma / beta
+ *                        [K] given (lda == K): ln_linear() of LayerNorm(A) with a QAct from qact_alloc() - the pre-quantised hand-off; with epilogue operands
+ *                        the LayerNorm launch and linear() on that QAct, as the engine's feed-forward sends its GEGLU projection.
+ *                        info_out [3] (may be NULL): the Lin got an MX-fp8 weight, the MX GEMM ran (else the fp16 one), the LayerNorm wrote the QAct.
+ *                        What quant_lin() took from the persistent arena is released before the entry returns. */
+int ug_op_quant_mx8_ex(ug_ctx* ctx, const float* x, int M, int K, long ldx, long guard, long ld_s, unsigned char* q_inout, unsigned* s_inout);
+int ug_op_linear_mx8_ex(ug_ctx* ctx, const float* A, int M, int K, const float* W, int N, const float* bias, const float* R1, long ldr1, const float* R2, long ldr2,
+                        float c0, float c1, float c2, int act, int geglu, long ldo, long guard, int poison, float* out_inout,
+                        unsigned char* a8_out, unsigned* sa_out, int* plan_out /*[2]*/);
+int ug_op_linear_engine(ug_ctx* ctx, const float* A, int M, long lda, const float* W, int N, int K, const float* bias, const float* gamma, const float* beta, float eps,
+                        const float* R1, long ldr1, const float* R2, long ldr2, float c0, float c1, float c2, int act, int geglu, long ldo, long guard,
+                        float* out_inout, int* info_out /*[3]*/);
 int ug_op_conv(ug_ctx* ctx, const float* x0_thwc, int C0, const float* x1_thwc, int C1, int T, int H, int W,
                const float* weight /*[O][I][kt][ky][kx]*/, const float* bias, int O, int kt, int k, int stride,
                int pad_t, int pad_l, int ups, float* out_thwc);

@@ -25,7 +25,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex", "ug_op_flash_attn_dh_ex", "ug_op_attention_generic_ex", "ug_op_gemm_batched",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
-    "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex",
+    "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex", "ug_op_quant_mx8_ex", "ug_op_linear_mx8_ex", "ug_op_linear_engine",
     "ug_op_clip_patchify", "ug_op_prep_video", "ug_op_init_latents", "ug_op_unet_input", "ug_op_euler_step_cfg", "ug_op_window_blend",
     "ug_op_time_conv_out", "ug_op_depth_post", "ug_op_add_grid_nearest", "ug_op_sn_normals_out", "ug_op_clip_assemble",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
@@ -217,6 +217,10 @@ def load_library():
     _set_argtypes(lib, {"ug_op_ff_ex": [vp, vp, ip, ip, vp, vp, vp, vp, vp, ip, vp, C.c_float, C.c_float, C.c_float, vp, vp, C.c_float, vp, ip,
                                         ip, ip, C.c_long, C.c_long, vp, vp]})
     lg, fl = C.c_long, C.c_float
+    _set_argtypes(lib, {
+        "ug_op_quant_mx8_ex": [vp, vp, ip, ip, lg, lg, lg, vp, vp],
+        "ug_op_linear_mx8_ex": [vp, vp, ip, ip, vp, ip, vp, vp, lg, vp, lg, fl, fl, fl, ip, ip, lg, lg, ip, vp, vp, vp, vp],
+        "ug_op_linear_engine": [vp, vp, ip, lg, vp, ip, ip, vp, vp, vp, fl, vp, lg, vp, lg, fl, fl, fl, ip, ip, lg, lg, vp, vp]})
     _set_argtypes(lib, {
         "ug_op_clip_patchify": [vp, vp, ip, ip, ip, ip, ip, ip, ip, lg, vp], "ug_op_prep_video": [vp, vp, vp, ip, ip, ip, fl, lg, vp, vp],
         "ug_op_init_latents": [vp, vp, ip, lg, fl, lg, vp], "ug_op_unet_input": [vp, vp, vp, lg, fl, ip, lg, vp],
@@ -554,6 +558,50 @@ class Engine:
         sa = np.empty((K // 128, (M + 255) // 256 * 256), np.uint32) if return_quant else None
         self._ck(self.lib.ug_op_linear_mx8(self.ctx, _ptr(A), M, K, _ptr(W), N, _ptr(b), int(bool(geglu)), _ptr(out), _ptr(a8), _ptr(sa)))
         return (out, a8, sa) if return_quant else out
+
+    def op_quant_mx8_ex(self, x, M, K, q, s):
+        """launch_quant_mx8 alone (ug_op_quant_mx8_ex in include/unigeo_hip_test.h).  x [M + guard, ldx] float, q [M + guard, K] uint8 and s [K // 128, ld_s]
+        uint32 go to the device as given (ldx, guard and ld_s are read off the shapes); returns new arrays with the device's whole q and s."""
+        x = _f32(x); q = np.array(q, dtype=np.uint8, order="C"); s = np.array(s, dtype=np.uint32, order="C")
+        guard = x.shape[0] - M
+        assert guard >= 0 and q.shape == (M + guard, K) and s.ndim == 2 and s.shape[0] == K // 128, (x.shape, q.shape, s.shape)
+        self._ck(self.lib.ug_op_quant_mx8_ex(self.ctx, _ptr(x), int(M), int(K), x.shape[1], guard, s.shape[1], _ptr(q), _ptr(s)))
+        return q, s
+
+    def op_linear_mx8_ex(self, A, W, bias=None, R1=None, R2=None, c0=1.0, c1=1.0, c2=1.0, act=0, geglu=False, out=None, guard=0, ldo=None, poison=True,
+                         return_quant=False):
+        """Both quantiser launches and the MX-fp8 GEMM with its whole epilogue (ug_op_linear_mx8_ex).  R1 [M, ldr1] / R2 [M, ldr2] and out [M + guard, ldo]
+        (None: zeros, ldo columns) go to the device as given.  Returns (the whole output buffer as the device holds it, (tile pick, group_m))
+        (+ the A bytes and its scale dwords [K // 128, round_up(M, 256)] with return_quant)."""
+        A, W = _f32(A), _f32(W); M, K = A.shape; N = W.shape[0]; nout = N // 2 if geglu else N
+        opt = lambda a: None if a is None else _f32(a)
+        b, r1, r2 = opt(bias), opt(R1), opt(R2)
+        buf = np.zeros((M + guard, ldo or nout), np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+        assert buf.ndim == 2 and buf.shape[0] == M + guard and all(r is None or (r.ndim == 2 and r.shape[0] == M) for r in (r1, r2)), buf.shape
+        a8 = np.empty((M, K), np.uint8) if return_quant else None
+        sa = np.empty((K // 128, (M + 255) // 256 * 256), np.uint32) if return_quant else None
+        plan = (C.c_int * 2)()
+        self._ck(self.lib.ug_op_linear_mx8_ex(self.ctx, _ptr(A), M, K, _ptr(W), N, _ptr(b), _ptr(r1), 0 if r1 is None else r1.shape[1], _ptr(r2),
+                                              0 if r2 is None else r2.shape[1], float(c0), float(c1), float(c2), int(act), int(bool(geglu)), buf.shape[1],
+                                              int(guard), int(bool(poison)), _ptr(buf), _ptr(a8), _ptr(sa), plan))
+        return (buf, tuple(plan), a8, sa) if return_quant else (buf, tuple(plan))
+
+    def op_linear_engine(self, A, W, K=None, bias=None, gamma=None, beta=None, eps=1e-5, R1=None, R2=None, c0=1.0, c1=1.0, c2=1.0, act=0, geglu=False,
+                         out=None, guard=0, ldo=None):
+        """One linear layer through the engine's quant_lin() and linear() - with gamma / beta, ln_linear() and its pre-quantised hand-off - over a 0xFF-filled
+        workspace (ug_op_linear_engine); the path follows the context's fp8_linears.  A [M, lda] with lda >= K (K: W's columns).  Returns (the whole
+        output buffer as the device holds it, (MX-fp8 weight bound, MX GEMM ran, the LayerNorm wrote the quantised activation))."""
+        A, W = _f32(A), _f32(W); M, lda = A.shape; N, Kw = W.shape; nout = N // 2 if geglu else N
+        assert K is None or K == Kw
+        opt = lambda a: None if a is None else _f32(a)
+        b, g, bt, r1, r2 = opt(bias), opt(gamma), opt(beta), opt(R1), opt(R2)
+        buf = np.zeros((M + guard, ldo or nout), np.float32) if out is None else np.array(out, dtype=np.float32, order="C")
+        assert buf.ndim == 2 and buf.shape[0] == M + guard and all(r is None or (r.ndim == 2 and r.shape[0] == M) for r in (r1, r2)), buf.shape
+        info = (C.c_int * 3)()
+        self._ck(self.lib.ug_op_linear_engine(self.ctx, _ptr(A), M, lda, _ptr(W), N, Kw, _ptr(b), _ptr(g), _ptr(bt), float(eps), _ptr(r1),
+                                              0 if r1 is None else r1.shape[1], _ptr(r2), 0 if r2 is None else r2.shape[1], float(c0), float(c1), float(c2),
+                                              int(act), int(bool(geglu)), buf.shape[1], int(guard), _ptr(buf), info))
+        return buf, tuple(info)
 
     def run_traced(self, steps, decode_chunk=8, with_normals=False):
         """ug_dc_run with the latents after every Euler step copied out: returns [steps, T, 4, h, w] float32."""

@@ -512,31 +512,90 @@ int ug_op_ff_ex(ug_ctx* x, const float* X, int M, int C, const float* W1, const 
   });
 }
 
-int ug_op_linear_mx8(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, int geglu, float* out,
-                     unsigned char* a8_out, unsigned* sa_out) {
+// what is left of the workspace above the current mark, filled with 0xFF (e8m0 NaN in every scale byte): what a product launch may find there
+static void poison_rest(Ctx& c) {
+  void* top = c.ws.alloc(0);
+  UG_CHECK(hipMemsetAsync(top, 0xFF, c.ws.capacity() - c.ws.mark(), c.stream));
+}
+
+// The quantiser launch alone (tests/test_mx8_forms_gpu.py; the contract stands in include/unigeo_hip_test.h).
+int ug_op_quant_mx8_ex(ug_ctx* x, const float* xin, int M, int K, long ldx, long guard, long ld_s, unsigned char* q_inout, unsigned* s_inout) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(xin && q_inout && s_inout && M >= 1 && K >= 1 && ldx >= K && guard >= 0, "ug_op_quant_mx8_ex: arguments");
+    UG_REQUIRE(K % 128 == 0 && ldx % 8 == 0 && ld_s >= M, "ug_op_quant_mx8_ex: the launcher's rules (checked before the caller's buffers are sized by them)");
+    const long rows = M + guard;
+    const size_t qb = (size_t)rows * K, sb = (size_t)(K / 128) * ld_s * 4;
+    f16* dX = up16(c, xin, rows * ldx);
+    unsigned char* q = (unsigned char*)c.ws.alloc(qb); unsigned* s = (unsigned*)c.ws.alloc(sb);
+    UG_CHECK(hipMemcpy(q, q_inout, qb, hipMemcpyHostToDevice)); UG_CHECK(hipMemcpy(s, s_inout, sb, hipMemcpyHostToDevice));
+    launch_quant_mx8(dX, ldx, M, K, q, s, ld_s, c.stream);
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    UG_CHECK(hipMemcpy(q_inout, q, qb, hipMemcpyDeviceToHost)); UG_CHECK(hipMemcpy(s_inout, s, sb, hipMemcpyDeviceToHost));
+  });
+}
+
+// Every epilogue form of the MX-fp8 GEMM behind the two quantiser launches (the contract stands in include/unigeo_hip_test.h).
+int ug_op_linear_mx8_ex(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, const float* R1, long ldr1, const float* R2, long ldr2,
+                        float c0, float c1, float c2, int act, int geglu, long ldo, long guard, int poison, float* out_inout,
+                        unsigned char* a8_out, unsigned* sa_out, int* plan_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int nout = geglu ? N / 2 : N;
+    UG_REQUIRE(A && W && out_inout && M >= 1 && N >= 8 && K >= 1 && guard >= 0, "op_linear_mx8: arguments");
     UG_REQUIRE(K % 128 == 0 && N % 8 == 0, "op_linear_mx8: K % 128 == 0, N % 8 == 0");
+    UG_REQUIRE(!geglu || N % 128 == 0, "op_linear_mx8: GEGLU needs N % 128 == 0");
+    UG_REQUIRE(ldo >= nout && (!R1 || ldr1 >= nout) && (!R2 || ldr2 >= nout), "op_linear_mx8: rows narrower than the output");
     std::vector<float> Wp, bp;
     if (geglu) { pack_geglu(W, bias, N, K, Wp, bp); W = Wp.data(); if (bias) bias = bp.data(); }
     f16* dA = up16(c, A, (long)M * K); f16* dW = up16(c, W, (long)N * K);
     f16* db = up16_opt(c, bias, N);
+    f16* dR1 = up16_opt(c, R1, (long)M * ldr1); f16* dR2 = up16_opt(c, R2, (long)M * ldr2);
+    f16* dO = up16(c, out_inout, (M + guard) * ldo);
     const long ld_sa = (M + 255) / 256 * 256, ld_sw = (N + 255) / 256 * 256;
+    if (poison) poison_rest(c);   // the four buffers below and everything above them: rows [M, ld_sa) / [N, ld_sw) of the scale areas then hold e8m0 NaN, as in the product
     unsigned char* a8 = (unsigned char*)c.ws.alloc((size_t)M * K); unsigned char* w8 = (unsigned char*)c.ws.alloc((size_t)N * K);
-    unsigned* sa = (unsigned*)c.ws.alloc((size_t)(K / 128) * ld_sa * 4); unsigned* sw = (unsigned*)c.ws.alloc((size_t)(K / 128) * ld_sw * 4);
-    UG_CHECK(hipMemsetAsync(sa, 0, (size_t)(K / 128) * ld_sa * 4, c.stream)); UG_CHECK(hipMemsetAsync(sw, 0, (size_t)(K / 128) * ld_sw * 4, c.stream));
+    unsigned* sw = (unsigned*)c.ws.alloc((size_t)(K / 128) * ld_sw * 4); unsigned* sa = (unsigned*)c.ws.alloc((size_t)(K / 128) * ld_sa * 4);
     launch_quant_mx8(dA, K, M, K, a8, sa, ld_sa, c.stream);
     launch_quant_mx8(dW, K, N, K, w8, sw, ld_sw, c.stream);
-    const int nout = geglu ? N / 2 : N;
-    f16* dO = c.ws.get<f16>((long)M * nout);
-    GemmP p = dense_gemm(c, (const f16*)a8, M, K, (const f16*)w8, N, db, dO, nout);
+    GemmP p = dense_gemm(c, (const f16*)a8, M, K, (const f16*)w8, N, db, dO, ldo);
+    p.R1 = dR1; p.ldr1 = ldr1; p.c1 = c1; p.R2 = dR2; p.ldr2 = ldr2; p.c2 = c2; p.c0 = c0; p.act = act;
     p.flags = geglu ? UG_F_GEGLU : 0;
     p.sa = sa; p.ld_sa = ld_sa; p.sw = sw; p.ld_sw = ld_sw;
     gemm_apply_tune(p, c.tune);
-    launch_gemm_mx8(p, c.stream);
-    down16(c, dO, out, (long)M * nout);
+    launch_gemm_mx8(p, c.stream, plan_out);
+    down16(c, dO, out_inout, (M + guard) * ldo);
     if (a8_out) UG_CHECK(hipMemcpy(a8_out, a8, (size_t)M * K, hipMemcpyDeviceToHost));
     if (sa_out) UG_CHECK(hipMemcpy(sa_out, sa, (size_t)(K / 128) * ld_sa * 4, hipMemcpyDeviceToHost));
+  });
+}
+
+int ug_op_linear_mx8(ug_ctx* x, const float* A, int M, int K, const float* W, int N, const float* bias, int geglu, float* out,
+                     unsigned char* a8_out, unsigned* sa_out) {
+  return ug_op_linear_mx8_ex(x, A, M, K, W, N, bias, nullptr, 0, nullptr, 0, 1.f, 1.f, 1.f, 0, geglu, geglu ? N / 2 : N, 0, 0, out, a8_out, sa_out, nullptr);
+}
+
+// One linear layer through the engine's quant_lin() and linear() / ln_linear() over a 0xFF-filled workspace (the contract stands in include/unigeo_hip_test.h).
+int ug_op_linear_engine(ug_ctx* x, const float* A, int M, long lda, const float* W, int N, int K, const float* bias, const float* gamma, const float* beta, float eps,
+                        const float* R1, long ldr1, const float* R2, long ldr2, float c0, float c1, float c2, int act, int geglu, long ldo, long guard,
+                        float* out_inout, int* info_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int nout = geglu ? N / 2 : N;
+    UG_REQUIRE(A && W && out_inout && M >= 1 && N >= 8 && N % 8 == 0 && K >= 8 && K % 8 == 0 && guard >= 0, "ug_op_linear_engine: arguments");
+    UG_REQUIRE(lda >= K && lda % 8 == 0 && ldo >= nout && (!R1 || ldr1 >= nout) && (!R2 || ldr2 >= nout), "ug_op_linear_engine: rows narrower than the matrix");
+    UG_REQUIRE(!geglu || N % 128 == 0, "ug_op_linear_engine: GEGLU needs N % 128 == 0");
+    UG_REQUIRE(!gamma || (beta && lda == K), "ug_op_linear_engine: the LayerNorm takes beta and tight rows");
+    std::vector<float> Wp, bp;
+    if (geglu) { pack_geglu(W, bias, N, K, Wp, bp); W = Wp.data(); if (bias) bias = bp.data(); }
+    f16* dA = up16(c, A, (long)M * lda); f16* dW = up16(c, W, (long)N * K); f16* db = up16_opt(c, bias, N);
+    f16* dg = up16_opt(c, gamma, K); f16* dbt = up16_opt(c, beta, K);
+    f16* dR1 = up16_opt(c, R1, (long)M * ldr1); f16* dR2 = up16_opt(c, R2, (long)M * ldr2);
+    f16* dO = up16(c, out_inout, (M + guard) * ldo);
+    poison_rest(c);
+    test_linear_engine(c, dA, M, lda == K ? 0 : lda, dW, db, K, N, dg, dbt, eps, dR1, ldr1, c1, dR2, ldr2, c2, c0, act, geglu ? UG_F_GEGLU : 0, dO,
+                       ldo == nout ? 0 : ldo, info_out);
+    down16(c, dO, out_inout, (M + guard) * ldo);
   });
 }
 

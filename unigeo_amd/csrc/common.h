@@ -92,8 +92,8 @@ struct GemmP {
 // cfg / split -1 = planner's choice; knobs = bit mask documented in kernels/gemm.hip
 struct GemmTune { int cfg = -1, split = -1, knobs = 0; };
 static inline void gemm_apply_tune(GemmP& p, const GemmTune& t) { p.tune_cfg_p1 = t.cfg + 1; p.tune_split_p1 = t.split + 1; p.tune_knobs = t.knobs; }
-void launch_gemm_mx8(const GemmP& p, hipStream_t s);   // dense only; C0 = lda and ldw in BYTES (= elements)
-// fp16 [M, K] (row stride ldx) -> e4m3 bytes [M, K] + e8m0 scales (layout above, ld_s >= round_up(M, 256)); K % 128 == 0
+void launch_gemm_mx8(const GemmP& p, hipStream_t s, int* plan_out = nullptr);   // dense only; C0 = lda and ldw in BYTES (= elements); plan_out [2] = (tile pick, group_m) as launched
+// fp16 [M, K] (row stride ldx) -> e4m3 bytes [M, K] + e8m0 scales (layout above, ld_s >= M; launch_gemm_mx8 takes ld_s % 4 == 0 and masks its fetch at ld_s); K % 128 == 0
 void launch_quant_mx8(const f16* x, long ldx, long M, int K, unsigned char* q, unsigned* scales, long ld_s, hipStream_t s);
 void launch_gemm(const GemmP& p, int batch, hipStream_t s, int* stat_rb = nullptr);   // stat_rb: rows per statistics block written (0 = none), see GemmP::stat_part
 // weight-stationary streaming GEMM for K = 320, N in {320, 640, 960} (kernels/gemm_stream.hip; tile config 80): dense, fp16 out, bias + one residual

@@ -231,6 +231,13 @@ void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x
 // in-kernel LayerNorm and the whole-rounds row split the context's switches and M select.  Returns the rows the fused kernel took (0: none).
 long test_ln_ff(Ctx& c, const f16* x, long M, int C, const f16* gamma, const f16* beta, float eps, const f16* addvec, long rows_per_vec,
                 const f16* W1, const f16* b1, const f16* W2, const f16* b2, const f16* R2, float c0, float c1, float c2, f16* out);
+// one linear layer under the engine's own rules (op-level tests): a Lin built from device tensors (W [out][in], bias may be NULL) goes through quant_lin()
+// and then linear() with an Epi of (R1, ldr1, c1, R2, ldr2, c2, c0, act, flags), lda and ldo (0: tight) - with the context's fp8_linears whichever of the
+// MX-fp8 and the fp16 GEMM linear() picks.  gamma / beta given: ln_linear() of LayerNorm(A) (tight rows) with a QAct from qact_alloc() under
+// transformer_forward's rule - with an epilogue, the LayerNorm launch and linear() on that QAct, as ff_pair sends its GEGLU projection.  info [3]: l.w8 bound, the MX GEMM ran (no fp16 launch was planned), the LayerNorm wrote the QAct.
+// What quant_lin() took from c.persist and everything taken from c.ws is released before it returns.
+void test_linear_engine(Ctx& c, const f16* A, long M, long lda, const f16* W, const f16* bias, int in, int out, const f16* gamma, const f16* beta, float eps,
+                        const f16* R1, long ldr1, float c1, const f16* R2, long ldr2, float c2, float c0, int act, int flags, f16* dst, long ldo, int* info);
 
 // ---- StableNormal (sn_graphs.inc) ----
 void bind_sn(Ctx& c, const UNetCfg& ucfg, const VAECfg& vcfg, const CLIPCfg& dcfg, const std::string& prefix);   // "<prefix>{vae,unet_yoso,controlnet_yoso,unet,controlnet_dino,dino}."

@@ -1397,6 +1397,42 @@ long test_ln_ff(Ctx& c, const f16* x, long M, int C, const f16* gamma, const f16
   c.ws.release(mk);
   return ff_pair_fusable(c, M, f1, f2, e) ? ff_fused_rows(c, M) : 0;
 }
+// one linear layer through the engine's own rules (op-level tests; engine.h): quant_lin() on a Lin built from device tensors, then linear() - or, with
+// gamma / beta, ln_linear() with the QAct hand-off under transformer_forward's rule.  What quant_lin took from c.persist is released before returning.
+void test_linear_engine(Ctx& c, const f16* A, long M, long lda, const f16* W, const f16* bias, int in, int out, const f16* gamma, const f16* beta, float eps,
+                        const f16* R1, long ldr1, float c1, const f16* R2, long ldr2, float c2, float c0, int act, int flags, f16* dst, long ldo, int* info) {
+  Lin l; l.w = W; l.b = bias; l.in = in; l.out = out;
+  struct Marks {   // both arenas go back on every way out, once the stream is idle
+    Ctx& c; size_t pk, mk;
+    ~Marks() { (void)hipStreamSynchronize(c.stream); c.ws.release(mk); c.persist.release(pk); }
+  } marks{c, c.persist.mark(), c.ws.mark()};
+  quant_lin(c, l);
+  std::vector<int> plan;
+  {
+    PlanLog log(c, &plan);       // run_gemm logs the fp16 launches; the MX path does not go through it
+    if (gamma) {
+      Norm ln; ln.g = gamma; ln.b = beta; ln.c = in; ln.eps = eps;
+      const bool q8 = c.fp8_linears && !getenv("UG_NO_LNQ") && in % 128 == 0 && M >= 256 && l.w8;
+      QAct qa; if (q8) qa = qact_alloc(c, M, in);
+      f16* t1 = c.ws.get<f16>(M * in);
+      const QAct* qp = q8 ? &qa : nullptr;
+      if (!R1 && !R2 && !flags && !act && c0 == 1.f && !ldo) ln_linear(c, A, M, ln, t1, l, dst, qp);
+      else {   // the hand-off with an epilogue, as ff_pair sends its GEGLU projection: the LayerNorm launch, then linear() on the QAct
+        layernorm(c, A, M, ln, t1, nullptr, 1, nullptr, qp);
+        Epi e; e.R1 = R1; e.ldr1 = ldr1; e.c1 = c1; e.R2 = R2; e.ldr2 = ldr2; e.c2 = c2; e.c0 = c0; e.act = act; e.flags = flags;
+        if (qp) { e.a8 = qp->a8; e.sa8 = qp->sa; e.ld_sa8 = qp->ld; }
+        linear(c, t1, M, l, dst, e, 0, ldo);
+      }
+      if (info) info[2] = q8 ? 1 : 0;
+    } else {
+      Epi e; e.R1 = R1; e.ldr1 = ldr1; e.c1 = c1; e.R2 = R2; e.ldr2 = ldr2; e.c2 = c2; e.c0 = c0; e.act = act; e.flags = flags;
+      linear(c, A, M, l, dst, e, lda, ldo);
+      if (info) info[2] = 0;
+    }
+  }
+  if (info) { info[0] = l.w8 ? 1 : 0; info[1] = plan.empty() ? 1 : 0; }
+  UG_CHECK(hipStreamSynchronize(c.stream));
+}
 
 static f16* vae_encode_wide(Ctx& c, VAE& v, const f16* x8, int T, int H, int W) {
   UG_REQUIRE(v.wide_bound, "float32-grade VAE encoder weights are not bound");

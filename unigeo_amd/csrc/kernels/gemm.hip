@@ -270,8 +270,11 @@ __global__ __launch_bounds__(WMW * WNW * 64, (GemmOcc<BM, BN, BK, NST, WMW, WNW>
       unsigned* sc = (unsigned*)(smem + NST * STAGE) + buf * (BM + BN) + (wave ? BM : 0);
       const int rows = wave ? BN : BM;
       const unsigned* g = wave ? p.sw + (long)(kt0 / BK) * p.ld_sw + ld_n0 : p.sa + (long)(kt0 / BK) * p.ld_sa + ld_m0;
-      // lanes past the tile's rows stay masked off: the 1 KiB image of a full-wave load would run over the neighbouring scale area
-      if (4 * lane < rows) __builtin_amdgcn_global_load_lds((gptr_t)(g + 4 * lane), (lptr_t)sc, 16, 0, 0);
+      // lanes past the tile's rows stay masked off: the 1 KiB image of a full-wave load would run over the neighbouring scale area.  So do lanes
+      // whose rows lie past the scale area itself (ld % 4 == 0, launch_gemm_mx8): the last 192-row tile can reach beyond pad256(M), and on the
+      // last K step that is the end of the allocation.  Those rows are >= M / >= N: their products are never stored.
+      const long left = (wave ? p.ld_sw - ld_n0 : p.ld_sa - ld_m0) - 4 * lane;
+      if (4 * lane < rows && left > 0) __builtin_amdgcn_global_load_lds((gptr_t)(g + 4 * lane), (lptr_t)sc, 16, 0, 0);
     }
     if (BUFA) {
 #pragma unroll
@@ -1211,10 +1214,12 @@ static void launch_mx(const GemmP& p, hipStream_t s) {
   if (bufa) launch_mx_t<BM, BN, NST, WMW, WNW, true>(p, s);
   else launch_mx_t<BM, BN, NST, WMW, WNW, false>(p, s);
 }
-void launch_gemm_mx8(const GemmP& p0, hipStream_t s) {
+void launch_gemm_mx8(const GemmP& p0, hipStream_t s, int* plan_out) {
   GemmP p = p0;
   UG_REQUIRE(!p.conv && p.K % 128 == 0 && p.C0 % 16 == 0 && p.ldw % 16 == 0, "MX-fp8 GEMM: dense, K % 128 == 0, 16-byte aligned rows");
   UG_REQUIRE(p.sa && p.sw && p.zero, "MX-fp8 GEMM needs block scales");
+  // the kernel fetches four rows' scale dwords per lane and masks a lane by its first row against ld (gemm_kernel<MX>)
+  UG_REQUIRE(p.ld_sa % 4 == 0 && p.ld_sw % 4 == 0 && p.ld_sa >= p.M && p.ld_sw >= p.N, "MX-fp8 GEMM: scale rows ld % 4 == 0, ld_sa >= M, ld_sw >= N");
   UG_REQUIRE(p.M > 0 && p.N > 0 && p.nb_inner >= 1 && p.splitk <= 1, "MX-fp8 GEMM shape");
   if (p.flags & UG_F_GEGLU) UG_REQUIRE(p.N % 128 == 0, "GEGLU GEMM needs N % 128 == 0");
   p.K /= 2; p.C0 /= 2; p.ldw /= 2;          // bytes -> the loaders' fp16 units (see gemm_kernel<MX>)
@@ -1244,6 +1249,7 @@ void launch_gemm_mx8(const GemmP& p0, hipStream_t s) {
       while (g * 2 <= ntm && (double)(g * 2) * (g * 2) <= 32.0 * percu * bn / bm * 1.5) g *= 2;
     p.group_m = g;
   }
+  if (plan_out) { plan_out[0] = pick; plan_out[1] = p.group_m; }
   switch (pick) {
     case 0: launch_mx<256, 256, 2, 2, 4>(p, s); break;
     case 1: launch_mx<256, 128, 3, 4, 2>(p, s); break;
