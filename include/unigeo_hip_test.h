@@ -214,6 +214,25 @@ int ug_op_bind_conv(ug_ctx* ctx, const float* weight, const float* bias, int cin
 int ug_op_conv_bound(ug_ctx* ctx, const float* weight, const float* bias, int cin, int O, int kt, int k, int upsampler,
                      const float* x0_thwc, int C0, const float* x1_thwc, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
                      const float* R1, float c0, float c1, int act, long ldo, long guard, float* out_inout, int* plan_out /*[9]*/);
+/* The epilogue operands of the graphs on every GEMM kernel family (tests/test_epilogue_forms_gpu.py):
+ *     out = act(c0 * f(acc + bias + bias2) + c1 * R1 + c2 * R2),  f = GEGLU or the identity
+ * through the engine's linear() / conv(), honouring ug_tune_force.  bias, bias2, R1, R2 may be NULL.  out_inout [rows + guard, ldo] goes to the device as
+ * given and comes back whole.  plan_out [2] (may be NULL) = the tile config launch_gemm launched (the planner's or the forced one; 70 - 73 / 80 where the
+ * halo-staged / streaming kernel took the launch, 60 for the row-split pair) and the split factor.  A bad call returns an error and leaves the context usable.
+ *   ug_op_linear_ex: the fp16 path of linear(); refuses a context with fp8_linears set.  A [M, lda] (lda >= K, lda % 8 == 0), W [N, K], bias / bias2 [N],
+ *                    R1 [M, ldr1], R2 [M, ldr2], out_inout [M + guard, ldo]; the output width is N, with geglu != 0 N / 2 (N % 128 == 0; W, bias and bias2
+ *                    in checkpoint order [values | gates], packed into the bound row order here).
+ *   ug_op_conv_epi : the checkpoint-layout weight bound by bind_conv and launched by conv(), as ug_op_conv_bound (no upsampling forms): one or two sources,
+ *                    kt in {1, 3}, stride 1 / 2; bias2 [O], R1 [rows, ldr1], R2 [rows, ldr2], rows = T * (H / stride) * (W / stride).  want_stats != 0: the
+ *                    launch is handed a StatPart of ceil(rows / 48) * O float2 (the size stat_alloc gives it): stat_inout (2 floats per float2) is uploaded
+ *                    bit for bit, downloaded whole, and *rb_out = rows per statistics block, 0 when the launch declined (it then wrote nothing there). */
+int ug_op_linear_ex(ug_ctx* ctx, const float* A, int M, long lda, const float* W, int N, int K, const float* bias, const float* bias2,
+                    const float* R1, long ldr1, const float* R2, long ldr2, float c0, float c1, float c2, int act, int geglu,
+                    long ldo, long guard, float* out_inout, int* plan_out /*[2]*/);
+int ug_op_conv_epi(ug_ctx* ctx, const float* weight, const float* bias, int cin, int O, int kt, int k,
+                   const float* x0_thwc, int C0, const float* x1_thwc, int C1, int T, int H, int W, int stride, int pad_t, int pad_l,
+                   const float* bias2, const float* R1, long ldr1, const float* R2, long ldr2, float c0, float c1, float c2, int act,
+                   long ldo, long guard, float* out_inout, int want_stats, float* stat_inout, int* rb_out, int* plan_out /*[2]*/);
 /* Clip inputs made on the device (kernels/noise.hip; behind ug_dc_set_inputs_ex of the product header).
  *   ug_op_philox_u32  : Philox4x32-10 words of blocks block_offset .. block_offset + nblocks - 1 for key = seed (lo, hi) and counter
  *                       (q lo, q hi, stream, 0) -> out [nblocks][4] uint32 (the generator against the published known-answer vectors)

@@ -25,7 +25,7 @@ EXPORTS = [
     "ug_op_temporal_attn", "ug_op_attention_generic", "ug_op_flash_attn_dh", "ug_op_euler_step", "ug_op_flash_cross_attn", "ug_op_temporal_attn_nv",
     "ug_op_groupnorm_ex", "ug_op_layernorm_ex", "ug_op_flash_attn_dh_ex", "ug_op_attention_generic_ex", "ug_op_gemm_batched",
     "ug_op_split_pair", "ug_op_gn32_pair", "ug_op_conv_wide", "ug_op_attn_wide",
-    "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex", "ug_op_quant_mx8_ex", "ug_op_linear_mx8_ex", "ug_op_linear_engine",
+    "ug_op_bind_conv", "ug_op_conv_bound", "ug_op_ff_ex", "ug_op_quant_mx8_ex", "ug_op_linear_mx8_ex", "ug_op_linear_engine", "ug_op_linear_ex", "ug_op_conv_epi",
     "ug_op_clip_patchify", "ug_op_prep_video", "ug_op_init_latents", "ug_op_unet_input", "ug_op_euler_step_cfg", "ug_op_window_blend",
     "ug_op_time_conv_out", "ug_op_depth_post", "ug_op_add_grid_nearest", "ug_op_sn_normals_out", "ug_op_clip_assemble",
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
@@ -221,6 +221,9 @@ def load_library():
         "ug_op_quant_mx8_ex": [vp, vp, ip, ip, lg, lg, lg, vp, vp],
         "ug_op_linear_mx8_ex": [vp, vp, ip, ip, vp, ip, vp, vp, lg, vp, lg, fl, fl, fl, ip, ip, lg, lg, ip, vp, vp, vp, vp],
         "ug_op_linear_engine": [vp, vp, ip, lg, vp, ip, ip, vp, vp, vp, fl, vp, lg, vp, lg, fl, fl, fl, ip, ip, lg, lg, vp, vp]})
+    _set_argtypes(lib, {
+        "ug_op_linear_ex": [vp, vp, ip, lg, vp, ip, ip, vp, vp, vp, lg, vp, lg, fl, fl, fl, ip, ip, lg, lg, vp, vp],
+        "ug_op_conv_epi": [vp, vp, vp, ip, ip, ip, ip, vp, ip, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, lg, vp, lg, fl, fl, fl, ip, lg, lg, vp, ip, vp, vp, vp]})
     _set_argtypes(lib, {
         "ug_op_clip_patchify": [vp, vp, ip, ip, ip, ip, ip, ip, ip, lg, vp], "ug_op_prep_video": [vp, vp, vp, ip, ip, ip, fl, lg, vp, vp],
         "ug_op_init_latents": [vp, vp, ip, lg, fl, lg, vp], "ug_op_unet_input": [vp, vp, vp, lg, fl, ip, lg, vp],
@@ -1292,6 +1295,47 @@ class Engine:
         self._ck(self.lib.ug_op_conv_bound(self.ctx, _ptr(w), _ptr(b), I, O, kt, k, int(bool(upsampler)), _ptr(x0), C0, _ptr(x1a), C1, T, H, W,
                                            stride, pad_t, pad_l, ups, _ptr(r), c0, c1, act, int(ldo), int(guard), _ptr(out), plan))
         return out, tuple((plan[1 + 2 * i], plan[2 + 2 * i]) for i in range(plan[0]))
+
+    # the epilogue operands of the graphs on linear() / conv() (tests/test_epilogue_forms_gpu.py).  Residuals are [rows, ld] arrays (ld >= the output width),
+    # the output buffer [rows + guard, ldo] is filled with `fill` (or given as `out`) before it goes to the device and comes back whole.
+    STAT_SENTINEL = 0x7FC5A5A5      # a quiet NaN with a payload no kernel produces: the bit pattern of an untouched statistics word
+
+    def op_linear_ex(self, A, W, bias=None, bias2=None, R1=None, R2=None, c0=1.0, c1=1.0, c2=1.0, act=0, geglu=False, K=None, ldo=0, guard=0, fill=0.0):
+        """A [M, lda] (lda >= K = W's columns), W [N, K]: act(c0 * f(A[:, :K] W^T + bias + bias2) + c1 * R1 + c2 * R2) through the engine's fp16 linear()
+        (ug_op_linear_ex).  Returns (out [M + guard, ldo] as the device holds it, (tile config launched, split factor))."""
+        A, W = _f32(A), _f32(W); M, lda = A.shape; N, Kw = W.shape; nout = N // 2 if geglu else N
+        assert K is None or K == Kw
+        opt = lambda a: None if a is None else _f32(a)
+        b, b2, r1, r2 = opt(bias), opt(bias2), opt(R1), opt(R2)
+        assert all(v is None or v.shape == (N,) for v in (b, b2)) and all(r is None or (r.ndim == 2 and r.shape[0] == M) for r in (r1, r2))
+        out = np.full((M + guard, ldo or nout), fill, np.float32)
+        plan = (C.c_int * 2)()
+        self._ck(self.lib.ug_op_linear_ex(self.ctx, _ptr(A), M, lda, _ptr(W), N, Kw, _ptr(b), _ptr(b2), _ptr(r1), 0 if r1 is None else r1.shape[1],
+                                          _ptr(r2), 0 if r2 is None else r2.shape[1], float(c0), float(c1), float(c2), int(act), int(bool(geglu)),
+                                          out.shape[1], int(guard), _ptr(out), plan))
+        return out, tuple(plan)
+
+    def op_conv_epi(self, x0, weight, bias=None, x1=None, stride=1, pad_t=1, pad_l=1, bias2=None, R1=None, R2=None, c0=1.0, c1=1.0, c2=1.0, act=0,
+                    ldo=0, guard=0, fill=0.0, stats=False):
+        """weight [O, I, kt, k, k] bound on the device and launched by the engine's conv() on x0 [T,H,W,C0] (+ x1 [T,H,W,C1]) with the whole epilogue
+        (ug_op_conv_epi).  Returns (out [rows + guard, ldo], (tile config launched, split factor)), and with stats=True also (rb, part): the rows per
+        statistics block the launch reported (0: declined) and the statistics area [ceil(rows / 48), O, 2] float32 (sum, sum of squares), which went to the
+        device filled with STAT_SENTINEL."""
+        x0 = _f32(x0); T, H, W, C0 = x0.shape
+        x1a = None if x1 is None else _f32(x1); C1 = 0 if x1 is None else x1a.shape[-1]
+        w = _f32(weight); O, I, kt, k, _ = w.shape
+        opt = lambda a: None if a is None else _f32(a)
+        b, b2, r1, r2 = opt(bias), opt(bias2), opt(R1), opt(R2)
+        rows = T * (H // stride) * (W // stride)
+        assert all(v is None or v.shape == (O,) for v in (b, b2)) and all(r is None or (r.ndim == 2 and r.shape[0] == rows) for r in (r1, r2))
+        out = np.full((rows + guard, ldo or O), fill, np.float32)
+        part = np.full(((rows + 47) // 48, O, 2), self.STAT_SENTINEL, np.uint32).view(np.float32) if stats else None
+        plan = (C.c_int * 2)(); rb = C.c_int(0)
+        self._ck(self.lib.ug_op_conv_epi(self.ctx, _ptr(w), _ptr(b), I, O, kt, k, _ptr(x0), C0, _ptr(x1a), C1, T, H, W, stride, pad_t, pad_l,
+                                         _ptr(b2), _ptr(r1), 0 if r1 is None else r1.shape[1], _ptr(r2), 0 if r2 is None else r2.shape[1],
+                                         float(c0), float(c1), float(c2), int(act), out.shape[1], int(guard), _ptr(out), int(bool(stats)), _ptr(part),
+                                         C.cast(C.byref(rb), C.c_void_p), plan))
+        return (out, tuple(plan), int(rb.value), part) if stats else (out, tuple(plan))
 
     def op_attn_wide(self, qkv, T, S):
         q = _f32(qkv); Cc = q.shape[1] // 3

@@ -994,6 +994,71 @@ int ug_op_conv_bound(ug_ctx* x, const float* weight, const float* bias, int cin,
     down16(c, dO, out_inout, (rows + guard) * ldo);
   });
 }
+// ---- the epilogue operands of the graphs - bias2, R1 / c1, R2 / c2, c0, act - on the engine's linear() and conv() (tests/test_epilogue_forms_gpu.py; the
+// contract stands in include/unigeo_hip_test.h)
+static TestEpi upload_epi(Ctx& c, const float* bias2, int N, const float* R1, long ldr1, const float* R2, long ldr2, long rows, float c0, float c1, float c2, int act) {
+  TestEpi e;
+  e.bias2 = up16_opt(c, bias2, N);
+  e.R1 = up16_opt(c, R1, rows * ldr1); e.ldr1 = R1 ? ldr1 : 0; e.c1 = c1;
+  e.R2 = up16_opt(c, R2, rows * ldr2); e.ldr2 = R2 ? ldr2 : 0; e.c2 = c2;
+  e.c0 = c0; e.act = act;
+  return e;
+}
+int ug_op_linear_ex(ug_ctx* x, const float* A, int M, long lda, const float* W, int N, int K, const float* bias, const float* bias2,
+                    const float* R1, long ldr1, const float* R2, long ldr2, float c0, float c1, float c2, int act, int geglu,
+                    long ldo, long guard, float* out_inout, int* plan_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    const int nout = geglu ? N / 2 : N;
+    UG_REQUIRE(!c.fp8_linears, "ug_op_linear_ex: the fp16 path only - the context has fp8_linears set");
+    UG_REQUIRE(A && W && out_inout && M >= 1 && N >= 1 && K >= 8 && K % 8 == 0 && guard >= 0 && act >= 0 && act <= 2, "ug_op_linear_ex: arguments");
+    UG_REQUIRE(lda >= K && lda % 8 == 0 && ldo >= nout && (!R1 || ldr1 >= nout) && (!R2 || ldr2 >= nout), "ug_op_linear_ex: rows narrower than the matrix");
+    UG_REQUIRE(!geglu || N % 128 == 0, "ug_op_linear_ex: GEGLU needs N % 128 == 0");
+    std::vector<float> Wp, bp, Wq, b2p;
+    if (geglu) {     // checkpoint order [value | gate] -> the bound row order, bias2 with the rows it belongs to
+      pack_geglu(W, bias, N, K, Wp, bp);
+      if (bias2) { pack_geglu(W, bias2, N, K, Wq, b2p); bias2 = b2p.data(); }
+      W = Wp.data(); if (bias) bias = bp.data();
+    }
+    f16* dA = up16(c, A, (long)M * lda); f16* dW = up16(c, W, (long)N * K); f16* db = up16_opt(c, bias, N);
+    TestEpi e = upload_epi(c, bias2, N, R1, ldr1, R2, ldr2, M, c0, c1, c2, act);
+    e.flags = geglu ? UG_F_GEGLU : 0;
+    f16* dO = up16(c, out_inout, (M + guard) * ldo);
+    std::vector<int> plan, launched;
+    test_linear_epi(c, dA, M, lda == K ? 0 : lda, dW, db, K, N, e, dO, ldo == nout ? 0 : ldo, &plan, &launched);
+    UG_REQUIRE(plan.size() == 2 && launched.size() == 1, "ug_op_linear_ex: one GEMM launch");
+    if (plan_out) { plan_out[0] = launched[0]; plan_out[1] = plan[1]; }
+    down16(c, dO, out_inout, (M + guard) * ldo);
+  });
+}
+int ug_op_conv_epi(ug_ctx* x, const float* weight, const float* bias, int cin, int O, int kt, int k,
+                   const float* x0, int C0, const float* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l,
+                   const float* bias2, const float* R1, long ldr1, const float* R2, long ldr2, float c0, float c1, float c2, int act,
+                   long ldo, long guard, float* out_inout, int want_stats, float* stat_inout, int* rb_out, int* plan_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c); BindScope bs(c, "op_conv_epi.");
+    UG_REQUIRE(x0 && out_inout && T >= 1 && H >= 1 && W >= 1 && guard >= 0 && C0 >= 8 && C1 >= 0 && (C1 == 0 || x1) && act >= 0 && act <= 2, "ug_op_conv_epi: shape");
+    UG_REQUIRE((stride == 1 || stride == 2) && H % stride == 0 && W % stride == 0, "ug_op_conv_epi: stride 1 or 2, dividing the frame");
+    UG_REQUIRE(C0 % 8 == 0 && C1 % 8 == 0 && C0 + C1 == cin, "ug_op_conv_epi: C0 + C1 must be cin, each a multiple of 8");
+    UG_REQUIRE(ldo >= O && (!R1 || ldr1 >= O) && (!R2 || ldr2 >= O), "ug_op_conv_epi: rows narrower than the output channels");
+    UG_REQUIRE(!want_stats || (stat_inout && rb_out), "ug_op_conv_epi: want_stats needs stat_inout and rb_out");
+    const Conv cv = bind_op_conv(c, "op_conv_epi.conv", weight, bias, cin, O, kt, k, 0);
+    finish_binding(c, "op_conv_epi.");
+    const long px = (long)T * H * W, rows = (long)T * (H / stride) * (W / stride);
+    const f16* d0 = up16(c, x0, px * C0); const f16* d1 = C1 ? up16(c, x1, px * C1) : nullptr;
+    const TestEpi e = upload_epi(c, bias2, O, R1, ldr1, R2, ldr2, rows, c0, c1, c2, act);
+    f16* dO = up16(c, out_inout, (rows + guard) * ldo);
+    const long nstat = ((rows + 47) / 48) * (long)O * 2;     // floats: one float2 per (block of >= 48 rows, channel), as stat_alloc sizes the area
+    float* dS = want_stats ? up32g(c, stat_inout, nstat) : nullptr;
+    std::vector<int> plan, launched;
+    const int rb = test_conv_epi(c, cv, d0, C0, d1, C1, T, H, W, stride, pad_t, pad_l, e, (float2*)dS, dO, ldo == O ? 0 : ldo, &plan, &launched);
+    UG_REQUIRE(plan.size() == 2 && launched.size() == 1, "ug_op_conv_epi: one GEMM launch");
+    if (plan_out) { plan_out[0] = launched[0]; plan_out[1] = plan[1]; }
+    if (rb_out) *rb_out = rb;
+    down16(c, dO, out_inout, (rows + guard) * ldo);
+    if (want_stats) down32g(c, dS, stat_inout, nstat);
+  });
+}
 int ug_op_attn_wide(ug_ctx* x, const float* qkv, int T, int S, int C, float* out) {
   UG_TRY(x, {
     Ctx& c = x->c; Scope sc(c);

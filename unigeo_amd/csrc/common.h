@@ -83,9 +83,12 @@ struct GemmP {
   int halo_tw, halo_lg;  // set by launch_conv_halo only (kernels/conv_halo.hip): the tile is (256 / halo_tw) x halo_tw output pixels of one frame, halo_tw = 1 << halo_lg;
                          // the epilogue maps tile row r to launch row m0 + (r >> halo_lg) * Wo + (r & (halo_tw - 1))
   int tune_cfg_p1, tune_split_p1, tune_knobs;   // GemmTune of the launching context, + 1 so that a zeroed GemmP means "no override"
-  // GroupNorm statistics of the OUTPUT from the epilogue (round 4): per block of `rb` consecutive output rows (rb = the wave tile's rows, reported by
+  // GroupNorm statistics of the OUTPUT from the epilogue (round 4): per block of `rb` output rows of ONE frame (rb = the wave tile's rows, reported by
   // launch_gemm) and per column the sum / sum of squares of the fp16 values stored, stat_part[blk * N + n]; stat_hw = output rows per frame (blocks
-  // must not straddle frames).  launch_gemm declines (reports rb = 0, writes nothing) when the chosen kernel cannot: split-K, ragged tiles, ...
+  // must not straddle frames).  The tile_epilogue family's blocks are rb CONSECUTIVE output rows [blk * rb, (blk + 1) * rb); a halo tile's (configs 71 / 72)
+  // are the rb / TW image rows x TW pixels of one wave inside its TH x TW pixel tile - not consecutive rows.  What holds for every kernel, and what
+  // gn_finalize_cols consumes: frame t owns the blocks [t * stat_hw / rb, (t + 1) * stat_hw / rb) and they cover exactly its rows (section 28 of DESIGN.md).
+  // launch_gemm declines (reports rb = 0, writes nothing) when the chosen kernel cannot: split-K, ragged tiles, ...
   float2* stat_part; int stat_hw;
 };
 // tuning overrides (A/B tools and the tile-config tests; ug_tune_force sets them on ONE context, the engine copies them into every GemmP):
@@ -95,7 +98,7 @@ static inline void gemm_apply_tune(GemmP& p, const GemmTune& t) { p.tune_cfg_p1 
 void launch_gemm_mx8(const GemmP& p, hipStream_t s, int* plan_out = nullptr);   // dense only; C0 = lda and ldw in BYTES (= elements); plan_out [2] = (tile pick, group_m) as launched
 // fp16 [M, K] (row stride ldx) -> e4m3 bytes [M, K] + e8m0 scales (layout above, ld_s >= M; launch_gemm_mx8 takes ld_s % 4 == 0 and masks its fetch at ld_s); K % 128 == 0
 void launch_quant_mx8(const f16* x, long ldx, long M, int K, unsigned char* q, unsigned* scales, long ld_s, hipStream_t s);
-void launch_gemm(const GemmP& p, int batch, hipStream_t s, int* stat_rb = nullptr);   // stat_rb: rows per statistics block written (0 = none), see GemmP::stat_part
+void launch_gemm(const GemmP& p, int batch, hipStream_t s, int* stat_rb = nullptr, int* cfg_out = nullptr);   // stat_rb: rows per statistics block written (0 = none), see GemmP::stat_part; cfg_out: the tile config launched (70 - 73 / 80 where the halo-staged / streaming kernel took the planner's launch, 60 for the row-split pair)
 // weight-stationary streaming GEMM for K = 320, N in {320, 640, 960} (kernels/gemm_stream.hip; tile config 80): dense, fp16 out, bias + one residual
 bool gemm_stream_supported(const GemmP& p, int batch);
 void launch_gemm_stream(const GemmP& p, hipStream_t s);

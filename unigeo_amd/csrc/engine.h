@@ -181,6 +181,8 @@ struct Ctx {
   int ff_variant = 0, flash_variant = -1;   // ug_tune_ff / ug_tune_flash: per-context A/B overrides copied into FFusedP / FlashP (0 / -1 = the defaults)
   GemmTune tune;             // ug_tune_force: tile-config / split-K / knob overrides for THIS context's GEMM launches (tests, A/B tools)
   std::vector<int>* plan_log = nullptr;   // test_conv_bound: run_gemm appends the planner's (tile config, split factor) of every launch; null in the product
+  std::vector<int>* cfg_log = nullptr;    // test_linear_epi / test_conv_epi: run_gemm appends the tile config launch_gemm launched (the planner's, or 70 - 73 / 80 /
+                                          // 60 where the halo-staged kernel, the streaming kernel or the row-split pair took the launch); null in the product
 };
 
 void* pinned(Ctx& c, int slot, size_t bytes);   // page-locked staging buffer of at least `bytes`
@@ -225,6 +227,17 @@ void test_conv_wide(Ctx& c, const std::string& name, bool bias, const float* x, 
 Conv test_bind_conv(Ctx& c, const std::string& name, int cin, int cout, int kt, int k, bool bias, bool upsampler);
 void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l, int ups,
                      const f16* R1, float c0, float c1, int act, f16* out, long ldo, std::vector<int>* plan);
+// one launch of the engine's linear() (fp16 path: the Lin built from device tensors has no MX-fp8 copy) / conv() with the whole Epi the graphs send - the
+// time-embedding row bias2, both residuals with their leading dimensions (0: the output width) and coefficients, c0, act, flags (UG_F_GEGLU) - op-level tests
+// of the epilogue forms.  test_conv_epi: ups == 1 forms only; stat_part given: handed over as the StatPart of the launch (sized as stat_alloc sizes it), the
+// return value is the rows per statistics block the launch reported (0: it declined and wrote nothing).  plan / launched (may be NULL): the planner's (tile
+// config, split factor) and the tile config launch_gemm launched (Ctx::cfg_log), per GEMM launch.
+struct TestEpi { const f16* bias2 = nullptr; const f16* R1 = nullptr; long ldr1 = 0; float c1 = 1.f; const f16* R2 = nullptr; long ldr2 = 0; float c2 = 1.f;
+                 float c0 = 1.f; int act = 0; int flags = 0; };
+void test_linear_epi(Ctx& c, const f16* A, long M, long lda, const f16* W, const f16* bias, int in, int out, const TestEpi& te, f16* dst, long ldo,
+                     std::vector<int>* plan, std::vector<int>* launched);
+int test_conv_epi(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l,
+                  const TestEpi& te, float2* stat_part, f16* out, long ldo, std::vector<int>* plan, std::vector<int>* launched);
 // the pre-norm feed-forward of one transformer block on its own (op-level tests): the engine's ln_ff() called as transformer_forward calls it - a Lin pair
 // (W1 [8C][C] / b1 in the bound GEGLU row order, W2 [C][4C] / b2) and a Norm built from device tensors, the residual stream x' = fp16(x + addvec[row /
 // rows_per_vec]) (addvec NULL: x) as R1, optionally R2: out = c0 * FF(LayerNorm(x')) + c1 * x' + c2 * R2, through whichever of the fused kernel, its

@@ -237,7 +237,9 @@ static void run_gemm(Ctx& c, GemmP p, int batch, const char* tag, float alg = 1.
                                         (p.R1 ? (double)p.M * nout : 0.0) + (p.R2 ? (double)p.M * nout : 0.0));
     ProfScope ps(c, nm, 2.0 * p.M * p.N * (double)p.K * batch * (p.up_phase ? 2.25 : 1.0) * alg, bytes);
     if (so && so->part) { p.stat_part = so->part; p.stat_hw = p.conv ? p.Ho * p.Wo : stat_hw; }
-    launch_gemm(p, batch, c.stream, so && so->part ? &so->rb : nullptr);
+    int launched = -1;
+    launch_gemm(p, batch, c.stream, so && so->part ? &so->rb : nullptr, c.cfg_log ? &launched : nullptr);
+    if (c.cfg_log) c.cfg_log->push_back(launched);
   }
   c.ws.release(mk);
 }
@@ -1380,6 +1382,33 @@ void test_conv_bound(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x
   Epi e; e.R1 = R1; e.c0 = c0; e.c1 = c1; e.act = act;
   PlanLog log(c, plan);
   conv(c, x0, C0, x1, C1, T, H, W, cv, stride, pad_t, pad_l, ups, out, e, ldo);
+}
+// one linear() / conv() launch with every epilogue operand the graphs send (op-level tests of the epilogue forms; engine.h)
+namespace {
+struct CfgLog {    // as PlanLog, for the launched tile config
+  Ctx& c;
+  CfgLog(Ctx& c_, std::vector<int>* v) : c(c_) { c.cfg_log = v; }
+  ~CfgLog() { c.cfg_log = nullptr; }
+};
+Epi epi_of(const TestEpi& t) {
+  Epi e; e.bias2 = t.bias2; e.R1 = t.R1; e.ldr1 = t.ldr1; e.c1 = t.c1; e.R2 = t.R2; e.ldr2 = t.ldr2; e.c2 = t.c2; e.c0 = t.c0; e.act = t.act; e.flags = t.flags;
+  return e;
+}
+}
+void test_linear_epi(Ctx& c, const f16* A, long M, long lda, const f16* W, const f16* bias, int in, int out, const TestEpi& te, f16* dst, long ldo,
+                     std::vector<int>* plan, std::vector<int>* launched) {
+  Lin l; l.w = W; l.b = bias; l.in = in; l.out = out;
+  PlanLog log(c, plan); CfgLog clog(c, launched);
+  linear(c, A, M, l, dst, epi_of(te), lda, ldo);
+}
+int test_conv_epi(Ctx& c, const Conv& cv, const f16* x0, int C0, const f16* x1, int C1, int T, int H, int W, int stride, int pad_t, int pad_l,
+                  const TestEpi& te, float2* stat_part, f16* out, long ldo, std::vector<int>* plan, std::vector<int>* launched) {
+  Epi e = epi_of(te);
+  StatPart sp; sp.part = stat_part;
+  if (stat_part) e.so = &sp;
+  PlanLog log(c, plan); CfgLog clog(c, launched);
+  conv(c, x0, C0, x1, C1, T, H, W, cv, stride, pad_t, pad_l, 1, out, e, ldo);
+  return sp.rb;
 }
 // the pre-norm feed-forward of a transformer block on its own (op-level tests; engine.h): ln_ff() with the residual stream as transformer_forward hands it over
 long test_ln_ff(Ctx& c, const f16* x, long M, int C, const f16* gamma, const f16* beta, float eps, const f16* addvec, long rows_per_vec,

@@ -1441,7 +1441,7 @@ static bool cfg_geom(int cfg, int& bm, int& bn, int& wmw, int& wnw) {
   }
 }
 
-void launch_gemm(const GemmP& p0, int batch, hipStream_t s, int* stat_rb) {
+void launch_gemm(const GemmP& p0, int batch, hipStream_t s, int* stat_rb, int* cfg_out) {
   GemmP p = p0;
   if (stat_rb) *stat_rb = 0;
   if (!stat_rb) p.stat_part = nullptr;
@@ -1497,6 +1497,7 @@ void launch_gemm(const GemmP& p0, int batch, hipStream_t s, int* stat_rb) {
       b.group_m = pick_group_m(b, cb, 1, 1); b.tm_T = b.tm_nb = 0;
       launch_cfg(cb, b, 1, s);
       UG_CHECK(hipGetLastError());
+      if (cfg_out) *cfg_out = 60;
       return;
     }
   }
@@ -1555,6 +1556,7 @@ void launch_gemm(const GemmP& p0, int batch, hipStream_t s, int* stat_rb) {
     if (sdbg) fprintf(stderr, "[stat] M %d N %d K %d conv %d kt %d hw %d cfg %d split %d -> rb %d\n", p.M, p.N, p.K, p.conv, p.kt, p.stat_hw, cfg, split, ok ? wtm : 0);
     if (ok) *stat_rb = wtm; else p.stat_part = nullptr;
   }
+  if (cfg_out) *cfg_out = cfg;
   launch_cfg(cfg, p, batch, s);
   if (split > 1) {
     const long nvec = (long)p.M * (p.N / 8);
