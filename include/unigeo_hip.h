@@ -444,6 +444,50 @@ void ug_register_opts_default(ug_register_opts* o);
 int ug_prep_register_depth(ug_ctx* ctx, const unsigned short* depth_u16 /* host [T,H,W] */, int T, int H, int W,
                            const ug_register_opts* opts /* NULL: defaults */, unsigned short* out /* host [T,H,W] */);
 
+/* ScanNet++ mesh renderer on the device: depth, normals and the triangle index of a triangle mesh seen from T pinhole cameras - what the
+ * reference makes offline, through pyrender, OpenGL and two GLSL shaders, in dataset/scannetpp/preprocess_scannetpp_imu.py:470-497 to write
+ * the depth PNG and normal WebP files its loader reads.  ONE definition, evaluated identically here and by
+ * harness/render.py's render_mesh.  fl32 / fl64 are ONE IEEE operation in that type, never contracted into an FMA; a*b - c*d is two products
+ * and one difference; sums run in the order the brackets give.
+ *   inputs   verts float32 [NV,3], widened to float64; faces int32 [NF,3]; per frame world2cam = (R | T), row-major 3x4 float64, OpenCV axes
+ *            (x right, y down, z forward) and K = fx, fy, cx, cy in the convention in which pixel (col, row) looks along u = col + 0.5,
+ *            v = row + 0.5 (what the script hands to pyrender's IntrinsicsCamera); H, W; znear, zfar.
+ *   corners  p_i = R v_i + T per component as ((R_j0*x + R_j1*y) + R_j2*z) + T_j,  i = 0, 1, 2
+ *   cross    c0 = p1 x p2, c1 = p2 x p0, c2 = p0 x p1, with (a x b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x): swapping the
+ *            operands negates every component exactly, so the two triangles of a shared edge see edge values of exactly opposite sign
+ *   det      D = (p0.x*c0.x + p0.y*c0.y) + p0.z*c0.z
+ *   ray      r = (((col + 0.5) - cx) / fx, ((row + 0.5) - cy) / fy, 1)
+ *   edges    e_k = (r.x*c_k.x + r.y*c_k.y) + c_k.z,  den = (e0 + e1) + e2
+ *   covered  iff den != 0 and (e0 >= 0 and e1 >= 0 and e2 >= 0, or e0 <= 0 and e1 <= 0 and e2 <= 0) and, with z = D / den,
+ *            z >= znear and z <= zfar - double-sided, as the script's MetallicRoughnessMaterial(doubleSided=True).  All comparisons in this
+ *            positive form: a NaN drops out.  2-D homogeneous rasterisation: a triangle that crosses the camera plane needs no clipping, its
+ *            mirror image behind the camera has z < 0.
+ *   winner   per pixel the covered triangle of smallest fl32(z); equal fl32(z): the smaller triangle index (GL_LESS in draw order)
+ *   skipped  a triangle whose world normal n = (v1 - v0) x (v2 - v0) has a squared length (n.x*n.x + n.y*n.y) + n.z*n.z that is not > 0 and finite
+ *   depth    depth_mm = trunc(fl32(fl32(z) * 1000f)), 0 where no triangle covers the pixel; then 0 where mask < 255 (mask may be NULL)
+ *   normal   n / sqrt((n.x*n.x + n.y*n.y) + n.z*n.z) of the winner, negated when D > 0 (it then faces the camera);
+ *            q = floor(255 * (0.5 * n + 0.5) + 0.5);  m = (q / 255) * 2 - 1;  w_j = (R_j0*m.x + R_j1*m.y) + R_j2*m.z;  g = (w_0, -w_1, -w_2);
+ *            normal = trunc(((g + 1) / 2) * 255) clamped to 0..255; (0, 0, 0) where no triangle covers the pixel.  The mask leaves it alone.
+ *   index    tri_index = the winner, -1 where no triangle covers the pixel (optional)
+ * Which pixels a triangle is tested at is an implementation matter (a conservative screen box when all three corners lie in front of the
+ * camera, the whole frame otherwise); it never changes a result.  The minimum is ONE 64-bit integer atomicMin per covered pixel on
+ * (order-preserving key of fl32(z) << 32) | triangle index: no floating-point atomic, equal bytes from run to run.  The mesh is uploaded once
+ * per call, the frames are processed in chunks of bounded device size.
+ * ug_render_opts_default: znear 0.05, zfar 20 (the script's), flags 0.
+ * Errors (ug_last_error; the context stays usable; all are found on the host before anything is uploaded): NULL verts, faces, world2cam, K,
+ *   depth_mm or normal; NV, NF, T, H or W <= 0; NF >= 2^31; T * H * W >= 2^31; a face index outside 0..NV-1; a non-finite vertex, pose or
+ *   intrinsic; fx or fy <= 0; znear <= 0 or not finite; zfar <= znear; zfar > 65.535 (depth_mm is 16 bits of millimetres); any flag bit (none
+ *   is defined yet). */
+typedef struct {
+  double znear, zfar;   /* 0.05, 20 */
+  unsigned flags;       /* 0 */
+} ug_render_opts;
+void ug_render_opts_default(ug_render_opts* o);
+int ug_prep_render_mesh(ug_ctx* ctx, const float* verts /* host [NV,3] */, long NV, const int* faces /* host [NF,3] */, long NF,
+                        const double* world2cam /* host [T,12] */, const double* K /* host [T,4]: fx fy cx cy */, int T, int H, int W,
+                        const unsigned char* mask /* NULL or host [T,H,W] */, const ug_render_opts* opts /* NULL: defaults */,
+                        unsigned short* depth_mm /* host [T,H,W] */, unsigned char* normal /* host [T,H,W,3] */, int* tri_index /* NULL or host [T,H,W] */);
+
 /* HIP-event profiling of everything launched between begin and end; end returns a JSON
  * object {kernel_family: {ms, calls, flops, bytes}} valid until the next call on ctx. */
 int ug_profile_begin(ug_ctx* ctx);

@@ -33,7 +33,7 @@ EXPORTS = [
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
     "ug_pointmap_opts_default", "ug_pointmap_focal", "ug_pointmap_poses",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
-    "ug_register_opts_default", "ug_prep_register_depth",
+    "ug_register_opts_default", "ug_prep_register_depth", "ug_render_opts_default", "ug_prep_render_mesh",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -81,6 +81,10 @@ class PointmapOptsC(C.Structure):
 class RegisterOptsC(C.Structure):
     _fields_ = [("src_focal", C.c_double), ("dst_focal", C.c_double), ("src2dst", C.c_double * 12), ("divisor", C.c_float),
                 ("max_valid", C.c_float), ("flags", C.c_uint)]
+
+
+class RenderOptsC(C.Structure):
+    _fields_ = [("znear", C.c_double), ("zfar", C.c_double), ("flags", C.c_uint)]
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3, "l1": 4}    # UG_ALIGN_* of include/unigeo_hip.h
@@ -185,6 +189,10 @@ def load_library():
                         "ug_prep_gt_ex": [vp, vp, C.c_float, vp, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, vp, vp, vp, vp, vp, C.c_uint]})
     _set_argtypes(lib, {"ug_register_opts_default": [C.POINTER(RegisterOptsC)],
                         "ug_prep_register_depth": [vp, vp, ip, ip, ip, C.POINTER(RegisterOptsC), vp]})
+    _set_argtypes(lib, {"ug_render_opts_default": [C.POINTER(RenderOptsC)],
+                        "ug_prep_render_mesh": [vp, vp, C.c_long, vp, C.c_long, vp, vp, ip, ip, ip, vp, C.POINTER(RenderOptsC), vp, vp, vp]})
+    if hasattr(lib, "ug_render_opts_default"):
+        lib.ug_render_opts_default.restype = None
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -1098,6 +1106,28 @@ class Engine:
         out = np.empty((T, H, W), np.uint16)
         self._ck(self.lib.ug_prep_register_depth(self.ctx, _ptr(clip), T, H, W, C.byref(o), _ptr(out)))
         return out if d.ndim == 3 else out[0]
+
+    def prep_render_mesh(self, verts, faces, cam_to_world, K, H, W, masks=None, znear=None, zfar=None, with_index=True):
+        """A triangle mesh rendered from T cameras on the device (``ug_prep_render_mesh``): the arguments and the result
+        ``(depth_mm uint16 [T,H,W], normal uint8 [T,H,W,3], tri_index int32 [T,H,W])`` of ``harness.render.render_mesh``, byte for byte.
+        ``cam_to_world`` is inverted here with ``numpy.linalg.inv``, as the mirror does; ``znear`` / ``zfar`` ``None``: the library's defaults
+        (0.05, 20).  ``with_index=False`` passes ``tri_index = NULL`` and returns ``None`` in its place."""
+        from .harness.render import check_masks, check_render_args, intrinsics4, world2cam_from
+        o = RenderOptsC()
+        self.lib.ug_render_opts_default(C.byref(o))
+        if znear is not None:
+            o.znear = float(znear)
+        if zfar is not None:
+            o.zfar = float(zfar)
+        m = world2cam_from(cam_to_world)
+        T = len(m)
+        v, f, m, k = check_render_args(verts, faces, m, intrinsics4(K, T), H, W, o.znear, o.zfar, who="prep_render_mesh")
+        mk = check_masks(masks, T, H, W, who="prep_render_mesh")
+        depth = np.empty((T, H, W), np.uint16); normal = np.empty((T, H, W, 3), np.uint8)
+        index = np.empty((T, H, W), np.int32) if with_index else None
+        self._ck(self.lib.ug_prep_render_mesh(self.ctx, _ptr(v), len(v), _ptr(f), len(f), _ptr(m), _ptr(k), T, H, W, _ptr(mk), C.byref(o),
+                                              _ptr(depth), _ptr(normal), _ptr(index)))
+        return depth, normal, index
 
     # ---- ops (parity tests)
     def op_linear(self, A, W, bias=None, R1=None, c0=1.0, c1=1.0, act=0, geglu=False):

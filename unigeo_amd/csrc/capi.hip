@@ -1054,4 +1054,70 @@ int ug_prep_register_depth(ug_ctx* x, const unsigned short* depth, int T, int H,
   });
 }
 
+// ---------------------------------------------------------------- ScanNet++ mesh renderer (kernels/render.hip)
+void ug_render_opts_default(ug_render_opts* o) {
+  if (!o) return;
+  o->znear = 0.05; o->zfar = 20.0; o->flags = 0;      // preprocess_scannetpp_imu.py:340-341
+}
+
+int ug_prep_render_mesh(ug_ctx* x, const float* verts, long NV, const int* faces, long NF, const double* world2cam, const double* K, int T, int H,
+                        int W, const unsigned char* mask, const ug_render_opts* opts, unsigned short* depth_mm, unsigned char* normal,
+                        int* tri_index) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    ug_render_opts o;
+    if (opts) o = *opts; else ug_render_opts_default(&o);
+    if (o.flags) {
+      char hex[16]; snprintf(hex, sizeof hex, "0x%x", o.flags);
+      throw std::runtime_error(std::string("ug_prep_render_mesh: unknown flag bits ") + hex + " (none is defined)");
+    }
+    UG_REQUIRE(verts && faces && world2cam && K && depth_mm && normal, "verts, faces, world2cam, K, depth_mm and normal must not be NULL");
+    UG_REQUIRE(NV > 0 && NF > 0 && T > 0 && H > 0 && W > 0, "NV, NF, T, H and W must be positive");
+    UG_REQUIRE(NF < (1L << 31) && NV < (1L << 31), "NF and NV must stay below 2^31");
+    UG_REQUIRE((long)T * H * W < (1L << 31), "T * H * W must stay below 2^31");
+    UG_REQUIRE(std::isfinite(o.znear) && o.znear > 0, "znear must be finite and positive");
+    UG_REQUIRE(std::isfinite(o.zfar) && o.zfar > o.znear, "zfar must be finite and larger than znear");
+    UG_REQUIRE(o.zfar <= 65.535, "zfar must not exceed 65.535: depth_mm holds 16 bits of millimetres");
+    for (long i = 0; i < (long)T * 12; ++i) UG_REQUIRE(std::isfinite(world2cam[i]), "world2cam must be finite");
+    for (long i = 0; i < (long)T * 4; ++i) UG_REQUIRE(std::isfinite(K[i]), "K (fx, fy, cx, cy) must be finite");
+    for (int t = 0; t < T; ++t) UG_REQUIRE(K[4 * t] > 0 && K[4 * t + 1] > 0, "fx and fy must be positive");
+    for (long i = 0; i < NV * 3; ++i) UG_REQUIRE(std::isfinite(verts[i]), "a vertex is not finite");
+    for (long i = 0; i < NF * 3; ++i) UG_REQUIRE(faces[i] >= 0 && faces[i] < NV, "a face index lies outside 0..NV-1");
+    std::vector<double> tab((size_t)T * 16);
+    for (int t = 0; t < T; ++t) {
+      memcpy(tab.data() + (size_t)t * 16, world2cam + (size_t)t * 12, 12 * sizeof(double));
+      memcpy(tab.data() + (size_t)t * 16 + 12, K + (size_t)t * 4, 4 * sizeof(double));
+    }
+    float* dv = c.ws.get<float>(NV * 3); UG_CHECK(hipMemcpy(dv, verts, (size_t)NV * 12, hipMemcpyHostToDevice));      // the mesh: once per call
+    int* df = c.ws.get<int>(NF * 3); UG_CHECK(hipMemcpy(df, faces, (size_t)NF * 12, hipMemcpyHostToDevice));
+    double* dcam = c.ws.get<double>((long)T * 16); UG_CHECK(hipMemcpy(dcam, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+    const size_t px_f = (size_t)H * W;
+    const int Tc = prep_chunk_frames(T, px_f * 18);      // per pixel: an 8-byte z-buffer word, 2 + 3 + 4 bytes out, 1 byte of mask
+    const size_t px_c = px_f * Tc;
+    RenderBufs b;
+    b.big_cap = 2u << 20;      // entries of the large-box list, 12 bytes each; a box that finds it full is walked by its own thread
+    b.zbuf = (unsigned long long*)c.ws.alloc(px_c * 8);
+    b.big_id = (long long*)c.ws.alloc((size_t)b.big_cap * 8);
+    b.big_tile = c.ws.get<int>((long)b.big_cap);
+    b.big_count = (unsigned long long*)c.ws.alloc(8);
+    b.depth = (unsigned short*)c.ws.alloc(px_c * 2);
+    b.normal = (unsigned char*)c.ws.alloc(px_c * 3);
+    b.tri = tri_index ? c.ws.get<int>((long)px_c) : nullptr;
+    unsigned char* dm = mask ? (unsigned char*)c.ws.alloc(px_c) : nullptr;
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+      const int tc = std::min(Tc, T - t0);
+      if (mask) { UG_CHECK(hipMemcpy(dm, mask + px_f * t0, px_f * tc, hipMemcpyHostToDevice)); }
+      ProfRec r; r.name = "render_mesh"; r.flops = 0; r.bytes = (double)px_f * tc * 25;      // fill 8, resolve 8 + 9 per pixel; the splat's traffic depends on the view
+      if (c.prof_on) { UG_CHECK(hipEventCreate(&r.e0)); UG_CHECK(hipEventCreate(&r.e1)); UG_CHECK(hipEventRecord(r.e0, c.stream)); }
+      launch_render_mesh(dv, df, NF, dcam + (size_t)t0 * 16, tc, H, W, o.znear, o.zfar, dm, b, c.stream);
+      if (c.prof_on) { UG_CHECK(hipEventRecord(r.e1, c.stream)); c.prof.push_back(r); }
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      UG_CHECK(hipMemcpy(depth_mm + px_f * t0, b.depth, px_f * 2 * tc, hipMemcpyDeviceToHost));
+      UG_CHECK(hipMemcpy(normal + px_f * 3 * t0, b.normal, px_f * 3 * tc, hipMemcpyDeviceToHost));
+      if (tri_index) { UG_CHECK(hipMemcpy(tri_index + px_f * t0, b.tri, px_f * 4 * tc, hipMemcpyDeviceToHost)); }
+    }
+  });
+}
+
 }  // extern "C"

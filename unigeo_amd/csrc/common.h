@@ -440,3 +440,13 @@ void launch_prep_gt(const unsigned short* depth, const unsigned char* normals, c
 // device; m: the source-to-target transform, row-major 3x4
 struct RegArgs { double src_focal, dst_focal; double m[12]; float divisor, max_valid; int drop_sentinel; };
 void launch_register_depth(const unsigned short* depth, int T, int H, int W, const RegArgs& a, unsigned* zbuf, unsigned short* out, hipStream_t s);
+// ScanNet++ mesh renderer (kernels/render.hip).  verts [NV,3] float32, faces [NF,3] int32 (every index validated by the
+// caller), cams 16 doubles per frame = world-to-camera row-major 3x4, fx, fy, cx, cy; mask NULL or [T,H,W]; zbuf: T*H*W 64-bit words of
+// scratch; big_id / big_tile: big_cap entries of scratch for the boxes a whole workgroup walks, big_count one word; depth [T,H,W],
+// normal [T,H,W,3], tri NULL or [T,H,W].  All on the device; T * H * W < 2^31, NF < 2^31.
+struct RenderBufs {
+  unsigned long long* zbuf; long long* big_id; int* big_tile; unsigned long long* big_count; unsigned big_cap;
+  unsigned short* depth; unsigned char* normal; int* tri;
+};
+void launch_render_mesh(const float* verts, const int* faces, long NF, const double* cams, int T, int H, int W, double znear, double zfar,
+                        const unsigned char* mask, const RenderBufs& b, hipStream_t s);

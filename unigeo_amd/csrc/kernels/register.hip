@@ -11,15 +11,12 @@
 // Addresses: a source pixel reads depth[i] with i < n; its target index is t * H * W + yi * W + xi with 0 <= yi < H and 0 <= xi < W tested
 // in the positive form (a NaN fails it and is dropped), so it stays inside frame t of the z-buffer.
 #include "../common.h"
+#include "zkey.h"      // reg_key / reg_unkey: the order-preserving key of a float32, shared with render.hip
 
 #pragma clang fp contract(off)
 
 #define RB 256       // threads per block
 #define RMAXB 2048   // grid cap; the loops below stride over the rest
-
-// float32 -> uint32 whose unsigned order is the float order (-inf < ... < -0 < +0 < ... < +inf); NaN never reaches it
-__device__ __forceinline__ unsigned reg_key(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float reg_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 __global__ __launch_bounds__(RB) void k_reg_fill(unsigned* __restrict__ zbuf, long n, float init) {
   const unsigned k = reg_key(init);

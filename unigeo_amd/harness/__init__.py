@@ -12,6 +12,8 @@ from .scannetpp import ScannetPPDataset, ScannetPPSequence
 from .rgbd import (RGBDClipDataset, RGBDSequence, ScannetV2Dataset, bonnDataset, neuralRGBDDataset, read_tum_trajectory, replicaDataset,
                    sevenScenesDataset, RegisterOpts, register_depth)
 from .distributed import evaluate_sharded
+from .ply import read_ply_mesh, write_ply_mesh
+from .render import render_mesh, rescaled_size_and_intrinsics
 from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, read_ply, save_depth_normal_maps, write_ply
 
 __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_evaluation_in_global_coord",
@@ -22,4 +24,5 @@ __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_eval
            "read_tum_trajectory", "RegisterOpts", "register_depth",
            "camera_pose_evaluation", "tum_poses", "write_tum_trajectory", "save_camera_trajectories",
            "pointmap_focal", "pointmap_poses", "poses_from_pointmap",
-           "SPECTRAL_R_LUT", "colorbar_strip", "colorize", "panels_u8", "save_depth_normal_maps", "write_ply", "read_ply"]
+           "SPECTRAL_R_LUT", "colorbar_strip", "colorize", "panels_u8", "save_depth_normal_maps", "write_ply", "read_ply",
+           "read_ply_mesh", "write_ply_mesh", "render_mesh", "rescaled_size_and_intrinsics"]
