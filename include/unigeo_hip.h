@@ -410,6 +410,50 @@ int ug_prep_gt_ex(ug_ctx* ctx, const unsigned short* depth_u16 /* [T,Hi,Wi] */, 
                   const int* col_idx /* [Wo] */, int Wo, float max_depth, float* cam_normal_out, float* cam_coord_out, float* world_normal_out,
                   float* world_coord_out, float* mask_out, unsigned flags);
 
+/* Ground-truth normals for the loaders that have none (7-Scenes, Bonn, NeuralRGBD, Replica, ScanNetv2; harness/rgbd.py `normals="depth"`;
+ * DESIGN.md section 30): a plane fit to the back-projected depth, the reference's get_surface_normal_np (utils/geometry_utils.py:73-134, as
+ * test_vis_dataset.py uses it on 7-Scenes) with a masked window, an edge test and a validity mask.  The inputs, the tables, the two flags and
+ * the back-projection are ug_prep_gt_ex's: p(v, u) = cam_coord and bad(v, u) of NATIVE pixel (v, u) as documented above, computed by the same
+ * device function.  The fit runs on the full native frame and is produced only at the picked pixels (v, u) = (row_idx[oy], col_idx[ox]).
+ * ONE definition, evaluated identically here and by harness/normals.py's fit_normals.  Below the float32 points are widened to float64, every
+ * operation is ONE IEEE float64 operation, never contracted into an FMA, in the order the brackets give, and every sum runs left to right
+ * from +0:
+ *   centre   pc = p(v, u), dc = -pc.z.  bad(v, u): the pixel is invalid.
+ *   window   offsets (dy, dx), dy = -r..r outer, dx = -r..r inner (row-major); q = (v + dy, u + dx) is absent outside 0 <= row < Hi,
+ *            0 <= col < Wi; it takes part iff !bad(q) and, with edge >= 0, |(-p(q).z) - dc| <= edge * dc.  The centre always takes part.
+ *   sums     cnt = number of participants;  Sxx = sum x*x, Sxy = sum x*y, Sxz = sum x*z, Syy = sum y*y, Syz = sum y*z, Szz = sum z*z;
+ *            sx = sum x, sy = sum y, sz = sum z  over the participants' (x, y, z) = p(q).  cnt < min_count: the pixel is invalid.
+ *   system   c = double(cnt);  axx = Sxx/c + 1e-6, ayy = Syy/c + 1e-6, azz = Szz/c + 1e-6, axy = Sxy/c, axz = Sxz/c, ayz = Syz/c;
+ *            bx = sx/c, by = sy/c, bz = sz/c  (with the full 5 x 5 window the reference's ATA + 1e-6 I and AT1)
+ *   adjugate c00 = ayy*azz - ayz*ayz,  c01 = axz*ayz - axy*azz,  c02 = axy*ayz - axz*ayy,
+ *            c11 = axx*azz - axz*axz,  c12 = axy*axz - axx*ayz,  c22 = axx*ayy - axy*axy   (each two products and one difference)
+ *   solve    det = (axx*c00 + axy*c01) + axz*c02
+ *            n0 = ((c00*bx + c01*by) + c02*bz) / det,  n1 = ((c01*bx + c11*by) + c12*bz) / det,  n2 = ((c02*bx + c12*by) + c22*bz) / det
+ *   unit     den = sqrt((n0*n0 + n1*n1) + n2*n2) + 1e-6;  n = (n0/den, n1/den, n2/den)   (the reference's n / (|n| + 1e-6))
+ *   orient   n = -n where (n0*pc.x + n1*pc.y) + n2*pc.z > 0: the normal faces the camera
+ *   valid    iff the centre is valid, cnt >= min_count and n0, n1, n2 are finite
+ *   outputs  cam_normal = fl32(n);  world_normal_j = fl32((m_j0*g0 + m_j1*g1) + m_j2*g2) with g = cam_normal widened and m = M33 of the
+ *            frame's cam2key_t44, rounded once;  normal_mask = 1.  An invalid pixel gives +0 in all seven values.  UG_PREP_ZOOMED: a -0
+ *            comes out as +0, as in ug_prep_gt_ex; without it the sign of a zero is kept.
+ * ug_gt_normals_opts: radius r in 1..8 (2 = the reference's patch_size 5); edge < 0 switches the edge test off; min_count 0 = the majority of
+ *   the full window, (2r+1)^2 / 2 + 1 (integer division).  ug_gt_normals_opts_default: 2, 0.05, 0.  edge and the majority count are design
+ *   choices, not measurements; opts NULL: the defaults.
+ * Outputs are host float32: cam_normal / world_normal [T,3,Ho,Wo], normal_mask [T,Ho,Wo].  One thread per picked pixel walks its window; no
+ * atomics.  The clip is processed in chunks of frames of bounded device size.
+ * Errors (ug_last_error; the context stays usable; all are found on the host before anything is uploaded): a NULL required pointer; T or a
+ *   size <= 0; a row or column index outside the source; radius outside 1..8; a NaN edge; a negative min_count; a flag bit other than
+ *   UG_PREP_DEPTH_F64 | UG_PREP_ZOOMED (the bits are named); 2^31 output elements (T * 3 * Ho * Wo) or more. */
+typedef struct {
+  int radius;      /* 2 */
+  double edge;     /* 0.05; negative: off */
+  int min_count;   /* 0: (2 * radius + 1)^2 / 2 + 1 */
+} ug_gt_normals_opts;
+void ug_gt_normals_opts_default(ug_gt_normals_opts* o);
+int ug_prep_gt_normals(ug_ctx* ctx, const unsigned short* depth_u16 /* [T,Hi,Wi] */, float depth_divisor, const float* intrinsics_t33,
+                       const float* cam2key_t44, int T, int Hi, int Wi, const int* row_idx /* [Ho] */, int Ho, const int* col_idx /* [Wo] */,
+                       int Wo, float max_depth, const ug_gt_normals_opts* opts /* NULL: defaults */, float* cam_normal_out,
+                       float* world_normal_out, float* normal_mask_out, unsigned flags);
+
 /* 7-Scenes depth registration on the device: the raw Kinect depth image warped into the colour camera - what the reference does once, offline,
  * in dataset/sevenScenes/preprocess.py:82-140, to write the *.depth.proj.png files its loader reads.  A forward splat
  * with a z-buffer.  depth_u16 / out: host uint16 [T,H,W]; the output has the input's size and both principal points sit at the image centre.

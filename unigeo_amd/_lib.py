@@ -34,6 +34,7 @@ EXPORTS = [
     "ug_pointmap_opts_default", "ug_pointmap_focal", "ug_pointmap_poses",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_register_opts_default", "ug_prep_register_depth", "ug_render_opts_default", "ug_prep_render_mesh",
+    "ug_gt_normals_opts_default", "ug_prep_gt_normals",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -85,6 +86,10 @@ class RegisterOptsC(C.Structure):
 
 class RenderOptsC(C.Structure):
     _fields_ = [("znear", C.c_double), ("zfar", C.c_double), ("flags", C.c_uint)]
+
+
+class GtNormalsOptsC(C.Structure):
+    _fields_ = [("radius", C.c_int), ("edge", C.c_double), ("min_count", C.c_int)]
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3, "l1": 4}    # UG_ALIGN_* of include/unigeo_hip.h
@@ -193,6 +198,11 @@ def load_library():
                         "ug_prep_render_mesh": [vp, vp, C.c_long, vp, C.c_long, vp, vp, ip, ip, ip, vp, C.POINTER(RenderOptsC), vp, vp, vp]})
     if hasattr(lib, "ug_render_opts_default"):
         lib.ug_render_opts_default.restype = None
+    _set_argtypes(lib, {"ug_gt_normals_opts_default": [C.POINTER(GtNormalsOptsC)],
+                        "ug_prep_gt_normals": [vp, vp, C.c_float, vp, vp, ip, ip, ip, vp, ip, vp, ip, C.c_float, C.POINTER(GtNormalsOptsC), vp, vp, vp,
+                                               C.c_uint]})
+    if hasattr(lib, "ug_gt_normals_opts_default"):
+        lib.ug_gt_normals_opts_default.restype = None
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -1081,6 +1091,33 @@ class Engine:
         self._ck(self.lib.ug_prep_gt_ex(self.ctx, _ptr(d), float(depth_divisor), _ptr(n), _ptr(k), _ptr(m), T, Hi, Wi, _ptr(ri), Ho, _ptr(ci), Wo,
                                         float(max_depth), _ptr(cn), _ptr(cc), _ptr(wn), _ptr(wc), _ptr(mask), flags))
         return cn, cc, wn, wc, mask
+
+    def prep_gt_normals(self, depth_u16, intrinsics, cam2key, row_idx, col_idx, depth_divisor=1000.0, max_depth=80.0, depth_f64=False,
+                        zoomed=None, radius=2, edge=0.05, min_count=None):
+        """Normals fitted from the depth at the picked source pixels on the device (``ug_prep_gt_normals``) ->
+        ``(cam_normal, world_normal, normal_mask)``, float32 ``[T,3,Ho,Wo]`` x 2 and ``[T,Ho,Wo]``: bit-equal to
+        ``harness.normals.fit_normals`` on the full native frame followed by ``world_normals`` and the pick.  The depth, the cameras, the
+        tables, ``depth_f64`` and ``zoomed`` are ``prep_gt``'s; ``radius`` (1..8), ``edge`` (``None``: the edge test off) and ``min_count``
+        (``None``: the majority of the window) are ``fit_normals``'s, checked here the way it checks them."""
+        from .harness.normals import check_fit_options
+        radius, edge, min_count = check_fit_options(radius, edge, min_count, "prep_gt_normals")
+        d = np.asarray(depth_u16)
+        if d.dtype != np.uint16 or d.ndim != 3:
+            raise ValueError("prep_gt_normals: depth must be uint16 [T,Hi,Wi]")
+        d = np.ascontiguousarray(d)
+        T, Hi, Wi = d.shape
+        k, m = _f32(intrinsics).reshape(T, 3, 3), _f32(cam2key).reshape(T, 4, 4)
+        ri, ci = np.ascontiguousarray(row_idx, dtype=np.int32).reshape(-1), np.ascontiguousarray(col_idx, dtype=np.int32).reshape(-1)
+        Ho, Wo = ri.size, ci.size
+        cn, wn = (np.empty((T, 3, Ho, Wo), np.float32) for _ in range(2))
+        nm = np.empty((T, Ho, Wo), np.float32)
+        if zoomed is None:
+            zoomed = (Ho, Wo) != (Hi, Wi)
+        flags = (PREP_DEPTH_F64 if depth_f64 else 0) | (PREP_ZOOMED if zoomed else 0)
+        o = GtNormalsOptsC(radius, -1.0 if edge is None else edge, min_count)
+        self._ck(self.lib.ug_prep_gt_normals(self.ctx, _ptr(d), float(depth_divisor), _ptr(k), _ptr(m), T, Hi, Wi, _ptr(ri), Ho, _ptr(ci), Wo,
+                                             float(max_depth), C.byref(o), _ptr(cn), _ptr(wn), _ptr(nm), flags))
+        return cn, wn, nm
 
     def prep_register_depth(self, depth_u16, opts=None, invalid="keep"):
         """Raw depth warped into the colour camera on the device (``ug_prep_register_depth``): uint16 ``[T,H,W]`` or

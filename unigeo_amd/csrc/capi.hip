@@ -943,6 +943,23 @@ int ug_prep_resize_frames(ug_ctx* x, const unsigned char* frames, int T, int Hi,
   });
 }
 
+// What ug_prep_gt_ex and ug_prep_gt_normals share: the pick tables, checked against the source size before anything is uploaded, and the
+// per-frame camera table (20 doubles: fx, fy, cx, cy, M33 row-major, t3, 4 unused) on the device
+static void prep_upload_cameras(Ctx& c, const float* K, const float* M, int T, const int* row_idx, int Ho, int Hi, const int* col_idx, int Wo, int Wi,
+                                double** dcam, int** dri, int** dci) {
+  for (int i = 0; i < Ho; ++i) UG_REQUIRE(row_idx[i] >= 0 && row_idx[i] < Hi, "a row index lies outside the source");
+  for (int i = 0; i < Wo; ++i) UG_REQUIRE(col_idx[i] >= 0 && col_idx[i] < Wi, "a column index lies outside the source");
+  std::vector<double> tab((size_t)T * 20, 0.0);
+  for (int f = 0; f < T; ++f) {
+    const float* k = K + (size_t)f * 9; const float* m = M + (size_t)f * 16; double* q = tab.data() + (size_t)f * 20;
+    q[0] = k[0]; q[1] = k[4]; q[2] = k[2]; q[3] = k[5];
+    for (int r = 0; r < 3; ++r) { for (int j = 0; j < 3; ++j) q[4 + r * 3 + j] = m[r * 4 + j]; q[13 + r] = m[r * 4 + 3]; }
+  }
+  *dcam = c.ws.get<double>((long)T * 20); UG_CHECK(hipMemcpy(*dcam, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+  *dri = c.ws.get<int>(Ho); UG_CHECK(hipMemcpy(*dri, row_idx, (size_t)Ho * 4, hipMemcpyHostToDevice));
+  *dci = c.ws.get<int>(Wo); UG_CHECK(hipMemcpy(*dci, col_idx, (size_t)Wo * 4, hipMemcpyHostToDevice));
+}
+
 int ug_prep_gt_ex(ug_ctx* x, const unsigned short* depth, float depth_divisor, const unsigned char* normals, const float* K, const float* M, int T,
                   int Hi, int Wi, const int* row_idx, int Ho, const int* col_idx, int Wo, float max_depth, float* cam_normal, float* cam_coord,
                   float* world_normal, float* world_coord, float* mask, unsigned flags) {
@@ -958,17 +975,8 @@ int ug_prep_gt_ex(ug_ctx* x, const unsigned short* depth, float depth_divisor, c
     UG_REQUIRE(!normals || (cam_normal && world_normal), "cam_normal and world_normal must not be NULL when normals are given");
     UG_REQUIRE(T > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "T and the sizes must be positive");
     UG_REQUIRE((long)T * 3 * Ho * Wo < (1L << 31), "the outputs must stay below 2^31 elements");
-    for (int i = 0; i < Ho; ++i) UG_REQUIRE(row_idx[i] >= 0 && row_idx[i] < Hi, "a row index lies outside the source");
-    for (int i = 0; i < Wo; ++i) UG_REQUIRE(col_idx[i] >= 0 && col_idx[i] < Wi, "a column index lies outside the source");
-    std::vector<double> tab((size_t)T * 20, 0.0);      // per frame: fx, fy, cx, cy, M33 row-major, t3
-    for (int f = 0; f < T; ++f) {
-      const float* k = K + (size_t)f * 9; const float* m = M + (size_t)f * 16; double* q = tab.data() + (size_t)f * 20;
-      q[0] = k[0]; q[1] = k[4]; q[2] = k[2]; q[3] = k[5];
-      for (int r = 0; r < 3; ++r) { for (int j = 0; j < 3; ++j) q[4 + r * 3 + j] = m[r * 4 + j]; q[13 + r] = m[r * 4 + 3]; }
-    }
-    double* dcam = c.ws.get<double>((long)T * 20); UG_CHECK(hipMemcpy(dcam, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
-    int* dri = c.ws.get<int>(Ho); UG_CHECK(hipMemcpy(dri, row_idx, (size_t)Ho * 4, hipMemcpyHostToDevice));
-    int* dci = c.ws.get<int>(Wo); UG_CHECK(hipMemcpy(dci, col_idx, (size_t)Wo * 4, hipMemcpyHostToDevice));
+    double* dcam; int* dri; int* dci;
+    prep_upload_cameras(c, K, M, T, row_idx, Ho, Hi, col_idx, Wo, Wi, &dcam, &dri, &dci);
     const size_t src_f = (size_t)Hi * Wi, px_f = (size_t)Ho * Wo;
     const int Tc = prep_chunk_frames(T, src_f * (normals ? 5 : 2) + px_f * 13 * 4);
     unsigned short* dd = (unsigned short*)c.ws.alloc(src_f * 2 * Tc);
@@ -1001,6 +1009,63 @@ int ug_prep_gt(ug_ctx* x, const unsigned short* depth, float depth_divisor, cons
                float* world_normal, float* world_coord, float* mask) {
   return ug_prep_gt_ex(x, depth, depth_divisor, normals, K, M, T, Hi, Wi, row_idx, Ho, col_idx, Wo, max_depth, cam_normal, cam_coord, world_normal,
                        world_coord, mask, (Ho != Hi || Wo != Wi) ? UG_PREP_ZOOMED : 0);
+}
+
+// ---------------------------------------------------------------- normals fitted from the depth (kernels/gt_normals.hip)
+void ug_gt_normals_opts_default(ug_gt_normals_opts* o) {
+  if (!o) return;
+  o->radius = 2; o->edge = 0.05; o->min_count = 0;      // radius 2 = the reference's patch_size 5; edge and the majority count are design choices
+}
+
+int ug_prep_gt_normals(ug_ctx* x, const unsigned short* depth, float depth_divisor, const float* K, const float* M, int T, int Hi, int Wi,
+                       const int* row_idx, int Ho, const int* col_idx, int Wo, float max_depth, const ug_gt_normals_opts* opts, float* cam_normal,
+                       float* world_normal, float* normal_mask, unsigned flags) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    ug_gt_normals_opts o;
+    if (opts) o = *opts; else ug_gt_normals_opts_default(&o);
+    const unsigned unknown = flags & ~(unsigned)(UG_PREP_DEPTH_F64 | UG_PREP_ZOOMED);
+    if (unknown) {
+      char hex[16]; snprintf(hex, sizeof hex, "0x%x", unknown);
+      throw std::runtime_error(std::string("ug_prep_gt_normals: unknown flag bits ") + hex + " (UG_PREP_DEPTH_F64 | UG_PREP_ZOOMED)");
+    }
+    UG_REQUIRE(depth && K && M && row_idx && col_idx, "depth, intrinsics, cam2key, row_idx and col_idx must not be NULL");
+    UG_REQUIRE(cam_normal && world_normal && normal_mask, "cam_normal, world_normal and normal_mask must not be NULL");
+    UG_REQUIRE(T > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "T and the sizes must be positive");
+    UG_REQUIRE(o.radius >= 1 && o.radius <= 8, "radius must lie in 1..8");
+    UG_REQUIRE(o.edge == o.edge, "edge must not be NaN (negative: the edge test is off)");
+    UG_REQUIRE(o.min_count >= 0, "min_count must not be negative (0: the majority of the window)");
+    UG_REQUIRE((long)T * 3 * Ho * Wo < (1L << 31), "the outputs must stay below 2^31 elements");
+    double* dcam; int* dri; int* dci;
+    prep_upload_cameras(c, K, M, T, row_idx, Ho, Hi, col_idx, Wo, Wi, &dcam, &dri, &dci);
+    const size_t src_f = (size_t)Hi * Wi, px_f = (size_t)Ho * Wo;
+    const int Tc = prep_chunk_frames(T, src_f * 2 + px_f * 7 * 4);
+    unsigned short* dd = (unsigned short*)c.ws.alloc(src_f * 2 * Tc);
+    float* o_cn = c.ws.get<float>((long)(px_f * 3 * Tc));
+    float* o_wn = c.ws.get<float>((long)(px_f * 3 * Tc));
+    float* o_m = c.ws.get<float>((long)(px_f * Tc));
+    GtNormalsArgs a;
+    a.row_idx = dri; a.col_idx = dci; a.cam_normal = o_cn; a.world_normal = o_wn; a.normal_mask = o_m;
+    a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo; a.zoomed = (flags & UG_PREP_ZOOMED) != 0; a.depth_f64 = (flags & UG_PREP_DEPTH_F64) != 0;
+    a.divisor = depth_divisor; a.max_depth = max_depth; a.radius = o.radius;
+    a.min_count = o.min_count > 0 ? o.min_count : (2 * o.radius + 1) * (2 * o.radius + 1) / 2 + 1;
+    a.edge_on = o.edge >= 0; a.edge = o.edge;
+    for (int t0 = 0; t0 < T; t0 += Tc) {
+      const int tc = std::min(Tc, T - t0);
+      UG_CHECK(hipMemcpy(dd, depth + src_f * t0, src_f * 2 * tc, hipMemcpyHostToDevice));
+      a.depth = dd; a.cam = dcam + (size_t)t0 * 20; a.n = (long)px_f * tc;
+      ProfRec r; r.name = "gt_normals"; r.flops = 0; r.bytes = (double)src_f * tc * 2 + (double)px_f * tc * 28;      // under ug_profile_begin only
+      if (c.prof_on) { UG_CHECK(hipEventCreate(&r.e0)); UG_CHECK(hipEventCreate(&r.e1)); UG_CHECK(hipEventRecord(r.e0, c.stream)); }
+      launch_prep_gt_normals(a, c.stream);
+      if (c.prof_on) { UG_CHECK(hipEventRecord(r.e1, c.stream)); c.prof.push_back(r); }
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      const size_t n3 = px_f * 3 * tc * 4, off3 = px_f * 3 * t0;
+      UG_CHECK(hipMemcpy(cam_normal + off3, o_cn, n3, hipMemcpyDeviceToHost));
+      UG_CHECK(hipMemcpy(world_normal + off3, o_wn, n3, hipMemcpyDeviceToHost));
+      UG_CHECK(hipMemcpy(normal_mask + px_f * t0, o_m, px_f * tc * 4, hipMemcpyDeviceToHost));
+    }
+  });
 }
 
 // ---------------------------------------------------------------- 7-Scenes depth registration (kernels/register.hip)

@@ -436,6 +436,16 @@ void launch_prep_resize(const unsigned char* frames, const int* ridx, const doub
 void launch_prep_gt(const unsigned short* depth, const unsigned char* normals, const double* cam, const int* row_idx, const int* col_idx, int T,
                     int Hi, int Wi, int Ho, int Wo, float divisor, float max_depth, int depth_f64, int zoomed, float* cam_normal, float* world_normal,
                     float* cam_coord, float* world_coord, float* mask, hipStream_t s);
+// Ground-truth normals fitted from the depth at the picked pixels (kernels/gt_normals.hip).  depth [T,Hi,Wi] uint16, cam
+// and the tables as launch_prep_gt takes them, the outputs [T,3,Ho,Wo] x 2 and [T,Ho,Wo]; all on the device, n = T * Ho * Wo.  The caller
+// has validated the tables, 1 <= radius <= 8 and min_count >= 1; edge is read only when edge_on.
+struct GtNormalsArgs {
+  const unsigned short* depth; const double* cam; const int* row_idx; const int* col_idx;
+  float* cam_normal; float* world_normal; float* normal_mask;
+  long n; int Hi, Wi, Ho, Wo; int zoomed, depth_f64; float divisor, max_depth;
+  int radius, min_count, edge_on; double edge;
+};
+void launch_prep_gt_normals(const GtNormalsArgs& a, hipStream_t s);
 // 7-Scenes depth registration (kernels/register.hip): depth / out uint16 [T,H,W], zbuf T*H*W words of scratch, all on the
 // device; m: the source-to-target transform, row-major 3x4
 struct RegArgs { double src_focal, dst_focal; double m[12]; float divisor, max_valid; int drop_sentinel; };

@@ -5,6 +5,7 @@
 // computes a coordinate or mirrors an index, it gathers what the table names.  The tables are validated before upload (0 <= idx < n_in), and
 // every other address is an affine function of the thread's own output index.
 #include "../common.h"
+#include "prep_point.h"      // prep_point: the back-projection of one depth pixel and the loaders' `bad` rule
 
 #define PB 256       // threads per block
 #define PMAXB 1024   // grid cap; the loops below stride over the rest
@@ -78,11 +79,8 @@ __global__ __launch_bounds__(PB) void k_prep_gt(const PrepGtArgs a) {
     const int sy = a.row_idx[oy], sx = a.col_idx[ox];
     const long sp = (t * a.Hi + sy) * a.Wi + sx;
     const double* q = a.cam + t * 20;
-    const double dd = a.depth_f64 ? (double)a.depth[sp] / (double)a.divisor : (double)__fdiv_rn((float)a.depth[sp], a.divisor);
-    const float d = (float)dd;
-    const float x = (float)(((double)sx - q[2]) * dd / q[0]);
-    const float y = (float)(((double)sy - q[3]) * dd / q[1]);
-    float c[3] = {x, -y, -d};
+    const PrepPoint pt = prep_point(a.depth[sp], sx, sy, q, a.divisor, a.max_depth, a.depth_f64);      // shared with the normal fit (gt_normals.hip)
+    float c[3] = {pt.c[0], pt.c[1], pt.c[2]};
     float nn[3] = {0.f, 0.f, 0.f};
     if (a.normals) {
       const unsigned char* p = a.normals + sp * 3;
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(PB) void k_prep_gt(const PrepGtArgs a) {
       wn[r] = (float)(m[0] * (double)nn[0] + m[1] * (double)nn[1] + m[2] * (double)nn[2]);
       wc[r] = (float)(m[0] * (double)c[0] + m[1] * (double)c[1] + m[2] * (double)c[2] + q[13 + r]);
     }
-    const bool bad = x != x || y != y || d != d || d < 1e-3f || d > a.max_depth;
+    const bool bad = pt.bad;
     if (a.zoomed)
       for (int j = 0; j < 3; ++j) { nn[j] = __fadd_rn(nn[j], 0.f); wn[j] = __fadd_rn(wn[j], 0.f); c[j] = __fadd_rn(c[j], 0.f); wc[j] = __fadd_rn(wc[j], 0.f); }
     const long o = t * 3 * plane + rem;

@@ -15,6 +15,7 @@ import numpy as np
 
 from .camera import CAMERA_KEYS, camera_pose_evaluation, save_camera_trajectories
 from .io_utils import prepare_gt_label
+from .normals import NORMALS_MODES
 from .pointmap import poses_from_pointmap
 from .vis import save_depth_normal_maps, write_ply
 from .metrics import (DEPTH_ALIGNMENTS, DEPTH_ALIGN_SPACES, PCD_KEYS, MetricsManager, check_disp_clip_min, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
@@ -31,9 +32,12 @@ def parse_dataset_config(config):
            "target_size": (config["h"], config["w"])}
     for k in ("split", "split_file", "scenes",       # optional: which scene list the loader walks (default: the split file)
               "prep",                                # optional: host | device clip preparation of the ScanNet++ / RGB-D loaders (DESIGN.md sections 16, 17)
-              "register", "register_invalid"):       # optional, 7-Scenes: host | device registration of raw depth, keep | drop of its 65535 marker (section 22)
+              "register", "register_invalid",        # optional, 7-Scenes: host | device registration of raw depth, keep | drop of its 65535 marker (section 22)
+              "normals", "normals_radius", "normals_edge", "normals_min_count"):   # optional, RGB-D loaders: normals fitted to the depth (section 30)
         if k in config:
             out[k] = config[k]
+    if out.get("normals") not in NORMALS_MODES:
+        raise ValueError(f"normals must be 'depth' or absent, not {out['normals']!r}")
     return out
 
 
@@ -156,7 +160,9 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     coloured depth | colour bar, composed on the GPU from the resident outputs under ``device_metrics=True`` and by the numpy mirror otherwise
     (DESIGN.md section 15).  Rows and CSV do not change.
     ``eval_normal`` on a dataset without ground-truth normals (the RGB-D loaders of ``harness/rgbd.py``) raises ``ValueError`` at the first such clip,
-    before the model runs on it.
+    before the model runs on it.  ``normals: depth`` in the dataset keys (with ``normals_radius`` / ``normals_edge`` / ``normals_min_count``;
+    DESIGN.md section 30) makes those loaders fit normals to their depth; the normal metrics then use ``gt_normal_masks`` (``mask`` and the fit's
+    ``normal_mask``) on the host and on the device path, every other metric keeps ``gt_masks``.
     ``eval_pcd`` (eval.py:66-83) adds ``acc / comp / nc1 / nc2`` and their medians: the model's ``pred_world_pts`` when it
     returns them, else ``world_points_from_depth`` of its depth with ``eval_depth``'s ``max_depth`` and clips (on the resident depth under
     ``device_metrics=True``), against ``gt_world_pts`` on ``gt_masks`` through ``pcd_evaluation`` / ``ug_eval_pcd``
@@ -190,7 +196,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
         seq = f"{data_idx:03d}_{data['scene_name']}"
         if "eval_normal" in config and "cam_normal" not in data:
             raise ValueError(f"eval_normal: clip {seq} of dataset {data.get('_dataset', type(dataset).__name__)!r} has no ground-truth normals "
-                             f"(the sample lacks 'cam_normal'); remove eval_normal from the configuration")
+                             f"(the sample lacks 'cam_normal'); remove eval_normal from the configuration, or set normals: depth on an RGB-D "
+                             f"dataset to fit them from its depth")
         if pcd_cfg is not None and "intrinsics" not in data and not getattr(mdl, "predicts_world_points", False):
             raise ValueError(f"eval_pcd: clip {seq} has no 'intrinsics' to turn the predicted depth into world points")
         if verbose:
@@ -227,10 +234,11 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
                 res = depth_evaluation(output["pred_depths"], gt["gt_depths"], max_depth=max_depth, custom_mask=gt["gt_masks"], **host_mode, **clips)
             metric.update(res[0])
         if "eval_normal" in config:
+            nmask = gt.get("gt_normal_masks", gt["gt_masks"])      # fitted normals bring their own validity (normals: depth)
             if eng is not None:
-                metric.update(eng.eval_normal(gt["gt_normals"].numpy(), gt["gt_masks"].numpy()))
+                metric.update(eng.eval_normal(gt["gt_normals"].numpy(), nmask.numpy()))
             else:
-                metric.update(normal_evaluation(output["pred_normals"], gt["gt_normals"], custom_mask=gt["gt_masks"]))
+                metric.update(normal_evaluation(output["pred_normals"], gt["gt_normals"], custom_mask=nmask))
         if pcd_cfg is not None:
             kw = {"threshold": pcd_cfg["threshold"], "downsample_num": pcd_cfg["downsample_num"], "seed": pcd_cfg["seed"] + data_idx,
                   "sampling": pcd_cfg["sampling"], "search": pcd_cfg["search"]}

@@ -1,6 +1,7 @@
 """GT preparation - mirrors ``/root/reference/utils/io_utils.py:4-45`` (``prepare_gt_label``): the unified sample
 dict (OpenGL camera coordinates, channel-first arrays) -> stacked torch tensors in OpenCV coordinates.  A sample without ``cam_normal``
-(the RGB-D loaders of ``harness/rgbd.py``) gives no ``gt_normals``; the reference's own function raises ``KeyError`` on those datasets."""
+(the RGB-D loaders of ``harness/rgbd.py``) gives no ``gt_normals``; the reference's own function raises ``KeyError`` on those datasets.
+A sample with ``normal_mask`` (those loaders with ``normals="depth"``) also gives ``gt_normal_masks`` = ``mask & normal_mask``."""
 import numpy as np
 
 _GL2CV = np.diag([1.0, -1.0, -1.0, 1.0]).astype(np.float32)
@@ -25,4 +26,6 @@ def prepare_gt_label(data):
     out = {"gt_world_pts": st(world), "gt_masks": st(masks), "gt_poses": st(poses), "gt_depths": st(depths), "gt_rgbs": st(rgbs)}
     if has_normals:
         out["gt_normals"] = st(normals)
+    if "normal_mask" in data:
+        out["gt_normal_masks"] = st([m & np.asarray(data["normal_mask"][i]).astype(bool) for i, m in enumerate(masks)])
     return out

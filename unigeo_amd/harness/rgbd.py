@@ -4,7 +4,8 @@ layout descriptions.
 The reference has one loader per dataset (``dataset/{sevenScenes,bonn,neuralRGBD,replica,scannetv2}/*.py``), which are one algorithm with
 five file layouts: read a 16-bit depth PNG, divide by a constant, back-project with VIEW 0's intrinsics in OpenGL convention
 (``utils/geometry_utils.py:246-253`` + the y/z flip), move the points into the key view, mask ``nan | d < 1e-3 | d > 20``.  There are no
-ground-truth normals: the samples carry no ``cam_normal`` / ``world_normal`` (the reference comments them out).  A ``Layout`` supplies what
+ground-truth normals: the samples carry no ``cam_normal`` / ``world_normal`` (the reference comments them out) unless ``normals="depth"``
+asks for normals fitted to the depth (``harness/normals.py``).  A ``Layout`` supplies what
 differs: file discovery and ordering, poses and intrinsics, the frame gap, the depth divisor, float32 or float64 depth arithmetic, an
 optional depth pre-clamp, an optional colour pre-resize and an optional aspect-ratio crop.
 
@@ -38,6 +39,7 @@ import numpy as np
 from PIL import Image
 
 from .dataset import split_clips
+from .normals import NORMALS_MODES, check_fit_options, fit_normals, world_normals
 from .scannetpp import PREP_MODES, _backproject_gl, _resize, resize_pick, resize_taps
 
 _GL_CV = np.float32([[1, 0, 0, 0], [0, -1, 0, 0], [0, 0, -1, 0], [0, 0, 0, 1]])
@@ -368,12 +370,22 @@ def _crop_box(layout, h, w):
     return (0, 0, w, h) if layout.crop_aspect is None else crop_to_aspect(h, w, layout.crop_aspect)
 
 
-def _assemble(root, seq, ids, keyview_idx, images, ext, K, cam, world, mask):
-    """The sample dict in the reference's key order (``*Sample.load`` + ``postprocess``)."""
+def _assemble(root, seq, ids, keyview_idx, images, ext, K, cam, world, mask, normals=None):
+    """The sample dict in the reference's key order (``*Sample.load`` + ``postprocess``).  ``normals = (cam_normal, world_normal,
+    normal_mask)``: the first two go where the reference's loaders have them commented out, ``normal_mask`` follows ``mask``."""
     ref_inv = np.linalg.inv(ext[keyview_idx])
-    return {"_base": root, "scene_name": "_".join(seq.scene_name.split("/")), "images": images,
-            "image_names": [os.path.basename(seq.rgb_paths[i]) for i in ids], "extrinsics": [e @ ref_inv for e in ext], "intrinsics": K,
-            "keyview_idx": keyview_idx, "cam_coord": cam, "caption": "", "world_coord": world, "mask": mask}
+    out = {"_base": root, "scene_name": "_".join(seq.scene_name.split("/")), "images": images,
+           "image_names": [os.path.basename(seq.rgb_paths[i]) for i in ids], "extrinsics": [e @ ref_inv for e in ext], "intrinsics": K,
+           "keyview_idx": keyview_idx}
+    if normals is not None:
+        out["cam_normal"] = normals[0]
+    out.update({"cam_coord": cam, "caption": ""})
+    if normals is not None:
+        out["world_normal"] = normals[1]
+    out.update({"world_coord": world, "mask": mask})
+    if normals is not None:
+        out["normal_mask"] = normals[2]
+    return out
 
 
 def _clip_cameras(seq, ids, box):
@@ -389,9 +401,22 @@ def _clip_cameras(seq, ids, box):
     return ext, K, Kc
 
 
-def load_clip(root, seq, ids, keyview_idx=0, depth=None):
+def _masked_frame(c):
+    """The loaders' validity rule on a whole back-projected frame: (``c`` with the bad pixels zeroed - a copy -, ``bad``)."""
+    bad = np.isnan(c).any(axis=0)
+    d = -1 * c[2]
+    d[np.isnan(d)] = 0
+    bad = bad | (d < 1e-3) | (d > MAX_DEPTH)
+    c = c.copy()
+    c[:, bad] = 0
+    return c, bad
+
+
+def load_clip(root, seq, ids, keyview_idx=0, depth=None, normals=None):
     """One clip at native size on the host: the reference's ``*Sample.load`` + ``postprocess``, step for step.  ``depth`` (uint16 ``[T,H,W]``)
-    stands in for the depth files: the registered clip of ``sevenScenesDataset(register=...)``."""
+    stands in for the depth files: the registered clip of ``sevenScenesDataset(register=...)``.  ``normals = (radius, edge, min_count)``:
+    the sample also carries ``cam_normal`` / ``world_normal`` / ``normal_mask``, fitted to the full native frame before the crop
+    (``harness/normals.py``)."""
     layout, base = seq.layout, os.path.join(root, seq.scene_name)
     frames = [_open_rgb(os.path.join(base, seq.rgb_paths[i]), layout) for i in ids]
     h, w = frames[0].shape[:2]
@@ -399,21 +424,23 @@ def load_clip(root, seq, ids, keyview_idx=0, depth=None):
     ext, K, Kc = _clip_cameras(seq, ids, box)
     ref = ext[keyview_idx]
     images, cam, world, masks = [], [], [], []
+    fitted = None if normals is None else ([], [], [])
     for j, i in enumerate(ids):
         images.append(frames[j].astype(np.float32).transpose(2, 0, 1)[:, y1:y2, x1:x2])
         raw = _open_depth(os.path.join(base, seq.depth_paths[i])) if depth is None else depth[j]
         c = _backproject_gl(depth_metres(raw, layout), K[0])     # view 0's intrinsics for all views, uncropped, on the full frame
         M = ref @ np.linalg.inv(ext[j])                          # source camera -> key-view camera
         wc = (np.matmul(M[:3, :3], c.reshape(3, -1)) + M[:3, 3][:, None]).reshape(c.shape)
+        if fitted is not None:
+            full, full_bad = _masked_frame(c)
+            n, nm = fit_normals(full, ~full_bad, *normals)
+            for lst, a in zip(fitted, (n, world_normals(n, M), nm)):
+                lst.append(np.ascontiguousarray(a[..., y1:y2, x1:x2]))
         c, wc = c[:, y1:y2, x1:x2], wc[:, y1:y2, x1:x2]
-        bad = np.isnan(c).any(axis=0)
-        d = -1 * c[2]
-        d[np.isnan(d)] = 0
-        bad = bad | (d < 1e-3) | (d > MAX_DEPTH)
-        c[:, bad] = 0
+        c, bad = _masked_frame(c)
         wc[:, bad] = 0
         cam.append(c); world.append(wc); masks.append((~bad).astype(np.float32))
-    return _assemble(root, seq, ids, keyview_idx, images, ext, Kc, cam, world, masks)
+    return _assemble(root, seq, ids, keyview_idx, images, ext, Kc, cam, world, masks, fitted)
 
 
 class RGBDClipDataset:
@@ -423,13 +450,17 @@ class RGBDClipDataset:
     ``prep="device"`` runs the resizes and the ground truth on the GPU; there is no fallback to the host path.
     ``register="host" | "device"`` (7-Scenes only; anywhere else it is a ``ValueError``): the scene holds raw depth, which is warped into the
     colour camera per clip before anything else sees it - on the host (``register_depth``) or on the dataset's engine (no fallback);
-    ``register_invalid="drop"`` leaves the raw 65535 marker out of it."""
+    ``register_invalid="drop"`` leaves the raw 65535 marker out of it.
+    ``normals="depth"`` (default ``None``: nothing changes) adds ``cam_normal`` / ``world_normal`` (lists of float32 ``[3,H,W]``) and
+    ``normal_mask`` (float32 ``[H,W]``): normals fitted to the depth on the full native frame (``harness/normals.py``'s ``fit_normals`` with
+    ``normals_radius`` / ``normals_edge`` / ``normals_min_count``; ``ug_prep_gt_normals`` under ``prep="device"``, bit-equal, no fallback),
+    cropped and resized like ``cam_coord``.  With ``register=`` the registered depth feeds the fit."""
 
     layout = None
 
     def __init__(self, root, scenes=None, split_file=None, split="test", clip_length=17, clip_overlap=0,
                  input_size=None, target_size=None, verbose=False, prep="host", device_id=0, engine=None, register=None,
-                 register_invalid="keep", **_):
+                 register_invalid="keep", normals=None, normals_radius=2, normals_edge=0.05, normals_min_count=None, **_):
         if prep not in PREP_MODES:
             raise ValueError(f"prep must be one of {list(PREP_MODES)}, not {prep!r}")
         if register not in REGISTER_MODES:
@@ -440,10 +471,16 @@ class RGBDClipDataset:
             if self.layout.raw_size is None:
                 raise ValueError(f"{self.layout.base_dataset}: register= is for 7-Scenes' raw depth; this dataset's depth needs no registration")
             self.layout = type(self.layout)(raw_depth=True)     # this dataset's own layout: the class attribute keeps the default pattern
+        if normals not in NORMALS_MODES:
+            raise ValueError(f"normals must be one of {list(NORMALS_MODES)}, not {normals!r}")
+        self.normals = normals
+        # without normals= the three options are not looked at, as before they existed
+        self.normals_opts = None if normals is None else check_fit_options(normals_radius, normals_edge, normals_min_count,
+                                                                            "normals_radius / normals_edge / normals_min_count")
         self.register, self.register_invalid = register, register_invalid
         self.prep, self.device_id, self.engine = prep, device_id, engine
         self._lock = threading.Lock()
-        self.last_timing = None                             # seconds of the last sample's stages: prep="device" decode / resize / gt, register= register
+        self.last_timing = None                             # seconds of the last sample's stages: prep="device" decode / resize / gt (/ normals), register= register
         name = self.layout.base_dataset
         if root is None or not os.path.isdir(root):
             raise FileNotFoundError(f"{name} root not found: {root!r}")
@@ -480,14 +517,15 @@ class RGBDClipDataset:
         if self.prep == "device":
             out = self._load_clip_device(seq, ids)
         else:
+            fit = self.normals_opts if self.normals is not None else None
             if self.register is None:
-                out = load_clip(self.root, seq, ids)
+                out = load_clip(self.root, seq, ids, normals=fit)
             else:
                 raw = decode_depth(self.root, seq, ids)
                 t0 = time.perf_counter()
                 depth = self._register(raw)
                 self.last_timing = {"register": time.perf_counter() - t0}
-                out = load_clip(self.root, seq, ids, depth=depth)
+                out = load_clip(self.root, seq, ids, depth=depth, normals=fit)
             if self.input_size is not None:
                 ht, wd = self.input_size
                 oh, ow = out["images"][0].shape[-2:]
@@ -496,7 +534,7 @@ class RGBDClipDataset:
                 out["intrinsics"] = [k * scale for k in out["intrinsics"]]
             if self.target_size is not None:
                 ht, wd = self.target_size
-                for attr in ("cam_coord", "world_coord", "mask"):
+                for attr in ("cam_coord", "world_coord", "mask") + (("cam_normal", "world_normal", "normal_mask") if fit is not None else ()):
                     out[attr] = [_resize(x, ht, wd, 0, False) for x in out[attr]]
         out["_index"] = index
         out["_dataset"] = self.base_dataset
@@ -543,17 +581,24 @@ class RGBDClipDataset:
             eng = self._device_engine()
             images = eng.prep_resize_frames(frames, ih, iw, row_taps=(ri + y1, rw), col_taps=(ci + x1, cwt))
             t2 = time.perf_counter()
-            _, cc, _, wc, mask = eng.prep_gt(depth, None, K0, M, y1 + resize_pick(ch, th), x1 + resize_pick(cw, tw),
-                                             depth_divisor=layout.depth_divisor, max_depth=layout.max_depth, depth_f64=layout.depth_f64,
-                                             zoomed=(th, tw) != (ch, cw))
+            rows, cols, gt_kw = y1 + resize_pick(ch, th), x1 + resize_pick(cw, tw), dict(
+                depth_divisor=layout.depth_divisor, max_depth=layout.max_depth, depth_f64=layout.depth_f64, zoomed=(th, tw) != (ch, cw))
+            _, cc, _, wc, mask = eng.prep_gt(depth, None, K0, M, rows, cols, **gt_kw)
             t3 = time.perf_counter()
+            fitted = None
+            if self.normals is not None:
+                r, e, mc = self.normals_opts
+                fitted = tuple(list(a) for a in eng.prep_gt_normals(depth, K0, M, rows, cols, radius=r, edge=e, min_count=mc, **gt_kw))
+            t4 = time.perf_counter()
         self.last_timing = {"decode": t1 - tr - t0, "resize": t2 - t1, "gt": t3 - t2}
+        if self.normals is not None:
+            self.last_timing["normals"] = t4 - t3
         if self.register is not None:
             self.last_timing["register"] = tr
         if self.input_size is not None:
             scale = np.array([[iw / cw] * 3, [ih / ch] * 3, [1.0] * 3], np.float32)
             Kc = [k * scale for k in Kc]
-        return _assemble(self.root, seq, ids, keyview_idx, list(images), ext, Kc, list(cc), list(wc), list(mask))
+        return _assemble(self.root, seq, ids, keyview_idx, list(images), ext, Kc, list(cc), list(wc), list(mask), fitted)
 
 
 class sevenScenesDataset(RGBDClipDataset):
