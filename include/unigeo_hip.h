@@ -254,6 +254,35 @@ int ug_dc_get_disparity(ug_ctx* ctx, float* disp_out /* host, [T*H*W] */);
 int ug_eval_depth_global(ug_ctx* ctx, const float* pred_depth /* NULL: resident depth */, const float* gt_depth, const float* gt_radius,
                          const float* cam2world_t44, const float* intrinsics_t33, const unsigned char* custom_mask /* or NULL */, int T, int H,
                          int W, const ug_depth_eval_opts* opts, double* out13, float* radius_map_out /* [T*H*W] or NULL */);
+/* Temporal alignment error (TAE) of a video depth (kernels/temporal.hip, harness/temporal.py).  UNPINNED: the reference
+ * has no such metric; it is restated from the published definition (ChronoDepth, Video Depth Anything), with one deliberate difference below.
+ * Aligned depth d of every pixel, float32, each operation rounded on its own, from the ORIGINAL prediction and the (s, t) that the clip's depth
+ * evaluation reported: a = fl(fl(s * pred) + t); with UG_DEPTH_ALIGN_DISPARITY, a = disp_clip_min where a is below it, d = 1 / a where a > 0,
+ * else 0; then d = post_clip_min where d is below it and post_clip_max where above (a NaN stays NaN).  Pre-clips enter through (s, t) only.
+ * Directed pairs P = 2 * (T - stride): pair 2i carries frame a = i into b = i + stride, pair 2i + 1 carries a = i + stride into b = i;
+ * rel_p34[p] = (inv(C_b) C_a)[:3] in float64, built on the host (harness/temporal.py relative_poses).
+ * Splat: a source pixel (row, col) of frame a with d > 0 and finite; in float64, one IEEE operation per step, never fused:
+ *   D = d;  X = ((col - cx_a) * D) / fx_a;  Y = ((row - cy_a) * D) / fy_a   (integer pixel indices, no half-pixel offset)
+ *   x3 = ((m0 * X + m1 * Y) + m2 * D) + m3, likewise y3, z3;  u = rint(((x3 / z3) * fx_b) + cx_b), v likewise (ties to even);  z = float32(z3)
+ * kept when z3 > 0, z > 0, z finite, u >= 0, v >= 0, v < H and u < W (a NaN anywhere drops the pixel).  The target pixel keeps the smallest z
+ * that reaches it (an integer atomicMin on an order-preserving key: the bytes do not depend on the order of arrival).  There is no source mask.
+ * Score: a reached target pixel q of pair p with d_b[q] > 0, 0 < gt_b[q] (and gt_b[q] < max_depth) and custom_mask_b[q] gives
+ * e = fl(|z - d_b|) / d_b in float32; the pair's value is sum(double(e)) / count, the sum in the fixed order of kernels/eval_reduce.h.  A pair
+ * with count == 0 is left out and counted as unscored - the deliberate difference: the published code scores it as 0.
+ * out4 = TAE (the mean of the scored pairs' values, a fraction like Abs Rel; NaN when no pair is scored), pairs scored, pairs total, pixels scored.
+ * pair_out [P,2] = value (NaN when unscored), count; warp_out [P,H,W] = the warped depth, 0 where unreached; err_out [P,H,W] = e, 0 where
+ * unscored (host arrays, each may be NULL).  pred == NULL: the resident depth of the last run, with the flag its resident disparity.
+ * T <= stride is no error: NaN, 0, 0, 0.  Errors (ug_last_error; the context stays usable): NULL opts / gt_depth / intrinsics / rel / out4;
+ * T, H or W <= 0; stride < 1; an unknown flag bit; a disp_clip_min that is not NaN and is <= 0 or infinite, or that comes without the flag;
+ * pred == NULL without a resident output of that shape; 2^31 or more pair-pixels P * H * W; a workspace too small (the message names the bytes
+ * needed).  Scratch: 4 bytes per pair-pixel for the z-buffer, 4 more for each requested map, and the uploads. */
+typedef struct { float s, t; unsigned flags /* UG_DEPTH_ALIGN_DISPARITY */; float disp_clip_min, post_clip_min, post_clip_max /* NaN: off */;
+                 float max_depth /* <= 0 or NaN: gt > 0 only */; int stride; } ug_tae_opts;
+void ug_tae_opts_default(ug_tae_opts* o);      /* 1, 0, 0, NaN, NaN, NaN, 80, 1 */
+int ug_eval_tae(ug_ctx* ctx, const float* pred /* NULL: resident depth; with the flag, the resident disparity */, const float* gt_depth,
+                const unsigned char* custom_mask /* or NULL */, const float* intrinsics_t33, const double* rel_p34 /* [P,3,4] */,
+                int T, int H, int W, const ug_tae_opts* opts, double* out4 /* TAE, pairs scored, pairs total, pixels scored */,
+                double* pair_out /* [P,2] value,count or NULL */, float* warp_out /* [P,H,W] or NULL */, float* err_out /* [P,H,W] or NULL */);
 
 /* Point-cloud evaluation: the reference's eval_pcd branch (eval.py:66-83, metrics/eval_pcd.py:10-168 with pcd_alignment.py, metrics/utils.py:14-42
  * and the Open3D calls it makes; kernels/pcd.hip).

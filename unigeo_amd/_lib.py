@@ -35,6 +35,7 @@ EXPORTS = [
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_register_opts_default", "ug_prep_register_depth", "ug_render_opts_default", "ug_prep_render_mesh",
     "ug_gt_normals_opts_default", "ug_prep_gt_normals",
+    "ug_tae_opts_default", "ug_eval_tae",
     "ug_profile_begin", "ug_profile_begin_shapes", "ug_profile_end", "ug_bench_gemm", "ug_bench_groupnorm", "ug_bench_mfma_peak", "ug_tune_force",
 ]
 
@@ -90,6 +91,11 @@ class RenderOptsC(C.Structure):
 
 class GtNormalsOptsC(C.Structure):
     _fields_ = [("radius", C.c_int), ("edge", C.c_double), ("min_count", C.c_int)]
+
+
+class TaeOptsC(C.Structure):
+    _fields_ = [("s", C.c_float), ("t", C.c_float), ("flags", C.c_uint), ("disp_clip_min", C.c_float), ("post_clip_min", C.c_float),
+                ("post_clip_max", C.c_float), ("max_depth", C.c_float), ("stride", C.c_int)]
 
 
 DEPTH_ALIGNMENTS = {"lstsq": 0, "median": 1, "scale": 2, "metric": 3, "l1": 4}    # UG_ALIGN_* of include/unigeo_hip.h
@@ -203,6 +209,10 @@ def load_library():
                                                C.c_uint]})
     if hasattr(lib, "ug_gt_normals_opts_default"):
         lib.ug_gt_normals_opts_default.restype = None
+    _set_argtypes(lib, {"ug_tae_opts_default": [C.POINTER(TaeOptsC)],
+                        "ug_eval_tae": [vp, vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(TaeOptsC), vp, vp, vp, vp]})
+    if hasattr(lib, "ug_tae_opts_default"):
+        lib.ug_tae_opts_default.restype = None
     lib.ug_clip_embed.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_encode.argtypes = [vp, vp, ip, ip, ip, vp]
     lib.ug_vae_decode.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -774,6 +784,41 @@ class Engine:
         res["valid_pixels"] = int(out[8])
         fits = (float(out[9]), float(out[10])), (float(out[11]), float(out[12]))
         return (res, *fits, rmap) if return_radius_map else (res, *fits)
+
+    def eval_tae(self, gt, cam2world, intrinsics, fit, mask=None, pred=None, max_depth=80.0, stride=1, space="depth", disp_clip_min=None,
+                 post_clip_min=None, post_clip_max=None, return_maps=False):
+        """Temporal alignment error on the device (``ug_eval_tae``) -> the dict of
+        ``harness.temporal.temporal_alignment_error``: ``TAE``, ``TAE pairs``, ``TAE pairs total``, ``TAE pixels`` and, with
+        ``return_maps=True``, ``pair_values`` ``[P,2]``, ``warp`` and ``err`` ``[P,H,W]``.  ``fit`` is the ``(s, t)`` the clip's ``eval_depth``
+        returned; ``pred=None`` scores the resident depth of the last run, with ``space="disparity"`` its resident disparity.  The relative
+        poses are built on the host by ``harness.temporal.relative_poses``, the function the mirror uses."""
+        from .harness.metrics import check_disp_clip_min
+        from .harness.temporal import relative_poses
+        check_disp_clip_min(space, disp_clip_min, "eval_tae")
+        g = _f32(gt)
+        if g.ndim != 3:
+            raise ValueError("eval_tae: gt must be [T,H,W]")
+        T, H, W = g.shape
+        stride = int(stride)
+        p = None if pred is None else _f32(pred).reshape(T, H, W)
+        m = None if mask is None else np.ascontiguousarray(np.asarray(mask).astype(np.uint8)).reshape(T, H, W)
+        k = _f32(intrinsics).reshape(T, 3, 3)
+        rel = np.ascontiguousarray(relative_poses(cam2world, stride) if stride >= 1 else np.zeros((0, 3, 4)), dtype=np.float64)
+        P = rel.shape[0]
+        relbuf = rel if P else np.zeros((1, 3, 4), np.float64)      # never a NULL pointer: T <= stride is a result, not an error
+        nan = float("nan")
+        o = TaeOptsC(float(fit[0]), float(fit[1]), DEPTH_ALIGN_DISPARITY if space == "disparity" else 0,
+                     *[nan if v is None else float(v) for v in (disp_clip_min, post_clip_min, post_clip_max, max_depth)], stride)
+        out = np.zeros(4, np.float64)
+        pairs = np.zeros((P, 2), np.float64) if return_maps else None
+        warp = np.zeros((P, H, W), np.float32) if return_maps else None
+        err = np.zeros((P, H, W), np.float32) if return_maps else None
+        self._ck(self.lib.ug_eval_tae(self.ctx, _ptr(p), _ptr(g), _ptr(m), _ptr(k), _ptr(relbuf), T, H, W, C.byref(o), _ptr(out), _ptr(pairs),
+                                      _ptr(warp), _ptr(err)))
+        res = {"TAE": float(out[0]), "TAE pairs": int(out[1]), "TAE pairs total": int(out[2]), "TAE pixels": int(out[3])}
+        if return_maps:
+            res.update({"pair_values": pairs, "warp": warp, "err": err})
+        return res
 
     # ---- point-cloud evaluation on device (DESIGN.md section 18)
     PCD_KEYS = ["acc", "comp", "nc1", "nc2", "acc_med", "comp_med", "nc1_med", "nc2_med"]

@@ -636,6 +636,86 @@ int ug_eval_depth_global(ug_ctx* x, const float* pred, const float* gt, const fl
   });
 }
 
+// ---------------------------------------------------------------- temporal alignment error (kernels/temporal.hip)
+void ug_tae_opts_default(ug_tae_opts* o) {
+  if (!o) return;
+  o->s = 1.f; o->t = 0.f; o->flags = 0u;
+  o->disp_clip_min = o->post_clip_min = o->post_clip_max = NAN;
+  o->max_depth = 80.f; o->stride = 1;
+}
+
+int ug_eval_tae(ug_ctx* x, const float* pred, const float* gt, const unsigned char* cmask, const float* K, const double* rel, int T, int H, int W,
+                const ug_tae_opts* o, double* out4, double* pair_out, float* warp_out, float* err_out) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(o != nullptr, "options must not be NULL");
+    UG_REQUIRE(gt && K && rel && out4, "gt_depth, intrinsics, rel and out4 must not be NULL");
+    UG_REQUIRE(T > 0 && H > 0 && W > 0, "T, H and W must be positive");
+    UG_REQUIRE(o->stride >= 1, "stride must be at least 1");
+    UG_REQUIRE((o->flags & ~(unsigned)UG_DEPTH_ALIGN_DISPARITY) == 0u, "unknown flag bit (UG_DEPTH_ALIGN_DISPARITY)");
+    const bool disparity = (o->flags & UG_DEPTH_ALIGN_DISPARITY) != 0u;
+    const float fl = o->disp_clip_min;
+    UG_REQUIRE(std::isnan(fl) || (fl > 0.f && std::isfinite(fl)), "disp_clip_min must be finite and positive (NaN: off)");
+    UG_REQUIRE(std::isnan(fl) || disparity, "disp_clip_min needs UG_DEPTH_ALIGN_DISPARITY");
+    if (!pred) {
+      UG_REQUIRE(c.io_ready && T == c.T && H == c.H && W == c.W, "no resident depth of that shape");
+      if (disparity) UG_REQUIRE(c.out_ready, "no resident disparity of that shape (run a clip first)");
+    }
+    const long plane = (long)H * W;
+    const long P = T > o->stride ? 2L * (T - o->stride) : 0;
+    UG_REQUIRE((double)P * (double)plane < 2147483648.0, "2^31 or more pair-pixels (2 * (T - stride) * H * W)");
+    if (P == 0) { out4[0] = NAN; out4[1] = out4[2] = out4[3] = 0.0; return 0; }
+    const long n = (long)T * plane, np_ = P * plane;
+    const int nbs = eval_nblocks(plane);
+    // the whole request is sized before the first allocation, so that a workspace too small is reported with the bytes the call needs
+    auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t need = r256((size_t)n * 4) + r256((size_t)T * 36) + r256((size_t)P * 96) + r256((size_t)np_ * 4) + r256((size_t)P * nbs * 16);
+    if (pred || disparity) need += r256((size_t)n * 4);
+    if (cmask) need += r256((size_t)n);
+    if (warp_out) need += r256((size_t)np_ * 4);
+    if (err_out) need += r256((size_t)np_ * 4);
+    const size_t room = c.ws.capacity() - c.ws.mark();
+    if (need > room)
+      throw std::runtime_error("ug_eval_tae: the workspace is too small: this call needs " + std::to_string(need) + " bytes of it and " +
+                               std::to_string(room) + " are free (raise workspace_bytes in ug_create)");
+    DepthEvalBufs d{c.d_depth, nullptr, nullptr, n};
+    if (pred || disparity) {
+      float* dx = c.ws.get<float>(n);
+      if (pred) UG_CHECK(hipMemcpy(dx, pred, n * 4, hipMemcpyHostToDevice));
+      else launch_disparity_from_frames(c.d_out_frames, c.d_mm, dx, n, c.stream);
+      d.dp = dx;
+    }
+    d.dg = c.ws.get<float>(n); UG_CHECK(hipMemcpy(d.dg, gt, n * 4, hipMemcpyHostToDevice));
+    if (cmask) { d.dm = (unsigned char*)c.ws.alloc(n); UG_CHECK(hipMemcpy(d.dm, cmask, n, hipMemcpyHostToDevice)); }
+    float* dk = c.ws.get<float>((long)T * 9); UG_CHECK(hipMemcpy(dk, K, (size_t)T * 36, hipMemcpyHostToDevice));
+    double* drel = c.ws.get<double>(P * 12); UG_CHECK(hipMemcpy(drel, rel, (size_t)P * 96, hipMemcpyHostToDevice));
+    unsigned* zbuf = c.ws.get<unsigned>(np_);
+    double* part = c.ws.get<double>(P * nbs * 2);
+    float* dwarp = warp_out ? c.ws.get<float>(np_) : nullptr;
+    float* derr = err_out ? c.ws.get<float>(np_) : nullptr;
+    TaeArgs a;
+    a.s = o->s; a.t = o->t; a.floor_ = fl; a.plo = clip_lo(o->post_clip_min); a.phi = clip_hi(o->post_clip_max);
+    a.md = depth_bound(o->max_depth); a.disparity = disparity ? 1 : 0; a.stride = o->stride;
+    int nb = 0;
+    launch_tae(d.dp, d.dg, d.dm, dk, drel, (int)P, H, W, a, zbuf, part, dwarp, derr, &nb, c.stream);
+    UG_CHECK(hipGetLastError());
+    UG_CHECK(hipStreamSynchronize(c.stream));
+    std::vector<double> hp((size_t)P * nb * 2);
+    UG_CHECK(hipMemcpy(hp.data(), part, hp.size() * 8, hipMemcpyDeviceToHost));
+    double tot = 0.0, pixels = 0.0; long scored = 0;
+    for (long p = 0; p < P; ++p) {
+      double sum = 0.0, cnt = 0.0;
+      for (int b = 0; b < nb; ++b) { sum += hp[((size_t)p * nb + b) * 2]; cnt += hp[((size_t)p * nb + b) * 2 + 1]; }      // block order
+      const double v = cnt > 0 ? sum / cnt : (double)NAN;
+      if (cnt > 0) { tot += v; ++scored; pixels += cnt; }
+      if (pair_out) { pair_out[p * 2] = v; pair_out[p * 2 + 1] = cnt; }
+    }
+    out4[0] = scored > 0 ? tot / (double)scored : (double)NAN; out4[1] = (double)scored; out4[2] = (double)P; out4[3] = pixels;
+    if (warp_out) UG_CHECK(hipMemcpy(warp_out, dwarp, (size_t)np_ * 4, hipMemcpyDeviceToHost));
+    if (err_out) UG_CHECK(hipMemcpy(err_out, derr, (size_t)np_ * 4, hipMemcpyDeviceToHost));
+  });
+}
+
 void ug_pcd_opts_default(ug_pcd_opts* o) { o->threshold = 0.1f; o->max_iteration = 30; o->knn = 30; }
 
 int ug_pcd_world_points(ug_ctx* x, const float* pred, const float* gt, const float* cam2world, const float* K, int T, int H, int W,

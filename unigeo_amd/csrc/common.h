@@ -450,6 +450,13 @@ void launch_prep_gt_normals(const GtNormalsArgs& a, hipStream_t s);
 // device; m: the source-to-target transform, row-major 3x4
 struct RegArgs { double src_focal, dst_focal; double m[12]; float divisor, max_valid; int drop_sentinel; };
 void launch_register_depth(const unsigned short* depth, int T, int H, int W, const RegArgs& a, unsigned* zbuf, unsigned short* out, hipStream_t s);
+// Temporal alignment error (kernels/temporal.hip).  s, t: the clip's fit; floor_: NaN when off; plo / phi: the post-clip
+// bounds (-inf / +inf when off); md: the depth bound of the score (NaN: gt > 0 only).  pred / gt [T,H,W], cmask NULL or [T,H,W], K [T,9] float32,
+// rel [P,12] doubles, zbuf / warp_out / err_out (either may be NULL) P*H*W words, part P * eval_nblocks(H*W) * 2 doubles (the block count comes
+// back in *nb_out).  All on the device; P = 2 * (T - stride) >= 1, P * H * W < 2^31.
+struct TaeArgs { float s, t, floor_, plo, phi, md; int disparity, stride; };
+void launch_tae(const float* pred, const float* gt, const unsigned char* cmask, const float* K, const double* rel, int P, int H, int W,
+                const TaeArgs& a, unsigned* zbuf, double* part, float* warp_out, float* err_out, int* nb_out, hipStream_t s);
 // ScanNet++ mesh renderer (kernels/render.hip).  verts [NV,3] float32, faces [NF,3] int32 (every index validated by the
 // caller), cams 16 doubles per frame = world-to-camera row-major 3x4, fx, fy, cx, cy; mask NULL or [T,H,W]; zbuf: T*H*W 64-bit words of
 // scratch; big_id / big_tile: big_cap entries of scratch for the boxes a whole workgroup walks, big_count one word; depth [T,H,W],

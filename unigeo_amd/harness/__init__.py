@@ -5,7 +5,8 @@ from .metrics import (MetricsManager, depth_evaluation, depth_evaluation_in_glob
                       pcd_evaluation, world_points_from_depth)
 from .camera import camera_pose_evaluation, save_camera_trajectories, tum_poses, write_tum_trajectory
 from .pointmap import pointmap_focal, pointmap_poses, poses_from_pointmap
-from .eval import (evaluate, parse_camera_eval_config, parse_dataset_config, parse_depth_coord, parse_metric_config, parse_pcd_eval_config,
+from .temporal import aligned_depth, relative_poses, temporal_alignment_error, warp_depth
+from .eval import (evaluate, parse_temporal_eval_config, parse_camera_eval_config, parse_dataset_config, parse_depth_coord, parse_metric_config, parse_pcd_eval_config,
                    import_class_from_module)
 from .dataset import SyntheticGeometryDataset, split_clips
 from .scannetpp import ScannetPPDataset, ScannetPPSequence
@@ -18,7 +19,8 @@ from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, read_ply, 
 
 __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_evaluation_in_global_coord",
            "l1_fit", "l1_objective", "normal_evaluation", "pcd_evaluation", "world_points_from_depth", "evaluate", "parse_dataset_config", "parse_depth_coord",
-           "parse_metric_config", "parse_pcd_eval_config", "parse_camera_eval_config", "import_class_from_module", "SyntheticGeometryDataset",
+           "parse_metric_config", "parse_pcd_eval_config", "parse_camera_eval_config", "parse_temporal_eval_config",
+           "aligned_depth", "relative_poses", "temporal_alignment_error", "warp_depth", "import_class_from_module", "SyntheticGeometryDataset",
            "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence",
            "RGBDClipDataset", "RGBDSequence", "sevenScenesDataset", "bonnDataset", "neuralRGBDDataset", "replicaDataset", "ScannetV2Dataset",
            "read_tum_trajectory", "RegisterOpts", "register_depth",

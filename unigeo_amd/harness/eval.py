@@ -6,7 +6,8 @@ depth / normal panels (eval.py:58-62; ``harness/vis.py``).
 the model's world points, or those of its aligned depth, against the ground-truth cloud.
 ``eval_camera`` (eval.py:85-95) scores the model's camera poses, or those recovered from its world points, with ATE and
 RPE (``harness/camera.py``, ``harness/pointmap.py``); the DepthCrafter / StableNormal plugins return
-neither, so a configuration that asks them for it is an error at the first clip.
+neither, so a configuration that asks them for it is an error at the first clip.  ``eval_temporal`` (not a key of the reference) scores
+the aligned depth's temporal alignment error between neighbouring frames (``harness/temporal.py``).
 """
 import importlib
 import os
@@ -17,6 +18,7 @@ from .camera import CAMERA_KEYS, camera_pose_evaluation, save_camera_trajectorie
 from .io_utils import prepare_gt_label
 from .normals import NORMALS_MODES
 from .pointmap import poses_from_pointmap
+from .temporal import temporal_alignment_error
 from .vis import save_depth_normal_maps, write_ply
 from .metrics import (DEPTH_ALIGNMENTS, DEPTH_ALIGN_SPACES, PCD_KEYS, MetricsManager, check_disp_clip_min, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
                       pcd_evaluation, world_points_from_depth)
@@ -43,7 +45,7 @@ def parse_dataset_config(config):
 
 def parse_metric_config(config):
     names = []
-    for key in ("eval_depth", "eval_pcd", "eval_camera", "eval_normal"):
+    for key in ("eval_depth", "eval_pcd", "eval_camera", "eval_normal", "eval_temporal"):
         if key in config:
             names.extend(config[key]["metric_names"])
     return names
@@ -136,6 +138,36 @@ def parse_camera_eval_config(config):
     return out
 
 
+TEMPORAL_EVAL_KEYS = ("metric_names", "stride")
+TEMPORAL_METRICS = ("TAE", "TAE gt")
+
+
+def parse_temporal_eval_config(config):
+    """``eval_temporal`` (not a key of the reference: the temporal alignment error of ``harness/temporal.py``):
+    ``metric_names`` out of ``TAE`` (the clip's aligned prediction) and ``TAE gt`` (the ground-truth depth itself under the same poses: the
+    floor the dataset allows), optional ``stride`` (default 1: consecutive frames) -> dict, or ``None`` without the key.  An unknown key, an
+    unknown metric name, a stride that is not a positive integer, ``eval_temporal`` without ``eval_depth`` (whose ``(s, t)`` it aligns with)
+    and ``eval_temporal`` with ``eval_depth.coord: global`` are a ``ValueError``."""
+    if "eval_temporal" not in config:
+        return None
+    cfg = config["eval_temporal"] or {}
+    unknown = sorted(set(cfg) - set(TEMPORAL_EVAL_KEYS))
+    if unknown:
+        raise ValueError(f"eval_temporal: unknown key(s) {unknown}; known: {list(TEMPORAL_EVAL_KEYS)}")
+    names = list(cfg.get("metric_names") or [])
+    bad = [n for n in names if n not in TEMPORAL_METRICS]
+    if bad:
+        raise ValueError(f"eval_temporal.metric_names: unknown name(s) {bad}; known: {list(TEMPORAL_METRICS)}")
+    stride = cfg.get("stride", 1)
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 1:
+        raise ValueError(f"eval_temporal.stride must be a positive integer, not {stride!r}")
+    if "eval_depth" not in config:
+        raise ValueError("eval_temporal needs eval_depth: it scores the depth aligned with that evaluation's scale and shift")
+    if (config["eval_depth"] or {}).get("coord", "camera") == "global":
+        raise ValueError("eval_temporal does not go with eval_depth.coord: global (its scale and shift belong to the camera-frame evaluation)")
+    return {"stride": int(stride), "gt": "TAE gt" in names}
+
+
 def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0, world=1, verbose=True,
              device_metrics=False, models=None, engine=None):
     """Run the reference's per-clip loop.  With ``world > 1`` this rank only evaluates clips
@@ -175,13 +207,19 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
     model's own engine or with ``engine=`` for a model that has none); a model that returns neither raises a ``ValueError`` that names the
     clip and the plugin.  Optional keys ``eval_camera.reproj_px`` and ``eval_camera.focal``; an unknown key raises before the first clip.
     ``vis_camera: True`` writes ``save_dir/camera_{seq}/pred_traj.txt``, ``gt_traj.txt`` (TUM format) and, with matplotlib, ``traj.png``;
-    without ``eval_camera`` it is a ``ValueError``.  A configuration without ``eval_camera`` gives the rows and bytes it gave before."""
+    without ``eval_camera`` it is a ``ValueError``.  A configuration without ``eval_camera`` gives the rows and bytes it gave before.
+    ``eval_temporal`` (not in the reference) adds ``TAE``, the temporal alignment error of the clip's depth aligned with
+    the ``(s, t)``, space, post-clips and ``max_depth`` of that clip's ``eval_depth``: ``temporal_alignment_error`` on the host,
+    ``ug_eval_tae`` on the resident depth (or disparity) under ``device_metrics=True``.  ``TAE gt``, by name only, scores the ground-truth
+    depth itself.  The row also carries ``TAE pairs`` / ``TAE pairs total`` / ``TAE pixels``; frames that pad a clip's tail are scored like
+    any other.  Needs ``eval_depth`` in camera coordinates and a sample with ``intrinsics`` (``ValueError`` otherwise); optional ``stride``."""
     alignment, max_depth, clips = parse_depth_eval_config(config)
     coord = parse_depth_coord(config)
     space, disp_clip_min = parse_depth_space_config(config)
     space_kw = {} if space == "depth" else {"disp_clip_min": disp_clip_min}
     pcd_cfg = parse_pcd_eval_config(config)
     cam_cfg = parse_camera_eval_config(config)
+    tae_cfg = parse_temporal_eval_config(config)
     host_mode = {"lstsq": {"align_with_lstsq": True}, "median": {}, "scale": {"align_with_scale": True}, "metric": {"metric_scale": True},
                  "l1": {"align_with_l1": True}}[alignment]
     if dataset is None:
@@ -200,6 +238,8 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
                              f"dataset to fit them from its depth")
         if pcd_cfg is not None and "intrinsics" not in data and not getattr(mdl, "predicts_world_points", False):
             raise ValueError(f"eval_pcd: clip {seq} has no 'intrinsics' to turn the predicted depth into world points")
+        if tae_cfg is not None and "intrinsics" not in data:
+            raise ValueError(f"eval_temporal: clip {seq} has no 'intrinsics' to carry a frame's depth into its neighbour's camera")
         if verbose:
             print("processing seq:", seq)
         output = mdl.forward(data)
@@ -233,6 +273,23 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
             else:
                 res = depth_evaluation(output["pred_depths"], gt["gt_depths"], max_depth=max_depth, custom_mask=gt["gt_masks"], **host_mode, **clips)
             metric.update(res[0])
+        if tae_cfg is not None:
+            K = np.stack([np.asarray(k, dtype=np.float32).reshape(3, 3) for k in data["intrinsics"]], 0)
+            gt_d, poses, cm = gt["gt_depths"].numpy(), gt["gt_poses"].numpy(), gt["gt_masks"].numpy()
+            kw = {"max_depth": max_depth, "stride": tae_cfg["stride"]}
+            pkw = {"space": space, **space_kw, **{k: v for k, v in clips.items() if k.startswith("post_")}}
+            fit = (np.float32(res[1][0]), np.float32(res[1][1]))      # the (s, t) of this clip's eval_depth
+            if eng is not None:
+                tae = eng.eval_tae(gt_d, poses, K, fit, cm, **kw, **pkw)
+            else:
+                tae = temporal_alignment_error(output["pred_disps" if space == "disparity" else "pred_depths"], gt_d, poses, K, fit,
+                                               custom_mask=cm, **kw, **pkw)
+            metric.update(tae)
+            if tae_cfg["gt"]:
+                if eng is not None:
+                    metric["TAE gt"] = eng.eval_tae(gt_d, poses, K, (1.0, 0.0), cm, pred=gt_d, **kw)["TAE"]
+                else:
+                    metric["TAE gt"] = temporal_alignment_error(gt_d, gt_d, poses, K, (1.0, 0.0), custom_mask=cm, **kw)["TAE"]
         if "eval_normal" in config:
             nmask = gt.get("gt_normal_masks", gt["gt_masks"])      # fitted normals bring their own validity (normals: depth)
             if eng is not None:
