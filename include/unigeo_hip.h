@@ -337,6 +337,26 @@ int ug_eval_pcd_ex(ug_ctx* ctx, const float* pred_pts /* NULL: resident points *
                    const long* sample_idx /* or NULL */, long n_sample, const ug_pcd_opts* opts, int flags, double* out32,
                    float* pred_cloud_out /* or NULL */, float* gt_cloud_out /* or NULL */, long* pred_idx_out /* or NULL */,
                    long* gt_idx_out /* or NULL */, long* search_stats /* [8] or NULL */);
+/* ug_eval_pcd_scores: ug_eval_pcd_ex plus precision / recall counts at distance thresholds and voxel-set counts for an occupancy IoU (DESIGN.md
+ * section 32; kernels/pcd.hip k_pcd_count_below, kernels/voxel.hip).  Both go beyond what the reference evaluates: metrics/utils.py carries
+ * completion_ratio (:7-11, recall at 0.05) and compute_iou (:45-60) and calls neither.
+ *   thresholds[0 .. n_thresholds), n_thresholds 0..8, each positive and finite: score_counts[2 * k] = how many moved predictions lie strictly
+ *     closer than thresholds[k] to their nearest ground-truth point, score_counts[2 * k + 1] = how many ground-truth points lie strictly closer
+ *     than that to their nearest moved prediction.  The distances are the arrays that acc and comp are the means of; no second search runs.
+ *     precision = count / n_points, recall likewise, in float64 on the host.
+ *   voxel_sizes[0 .. n_voxel_sizes), n_voxel_sizes 0..4, each positive and finite: a point's cell is floor(x / v) per axis from the world origin;
+ *     a point with a non-finite coordinate or a cell index outside (-2^20, 2^20) is skipped.  voxel_counts[6 * k ..] = cells of the moved
+ *     prediction, cells of the ground truth, cells of both, cells of either, skipped predictions, skipped ground-truth points.
+ *   With both counts 0 (or sopts NULL) the call is ug_eval_pcd_ex: the same launches, the same outputs.  An empty mask gives zero counts.
+ *   Errors (the context stays usable): a count outside its range, a threshold or voxel size that is not positive and finite, a NULL output for
+ *   a non-zero count, a voxel table that overflowed, and a workspace too small - the message names the bytes the call needs. */
+typedef struct { int n_thresholds; double thresholds[8]; int n_voxel_sizes; double voxel_sizes[4]; } ug_pcd_score_opts;
+void ug_pcd_score_opts_default(ug_pcd_score_opts* o);     /* both counts 0 */
+int ug_eval_pcd_scores(ug_ctx* ctx, const float* pred_pts /* NULL: resident points */, const float* gt_pts, const unsigned char* mask, long n_pixels,
+                       const long* sample_idx /* or NULL */, long n_sample, const ug_pcd_opts* opts, int flags, double* out32,
+                       float* pred_cloud_out /* or NULL */, float* gt_cloud_out /* or NULL */, long* pred_idx_out /* or NULL */,
+                       long* gt_idx_out /* or NULL */, long* search_stats /* [8] or NULL */, const ug_pcd_score_opts* sopts,
+                       long* score_counts /* [8 * 2] */, long* voxel_counts /* [4 * 6] */);
 
 /* Focal, camera poses and depth from world point maps: what the reference's point-map plugins take from
  * solve_depth_and_camera_from_3d_points (metrics/utils.py:68-160, called from model/spann3r.py:43; kernels/pointmap.hip).

@@ -275,6 +275,12 @@ int ug_op_pcd_fps(ug_ctx* ctx, const float* pts, long n, long k, long* idx_out, 
 int ug_op_pcd_nn_grid(ug_ctx* ctx, const double* query, long nq, const double* target, long nt, const double* T44, int* idx_out, double* dist_out,
                       long* stats /* [4] or NULL */);
 int ug_op_pcd_knn_normals_grid(ug_ctx* ctx, const double* pts, long n, int knn, int* nbr_out, double* normals_out, long* stats /* [4] or NULL */);
+/* The voxel set of ug_eval_pcd_scores alone (kernels/voxel.hip) on two host float64 clouds [na,3] / [nb,3] (either may be
+ * empty) -> out6: cells of a, cells of b, cells of both, cells of either, skipped points of a, skipped points of b.  capacity_log2 forces the
+ * table to 2^capacity_log2 slots (1..30) so that probing, wrap-around and a full table can be reached with a few thousand points; 0 takes the
+ * production rule (the smallest power of two >= 2 * (na + nb), at least 1024).  A table too small for the cells is an error return ("overflow"),
+ * never a wait, and the context stays usable. */
+int ug_op_voxel_set(ug_ctx* ctx, const double* a, long na, const double* b, long nb, double voxel_size, int capacity_log2, long* out6);
 /* Tuning aids (not on the product path): GEMM / implicit-conv microbenchmark on device-resident random data,
  * and an override of the tile/split-K heuristic (-1 = heuristic). ms_out: [ms per launch, cfg, split, M, K]. */
 /* GroupNorm launch-scheme A/B (mode: launch_groupnorm in kernels/norm.hip); tuning aid, no reference counterpart. */

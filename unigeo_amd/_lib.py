@@ -31,6 +31,7 @@ EXPORTS = [
     "ug_bind_stablenormal", "ug_sn_run", "ug_sn_unet_forward", "ug_sn_dino", "ug_sn_vae_decode", "ug_sn_vae_encode", "ug_resize_bilinear",
     "ug_pcd_opts_default", "ug_pcd_world_points", "ug_eval_pcd", "ug_op_pcd_nn", "ug_op_pcd_select", "ug_op_pcd_knn_normals", "ug_eval_pcd_fps", "ug_op_pcd_fps",
     "ug_eval_pcd_ex", "ug_op_pcd_nn_grid", "ug_op_pcd_knn_normals_grid",
+    "ug_pcd_score_opts_default", "ug_eval_pcd_scores", "ug_op_voxel_set",
     "ug_pointmap_opts_default", "ug_pointmap_focal", "ug_pointmap_poses",
     "ug_vis_depth_range", "ug_vis_panels", "ug_prep_resize_frames", "ug_prep_gt", "ug_prep_gt_ex",
     "ug_register_opts_default", "ug_prep_register_depth", "ug_render_opts_default", "ug_prep_render_mesh",
@@ -74,6 +75,10 @@ class DepthEvalOpts2C(C.Structure):
 
 class PcdOptsC(C.Structure):
     _fields_ = [("threshold", C.c_float), ("max_iteration", C.c_int), ("knn", C.c_int)]
+
+
+class PcdScoreOptsC(C.Structure):
+    _fields_ = [("n_thresholds", C.c_int), ("thresholds", C.c_double * 8), ("n_voxel_sizes", C.c_int), ("voxel_sizes", C.c_double * 4)]
 
 
 class PointmapOptsC(C.Structure):
@@ -188,6 +193,12 @@ def load_library():
     _set_argtypes(lib, {"ug_eval_pcd_ex": [vp, vp, vp, vp, C.c_long, vp, C.c_long, C.POINTER(PcdOptsC), ip, vp, vp, vp, vp, vp, vp],
                         "ug_op_pcd_nn_grid": [vp, vp, C.c_long, vp, C.c_long, vp, vp, vp, vp],
                         "ug_op_pcd_knn_normals_grid": [vp, vp, C.c_long, ip, vp, vp, vp]})
+    _set_argtypes(lib, {"ug_pcd_score_opts_default": [C.POINTER(PcdScoreOptsC)],
+                        "ug_eval_pcd_scores": [vp, vp, vp, vp, C.c_long, vp, C.c_long, C.POINTER(PcdOptsC), ip, vp, vp, vp, vp, vp, vp,
+                                               C.POINTER(PcdScoreOptsC), vp, vp],
+                        "ug_op_voxel_set": [vp, vp, C.c_long, vp, C.c_long, C.c_double, ip, vp]})
+    if hasattr(lib, "ug_pcd_score_opts_default"):
+        lib.ug_pcd_score_opts_default.restype = None
     _set_argtypes(lib, {"ug_pointmap_opts_default": [C.POINTER(PointmapOptsC)],
                         "ug_pointmap_focal": [vp, vp, ip, ip, C.c_double, C.c_double, vp],
                         "ug_pointmap_poses": [vp, vp, vp, ip, ip, ip, C.c_double, C.c_double, C.c_double, C.POINTER(PointmapOptsC), vp, vp, vp, vp]})
@@ -840,13 +851,22 @@ class Engine:
         return pts, (float(fit[0]), float(fit[1]))
 
     def eval_pcd(self, pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30,
-                 return_clouds=True, sampling="random", search="brute"):
+                 return_clouds=True, sampling="random", search="brute", fscore_thresholds=(), voxel_sizes=()):
         """``pcd_evaluation`` of ``harness/metrics.py`` on the device (``ug_eval_pcd``) -> the same dict.  ``pred_pts=None`` evaluates the
         points that the last ``pcd_world_points`` left resident.  The sampled positions are drawn here, as the host mirror draws them;
         ``sampling="fps"`` picks them on the device instead (``ug_eval_pcd_fps``) and adds ``pred_idx`` / ``gt_idx``.
         ``search="grid"`` (``ug_eval_pcd_ex`` with ``UG_PCD_SEARCH_GRID``) finds the same neighbours through a uniform
-        grid - every entry of the dict is bit-equal - and adds ``search_stats``."""
-        from .harness.metrics import pcd_sample_indices
+        grid - every entry of the dict is bit-equal - and adds ``search_stats``.  ``fscore_thresholds`` / ``voxel_sizes`` (DESIGN.md section
+        32), when either is not empty, send the call through ``ug_eval_pcd_scores`` and add the keys of the mirror: ``prec@t`` / ``recall@t`` /
+        ``fscore@t`` with ``score_counts``, ``iou@v`` with ``voxel_counts``; the device returns the integer counts, the values are formed
+        from them by the mirror's own functions."""
+        from .harness.metrics import PCD_MAX_THRESHOLDS, PCD_MAX_VOXEL_SIZES, pcd_sample_indices, pcd_score_names
+        taus, tau_names = pcd_score_names(fscore_thresholds, "fscore_thresholds", PCD_MAX_THRESHOLDS)
+        vsizes, vsize_names = pcd_score_names(voxel_sizes, "voxel_sizes", PCD_MAX_VOXEL_SIZES)
+        score = None
+        if taus or vsizes:
+            so = PcdScoreOptsC(len(taus), (C.c_double * 8)(*taus), len(vsizes), (C.c_double * 4)(*vsizes))
+            score = (so, np.zeros((8, 2), np.int64), np.zeros((4, 6), np.int64), tau_names, vsize_names)
         if sampling not in ("random", "fps"):
             raise ValueError(f"eval_pcd: sampling must be 'random' or 'fps', not {sampling!r}")
         if search not in ("brute", "grid"):
@@ -864,13 +884,17 @@ class Engine:
             pc = np.empty((ns, 3), np.float32) if return_clouds else None
             gc = np.empty((ns, 3), np.float32) if return_clouds else None
             ip, ig = np.empty(ns, np.int64), np.empty(ns, np.int64)
-            if grid:
+            if score is not None:
+                self._ck(self.lib.ug_eval_pcd_scores(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, None, int(downsample_num), C.byref(o),
+                                                     self.PCD_FPS | (self.PCD_SEARCH_GRID if grid else 0), _ptr(out), _ptr(pc), _ptr(gc), _ptr(ip),
+                                                     _ptr(ig), _ptr(stats), C.byref(score[0]), _ptr(score[1]), _ptr(score[2])))
+            elif grid:
                 self._ck(self.lib.ug_eval_pcd_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, None, int(downsample_num), C.byref(o),
                                                  self.PCD_FPS | self.PCD_SEARCH_GRID, _ptr(out), _ptr(pc), _ptr(gc), _ptr(ip), _ptr(ig), _ptr(stats)))
             else:
                 self._ck(self.lib.ug_eval_pcd_fps(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, int(downsample_num), C.byref(o), _ptr(out), _ptr(pc),
                                                   _ptr(gc), _ptr(ip), _ptr(ig)))
-            res = self._pcd_result(out, stats if grid else None)
+            res = self._pcd_result(out, stats if grid else None, score)
             res.update(pred_idx=ip, gt_idx=ig)
             if return_clouds:
                 col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[m > 0]
@@ -883,13 +907,17 @@ class Engine:
         out = np.zeros(32, np.float64)
         pc = np.empty((ns, 3), np.float32) if return_clouds else None
         gc = np.empty((ns, 3), np.float32) if return_clouds else None
-        if grid:
+        if score is not None:
+            self._ck(self.lib.ug_eval_pcd_scores(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
+                                                 self.PCD_SEARCH_GRID if grid else 0, _ptr(out), _ptr(pc), _ptr(gc), None, None, _ptr(stats),
+                                                 C.byref(score[0]), _ptr(score[1]), _ptr(score[2])))
+        elif grid:
             self._ck(self.lib.ug_eval_pcd_ex(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
                                              self.PCD_SEARCH_GRID, _ptr(out), _ptr(pc), _ptr(gc), None, None, _ptr(stats)))
         else:
             self._ck(self.lib.ug_eval_pcd(self.ctx, _ptr(p), _ptr(g), _ptr(m), m.size, _ptr(idx), 0 if idx is None else len(idx), C.byref(o),
                                           _ptr(out), _ptr(pc), _ptr(gc)))
-        res = self._pcd_result(out, stats if grid else None)
+        res = self._pcd_result(out, stats if grid else None, score)
         if return_clouds:
             keep = m > 0
             col = np.zeros((n_mask, 3), np.float32) if rgbs is None else _f32(rgbs).reshape(-1, 3)[keep]
@@ -900,8 +928,17 @@ class Engine:
     PCD_FPS, PCD_SEARCH_GRID = 1, 2      # UG_PCD_FPS, UG_PCD_SEARCH_GRID
     SEARCH_STAT_KEYS = ["settled", "leftover", "gt_cells", "gt_max_cell", "pred_cells", "pred_max_cell", "workspace_peak_bytes"]
 
-    def _pcd_result(self, out, stats=None):
+    def _pcd_result(self, out, stats=None, score=None):
         res = dict(zip(self.PCD_KEYS, out[:8].tolist()))
+        if score is not None:
+            from .harness.metrics import pcd_threshold_values, pcd_voxel_values
+            _, sc, vc, tau_names, vsize_names = score
+            if tau_names:
+                res.update(pcd_threshold_values(tau_names, sc[:len(tau_names)], int(out[8])))
+                res["score_counts"] = sc[:len(tau_names)].copy()
+            if vsize_names:
+                res.update(pcd_voxel_values(vsize_names, vc[:len(vsize_names)]))
+                res["voxel_counts"] = vc[:len(vsize_names)].copy()
         if stats is not None:
             res["search_stats"] = dict(zip(self.SEARCH_STAT_KEYS, (int(v) for v in stats[:7])))
         res.update(n_points=int(out[8]), icp_iterations=int(out[9]), icp_fitness=float(out[10]), icp_rmse=float(out[11]),
@@ -981,6 +1018,16 @@ class Engine:
         nbr, nrm, st = np.empty((len(p), min(knn, len(p))), np.int32), np.empty((len(p), 3), np.float64), np.zeros(4, np.int64)
         self._ck(self.lib.ug_op_pcd_knn_normals_grid(self.ctx, _ptr(p), len(p), int(knn), _ptr(nbr), _ptr(nrm), _ptr(st)))
         return nbr, nrm, dict(zip(self.GRID_STAT_KEYS, (int(v) for v in st)))
+
+    def op_voxel_set(self, a, b, voxel_size, capacity_log2=0):
+        """The voxel set of two float64 clouds alone (``ug_op_voxel_set``) -> int64 ``[6]``: cells of ``a``, of ``b``, of
+        both, of either, skipped points of ``a``, of ``b`` - the ``counts`` of ``harness.metrics.voxel_iou``.  ``capacity_log2`` forces the
+        table size (0: the production rule); a table too small raises."""
+        a = np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, 3)); b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(-1, 3))
+        out = np.zeros(6, np.int64)
+        self._ck(self.lib.ug_op_voxel_set(self.ctx, _ptr(a) if len(a) else None, len(a), _ptr(b) if len(b) else None, len(b), float(voxel_size),
+                                          int(capacity_log2), _ptr(out)))
+        return out
 
     def op_pcd_select(self, values, k):
         """The exact k-th smallest (from 0) of a float32 or float64 array."""

@@ -315,7 +315,8 @@ static void pcd_mean_median(Ctx& c, const double* v, long n, unsigned* sel, unsi
 // launch differently.
 static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, const unsigned char* mask, long n, const long* sample_idx, long n_sample,
                          bool fps, bool grid, const ug_pcd_opts* o, double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out,
-                         long* gt_idx_out, long* search_stats) {
+                         long* gt_idx_out, long* search_stats, const ug_pcd_score_opts* so = nullptr, long* score_counts = nullptr,
+                         long* voxel_counts = nullptr) {
   if (search_stats) for (int k = 0; k < 8; ++k) search_stats[k] = 0;
   UG_REQUIRE(o && gt_pts && mask && out, "options, gt_pts, mask and out32 must not be NULL");
   UG_REQUIRE(n > 0 && n < (1L << 31), "n_pixels must be positive and below 2^31");
@@ -472,6 +473,52 @@ static void eval_pcd_run(Ctx& c, const float* pred_pts, const float* gt_pts, con
     search_stats[2] = gridG.cells; search_stats[3] = cellmax[0]; search_stats[4] = gridP.cells; search_stats[5] = cellmax[1];
     search_stats[6] = (long)c.ws.peak();
   }
+
+  // counts below the thresholds over the two distance arrays just averaged, and the voxel sets of the two clouds behind them
+  if (so && so->n_thresholds > 0) {
+    PcdThresholds t;
+    t.n = so->n_thresholds;
+    for (int k = 0; k < PCD_MAX_THRESHOLDS; ++k) t.tau[k] = k < t.n ? so->thresholds[k] : 0.0;
+    unsigned* cpart = c.ws.get<unsigned>((long)PCD_MAXB * PCD_MAX_THRESHOLDS);
+    std::vector<unsigned> hp;
+    for (int a = 0; a < 2; ++a) {      // 0: accuracy distances -> precision, 1: completion distances -> recall
+      int nb = 0;
+      launch_pcd_count_below(a ? dist2 : dist, ns, t, cpart, &nb, c.stream);
+      UG_CHECK(hipGetLastError());
+      UG_CHECK(hipStreamSynchronize(c.stream));
+      hp.resize((size_t)nb * PCD_MAX_THRESHOLDS);
+      UG_CHECK(hipMemcpy(hp.data(), cpart, hp.size() * 4, hipMemcpyDeviceToHost));
+      for (int k = 0; k < t.n; ++k) {
+        long cnt = 0;
+        for (int b = 0; b < nb; ++b) cnt += hp[(size_t)b * PCD_MAX_THRESHOLDS + k];      // block order
+        score_counts[2 * k + a] = cnt;
+      }
+    }
+  }
+  if (so)
+    for (int k = 0; k < so->n_voxel_sizes; ++k)
+      voxel_set_run(c, moved, ns, g64, ns, so->voxel_sizes[k], voxel_capacity(2 * ns), voxel_counts + 6 * k, "ug_eval_pcd_scores");
+}
+
+// What eval_pcd_run takes from the workspace for n pixels of which m are masked in and ns are evaluated, allocation by allocation as the arena
+// rounds them, the count partials and the voxel table of section 32 included.  Exact for the brute-force search; with the grid the cell tables
+// (they depend on the extent of the clouds) and the scratch of the leftover queries are not in the figure.
+static size_t pcd_scores_request(long n, long m, long ns, bool host_pred, bool has_idx, bool sample, bool grid, int n_thr, int n_vox) {
+  auto r = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  size_t need = (host_pred ? r((size_t)n * 12) : 0) + r((size_t)n * 12) + r((size_t)n) + r((PCD_MAXB + 1) * 4) + 2 * r((size_t)n * 12);
+  if (m == 0) return need;
+  need += r(PCD_SEL_WORDS * 4) + r(16 * 8) + r((size_t)m * 4);
+  if (has_idx) need += r((size_t)ns * 8);
+  need += 2 * r((size_t)ns * 12) + 2 * r((size_t)ns * 24);
+  if (sample) need += r((size_t)m * 4) + 2 * r(2 * PCD_MAXB * 4) + r((size_t)ns * 4) + 2 * r((size_t)ns * 8);
+  need += r((size_t)ns * 4) + r((size_t)ns * 8);
+  if (grid) need += r((size_t)ns * 4) + r(4) + 2 * (r((size_t)PCD_MAXB * 7 * 8) + r(64) + r((size_t)ns * 24) + r((size_t)ns * 4));
+  else { const size_t ny = (size_t)pcd_nn_slices(ns, ns); need += r(ny * ns * 4) + r(ny * ns * 8); }
+  need += r(16 * 8) + r((size_t)PCD_MAXB * 17 * 8);
+  need += 3 * r((size_t)ns * 24) + r((size_t)ns * 4) + 3 * r((size_t)ns * 8);
+  if (n_thr > 0) need += r((size_t)PCD_MAXB * PCD_MAX_THRESHOLDS * 4);
+  if (n_vox > 0) need += voxel_table_bytes(voxel_capacity(2 * ns));
+  return need;
 }
 
 // ---------------------------------------------------------------- clip preparation helpers (ug_prep_*)
@@ -771,6 +818,51 @@ int ug_eval_pcd_ex(ug_ctx* x, const float* pred_pts, const float* gt_pts, const 
     UG_REQUIRE(!fps || !sample_idx, "UG_PCD_FPS picks the points itself: sample_idx must be NULL");
     eval_pcd_run(c, pred_pts, gt_pts, mask, n, sample_idx, n_sample, fps, (flags & UG_PCD_SEARCH_GRID) != 0, o, out, pred_cloud_out, gt_cloud_out,
                  pred_idx_out, gt_idx_out, search_stats);
+  });
+}
+void ug_pcd_score_opts_default(ug_pcd_score_opts* o) {
+  if (!o) return;
+  memset(o, 0, sizeof(*o));
+}
+int ug_eval_pcd_scores(ug_ctx* x, const float* pred_pts, const float* gt_pts, const unsigned char* mask, long n, const long* sample_idx, long n_sample,
+                       const ug_pcd_opts* o, int flags, double* out, float* pred_cloud_out, float* gt_cloud_out, long* pred_idx_out, long* gt_idx_out,
+                       long* search_stats, const ug_pcd_score_opts* so, long* score_counts, long* voxel_counts) {
+  if (!so || (so->n_thresholds == 0 && so->n_voxel_sizes == 0))
+    return ug_eval_pcd_ex(x, pred_pts, gt_pts, mask, n, sample_idx, n_sample, o, flags, out, pred_cloud_out, gt_cloud_out, pred_idx_out, gt_idx_out,
+                          search_stats);
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(so->n_thresholds >= 0 && so->n_thresholds <= PCD_MAX_THRESHOLDS, "n_thresholds must be 0..8");
+    UG_REQUIRE(so->n_voxel_sizes >= 0 && so->n_voxel_sizes <= PCD_MAX_VOXEL_SIZES, "n_voxel_sizes must be 0..4");
+    for (int k = 0; k < so->n_thresholds; ++k)
+      UG_REQUIRE(so->thresholds[k] > 0.0 && std::isfinite(so->thresholds[k]), "every threshold must be positive and finite");
+    for (int k = 0; k < so->n_voxel_sizes; ++k)
+      UG_REQUIRE(so->voxel_sizes[k] > 0.0 && std::isfinite(so->voxel_sizes[k]), "every voxel size must be positive and finite");
+    UG_REQUIRE(so->n_thresholds == 0 || score_counts, "score_counts must not be NULL when thresholds are given");
+    UG_REQUIRE(so->n_voxel_sizes == 0 || voxel_counts, "voxel_counts must not be NULL when voxel sizes are given");
+    const unsigned unknown = (unsigned)flags & ~(unsigned)(UG_PCD_FPS | UG_PCD_SEARCH_GRID);
+    if (unknown) {
+      char hex[16]; snprintf(hex, sizeof hex, "0x%x", unknown);
+      throw std::runtime_error(std::string("ug_eval_pcd_scores: unknown flag bits ") + hex + " (UG_PCD_FPS | UG_PCD_SEARCH_GRID)");
+    }
+    const bool fps = (flags & UG_PCD_FPS) != 0, grid = (flags & UG_PCD_SEARCH_GRID) != 0;
+    UG_REQUIRE(!fps || !sample_idx, "UG_PCD_FPS picks the points itself: sample_idx must be NULL");
+    UG_REQUIRE(mask && n > 0 && n < (1L << 31), "mask must not be NULL and n_pixels must be positive and below 2^31");
+    for (int k = 0; k < 2 * so->n_thresholds; ++k) score_counts[k] = 0;      // what an empty mask returns
+    for (int k = 0; k < 6 * so->n_voxel_sizes; ++k) voxel_counts[k] = 0;
+    // the whole request is sized before the first allocation, so that a workspace too small is reported with the bytes the call needs
+    long m = 0;
+    for (long i = 0; i < n; ++i) m += mask[i] > 0;
+    const bool sample = fps && n_sample > 0 && n_sample < m;
+    const long ns = (sample_idx || sample) ? n_sample : m;
+    UG_REQUIRE(ns >= 0 && ns < (1L << 31), "n_sample out of range");
+    const size_t need = pcd_scores_request(n, m, ns, pred_pts != nullptr, sample_idx != nullptr, sample, grid, so->n_thresholds, so->n_voxel_sizes);
+    const size_t room = c.ws.capacity() - c.ws.mark();
+    if (need > room)
+      throw std::runtime_error("ug_eval_pcd_scores: the workspace is too small: this call needs " + std::to_string(need) + " bytes of it and " +
+                               std::to_string(room) + " are free (raise workspace_bytes in ug_create)");
+    eval_pcd_run(c, pred_pts, gt_pts, mask, n, sample_idx, n_sample, fps, grid, o, out, pred_cloud_out, gt_cloud_out, pred_idx_out, gt_idx_out,
+                 search_stats, so, score_counts, voxel_counts);
   });
 }
 

@@ -372,6 +372,21 @@ int ug_op_pcd_knn_normals_grid(ug_ctx* x, const double* pts, long n, int knn, in
     if (stats) { stats[0] = st.settled; stats[1] = st.left; stats[2] = g.cells; stats[3] = cellmax; }
   });
 }
+// the voxel set alone, in a table of a forced size
+int ug_op_voxel_set(ug_ctx* x, const double* a, long na, const double* b, long nb, double voxel_size, int capacity_log2, long* out6) {
+  UG_TRY(x, {
+    Ctx& c = x->c; Scope sc(c);
+    UG_REQUIRE(out6 && (a || na == 0) && (b || nb == 0), "out6 must not be NULL, nor a cloud with points");
+    UG_REQUIRE(na >= 0 && nb >= 0 && na < (1L << 31) && nb < (1L << 31), "na and nb must be 0 .. 2^31 - 1");
+    UG_REQUIRE(voxel_size > 0.0 && std::isfinite(voxel_size), "voxel_size must be positive and finite");
+    UG_REQUIRE(capacity_log2 >= 0 && capacity_log2 <= 30, "capacity_log2 must be 0 (the production rule) or 1..30");
+    const long capacity = capacity_log2 ? 1L << capacity_log2 : voxel_capacity(na + nb);
+    double* da = c.ws.get<double>(na * 3 + 1); double* db = c.ws.get<double>(nb * 3 + 1);
+    if (na) UG_CHECK(hipMemcpy(da, a, (size_t)na * 24, hipMemcpyHostToDevice));
+    if (nb) UG_CHECK(hipMemcpy(db, b, (size_t)nb * 24, hipMemcpyHostToDevice));
+    voxel_set_run(c, da, na, db, nb, voxel_size, capacity, out6, "ug_op_voxel_set");
+  });
+}
 // farthest-point sampling alone
 int ug_op_pcd_fps(ug_ctx* x, const float* pts, long n, long k, long* idx_out, float* sel_dist_out) {
   UG_TRY(x, {

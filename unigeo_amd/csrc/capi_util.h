@@ -157,6 +157,43 @@ static inline void pcd_knn_search_grid(Ctx& c, const PcdGrid& g, int knn, int* n
   launch_pcd_knn_normals_list(g.pts, g.n, knn, left, nl, nbr, normals, c.stream);
 }
 
+// ------------------------------------------------------------------ voxel set: what ug_eval_pcd_scores (product) and ug_op_voxel_set (test) share
+// the production table: the smallest power of two >= 2 * points, at least 1024 slots - at most half full even when every point has a cell of its own
+static inline long voxel_capacity(long points) {
+  long cap = 1024;
+  while (cap < 2 * points) cap <<= 1;
+  return cap;
+}
+static inline size_t voxel_table_bytes(long capacity) {      // as the arena rounds the four allocations of voxel_set_run
+  auto r256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  return r256((size_t)capacity * 8) + r256((size_t)capacity * 4) + r256(VOX_STAT_WORDS * 4) + r256((size_t)PCD_MAXB * 3 * 4);
+}
+// cells of a (flag 1) and b (flag 2), device float64 [n,3] each, for edge v in a table of `capacity` slots -> out6 = |A|, |B|, |A & B|, |A | B|,
+// skipped points of a, of b.  A probe that ran through the whole table is an error.  Leaves the stream idle and the workspace as it found it.
+static inline void voxel_set_run(Ctx& c, const double* a, long na, const double* b, long nb_, double v, long capacity, long* out6, const char* who) {
+  const size_t mk = c.ws.mark();
+  unsigned long long* keys = c.ws.get<unsigned long long>(capacity); unsigned* flags = c.ws.get<unsigned>(capacity);
+  unsigned* stat = c.ws.get<unsigned>(VOX_STAT_WORDS); unsigned* part = c.ws.get<unsigned>((long)PCD_MAXB * 3);
+  int nb = 0;
+  launch_vox_fill(keys, flags, capacity, stat, c.stream);
+  launch_vox_insert(a, na, v, 1u, keys, flags, capacity, stat, c.stream);
+  launch_vox_insert(b, nb_, v, 2u, keys, flags, capacity, stat, c.stream);
+  launch_vox_count(flags, capacity, part, &nb, c.stream);
+  UG_CHECK(hipGetLastError());
+  UG_CHECK(hipStreamSynchronize(c.stream));
+  unsigned hs[VOX_STAT_WORDS];
+  std::vector<unsigned> hp((size_t)nb * 3);
+  UG_CHECK(hipMemcpy(hs, stat, sizeof(hs), hipMemcpyDeviceToHost));
+  UG_CHECK(hipMemcpy(hp.data(), part, hp.size() * 4, hipMemcpyDeviceToHost));
+  c.ws.release(mk);
+  if (hs[VOX_OVERFLOW])
+    throw std::runtime_error(std::string(who) + ": voxel table overflow: the cells of both clouds do not fit into " + std::to_string(capacity) + " slots");
+  long cnt[3] = {0, 0, 0};
+  for (int i = 0; i < nb; ++i) for (int k = 0; k < 3; ++k) cnt[k] += hp[(size_t)i * 3 + k];      // block order
+  out6[0] = cnt[0] + cnt[2]; out6[1] = cnt[1] + cnt[2]; out6[2] = cnt[2]; out6[3] = cnt[0] + cnt[1] + cnt[2];
+  out6[4] = hs[1]; out6[5] = hs[2];
+}
+
 // the result words of launch_masked_median, once the stream is idle: how many pixels were selected, the lower medians of prediction and ground truth
 static inline void read_masked_median(Ctx& c, const unsigned* sel, unsigned& count, float& mp, float& mg) {
   UG_CHECK(hipStreamSynchronize(c.stream));

@@ -370,6 +370,21 @@ void launch_pcd_move(const double* q, long n, const double* T44, double* out, hi
 void launch_pcd_knn_normals(const double* pts, long n, int knn, int* nbr /* [n][min(knn, n)] or NULL */, double* normals, hipStream_t s);
 void launch_pcd_normal_dot(const double* nq, const double* nt, const int* idx, long n, double* dot, hipStream_t s);
 void launch_pcd_sum(const double* v, long n, double* part /*[PCD_MAXB]*/, int* nb, hipStream_t s);
+// threshold scores and the voxel set (kernels/pcd.hip, kernels/voxel.hip): integer counts only
+#define PCD_MAX_THRESHOLDS 8             // = the thresholds array of ug_pcd_score_opts
+#define PCD_MAX_VOXEL_SIZES 4            // = its voxel_sizes array
+struct PcdThresholds { int n; double tau[PCD_MAX_THRESHOLDS]; };
+// how many of v[0 .. n) lie strictly below each threshold -> part [PCD_MAXB * PCD_MAX_THRESHOLDS] per-workgroup counts, *nb rows written
+void launch_pcd_count_below(const double* v, long n, const PcdThresholds& t, unsigned* part, int* nb, hipStream_t s);
+#define VOX_STAT_WORDS 4                 // stat[0]: a probe ran through the whole table; stat[1] / stat[2]: skipped points of cloud 1 / 2
+#define VOX_OVERFLOW 0
+// keys [capacity] 64-bit words and flags [capacity] 32-bit words, capacity a power of two; fill empties both and zeroes stat
+void launch_vox_fill(unsigned long long* keys, unsigned* flags, long capacity, unsigned* stat, hipStream_t s);
+// the cells of pts [n,3] for edge v go into the table with flag `bit` (1: prediction, 2: ground truth)
+void launch_vox_insert(const double* pts, long n, double v, unsigned bit, unsigned long long* keys, unsigned* flags, long capacity, unsigned* stat,
+                       hipStream_t s);
+// slots with flags 1, 2 and 3 -> part [PCD_MAXB * 3] per-workgroup counts, *nb rows written
+void launch_vox_count(const unsigned* flags, long capacity, unsigned* part, int* nb, hipStream_t s);
 // farthest-point sampling: k picks of a float32 cloud [n,3], 1 <= k <= n < 2^31, in k + 1 stream-ordered launches.
 // Scratch: m [n] the running smallest squared distance, pm / pi [2 * PCD_MAXB] the per-workgroup (best m, lowest index) of the even and odd launches.
 void launch_pcd_fps(const float* p, long n, long k, float* m, float* pm, int* pi, long* idx /*[k]*/, float* sel_dist /*[k]*/, hipStream_t s);

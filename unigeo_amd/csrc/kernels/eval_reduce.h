@@ -25,6 +25,19 @@ template <int OP> __device__ __forceinline__ double eval_block_reduce(double v, 
   __syncthreads();
   return r;
 }
+// the block sum of an integer count, folded the same way; sh holds EVAL_NT words and is free again on return
+__device__ __forceinline__ unsigned eval_block_count(unsigned v, unsigned* sh) {
+  const int tid = threadIdx.x;
+  sh[tid] = v;
+  __syncthreads();
+  for (int o = EVAL_NT / 2; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  const unsigned r = sh[0];
+  __syncthreads();
+  return r;
+}
 // the K block sums of a[0 .. K) -> part[blockIdx.x * K + k]
 template <int K> __device__ __forceinline__ void eval_store_sums(const double (&a)[K], double* sh, double* part) {
   for (int k = 0; k < K; ++k) {

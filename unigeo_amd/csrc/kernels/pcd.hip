@@ -232,6 +232,24 @@ __global__ __launch_bounds__(EVAL_NT) void k_pcd_sum(const double* v, long n, do
   for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) a[0] += v[i];
   eval_store_sums<1>(a, sh, part);
 }
+// how many v[i] lie strictly below each of the nt thresholds, one pass for all of them; a NaN is not below.  Integer
+// counts per workgroup -> part[b * PCD_MAX_THRESHOLDS + k], added by the caller in block order.
+__global__ __launch_bounds__(EVAL_NT) void k_pcd_count_below(const double* v, long n, PcdThresholds t, unsigned* part) {
+  __shared__ unsigned sh[EVAL_NT];
+  unsigned c[PCD_MAX_THRESHOLDS];
+#pragma unroll
+  for (int k = 0; k < PCD_MAX_THRESHOLDS; ++k) c[k] = 0u;
+  for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
+    const double d = v[i];
+#pragma unroll
+    for (int k = 0; k < PCD_MAX_THRESHOLDS; ++k) c[k] += (k < t.n && d < t.tau[k]) ? 1u : 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < PCD_MAX_THRESHOLDS; ++k) {
+    const unsigned r = eval_block_count(c[k], sh);
+    if (threadIdx.x == 0) part[(long)blockIdx.x * PCD_MAX_THRESHOLDS + k] = r;
+  }
+}
 __global__ __launch_bounds__(EVAL_NT) void k_pcd_move(const double* q, long n, const double* T44, double* out) {
   for (long i = (long)blockIdx.x * EVAL_NT + threadIdx.x; i < n; i += (long)gridDim.x * EVAL_NT) {
     double x = q[i * 3], y = q[i * 3 + 1], z = q[i * 3 + 2];
@@ -682,6 +700,10 @@ void launch_pcd_gather(const float* src, const long* idx, long ns, float* out32,
 void launch_pcd_sum(const double* v, long n, double* part, int* nb, hipStream_t s) {
   *nb = eval_nblocks(n);
   hipLaunchKernelGGL(k_pcd_sum, dim3(*nb), dim3(EVAL_NT), 0, s, v, n, part);
+}
+void launch_pcd_count_below(const double* v, long n, const PcdThresholds& t, unsigned* part, int* nb, hipStream_t s) {
+  *nb = eval_nblocks(n);
+  hipLaunchKernelGGL(k_pcd_count_below, dim3(*nb), dim3(EVAL_NT), 0, s, v, n, t, part);
 }
 
 // ------------------------------------------------------------------------------------------------------------- grid launchers

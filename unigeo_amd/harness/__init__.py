@@ -2,7 +2,7 @@
 Plain numpy / Python; the model call inside the loop is the only GPU work."""
 from .io_utils import prepare_gt_label
 from .metrics import (MetricsManager, depth_evaluation, depth_evaluation_in_global_coord, l1_fit, l1_objective, normal_evaluation,
-                      pcd_evaluation, world_points_from_depth)
+                      pcd_evaluation, pcd_threshold_scores, voxel_iou, world_points_from_depth)
 from .camera import camera_pose_evaluation, save_camera_trajectories, tum_poses, write_tum_trajectory
 from .pointmap import pointmap_focal, pointmap_poses, poses_from_pointmap
 from .temporal import aligned_depth, relative_poses, temporal_alignment_error, warp_depth
@@ -18,7 +18,7 @@ from .render import render_mesh, rescaled_size_and_intrinsics
 from .vis import SPECTRAL_R_LUT, colorbar_strip, colorize, panels_u8, read_ply, save_depth_normal_maps, write_ply
 
 __all__ = ["prepare_gt_label", "MetricsManager", "depth_evaluation", "depth_evaluation_in_global_coord",
-           "l1_fit", "l1_objective", "normal_evaluation", "pcd_evaluation", "world_points_from_depth", "evaluate", "parse_dataset_config", "parse_depth_coord",
+           "l1_fit", "l1_objective", "normal_evaluation", "pcd_evaluation", "pcd_threshold_scores", "voxel_iou", "world_points_from_depth", "evaluate", "parse_dataset_config", "parse_depth_coord",
            "parse_metric_config", "parse_pcd_eval_config", "parse_camera_eval_config", "parse_temporal_eval_config",
            "aligned_depth", "relative_poses", "temporal_alignment_error", "warp_depth", "import_class_from_module", "SyntheticGeometryDataset",
            "split_clips", "evaluate_sharded", "ScannetPPDataset", "ScannetPPSequence",

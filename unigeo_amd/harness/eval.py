@@ -20,8 +20,8 @@ from .normals import NORMALS_MODES
 from .pointmap import poses_from_pointmap
 from .temporal import temporal_alignment_error
 from .vis import save_depth_normal_maps, write_ply
-from .metrics import (DEPTH_ALIGNMENTS, DEPTH_ALIGN_SPACES, PCD_KEYS, MetricsManager, check_disp_clip_min, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
-                      pcd_evaluation, world_points_from_depth)
+from .metrics import (DEPTH_ALIGNMENTS, DEPTH_ALIGN_SPACES, PCD_KEYS, PCD_MAX_THRESHOLDS, PCD_MAX_VOXEL_SIZES, MetricsManager, check_disp_clip_min, depth_evaluation, depth_evaluation_in_global_coord, normal_evaluation,
+                      pcd_evaluation, pcd_score_names, world_points_from_depth)
 
 
 def import_class_from_module(module_name, class_name):
@@ -101,7 +101,10 @@ def parse_pcd_eval_config(config):
     (ICP correspondence distance, default 0.1) and ``seed`` (default 0; a clip draws with ``seed + data index``) -> dict, or ``None`` without
     the key.  ``sampling`` is ``random`` (default: the seeded draw) or ``fps`` (farthest-point sampling; ``seed`` is not
     used).  ``search`` is ``brute`` (default) or ``grid`` (the exact search through a uniform grid, DESIGN.md section 20: the same numbers, and the
-    one way to run ``pcd_downsample_num: -1`` on a full clip).  Anything else, and ``vis_pcd`` without ``eval_pcd``, is a ``ValueError``."""
+    one way to run ``pcd_downsample_num: -1`` on a full clip).  Optional ``fscore_thresholds`` (at most 8) and ``voxel_sizes`` (at most 4), lists
+    of positive finite numbers, add ``prec@t`` / ``recall@t`` / ``fscore@t`` and ``iou@v`` to every row; the number in a
+    key is ``format(x, "g")`` and no two entries may be written the same way.  Anything else, and ``vis_pcd`` without ``eval_pcd``, is a
+    ``ValueError``."""
     if "eval_pcd" not in config:
         if config.get("vis_pcd"):
             raise ValueError("vis_pcd needs eval_pcd: the point clouds it writes are the ones eval_pcd aligns")
@@ -113,8 +116,12 @@ def parse_pcd_eval_config(config):
     search = cfg.get("search", "brute")
     if search not in ("brute", "grid"):
         raise ValueError(f"eval_pcd.search must be 'brute' or 'grid', not {search!r}")
-    return {"downsample_num": int(cfg.get("pcd_downsample_num", -1)), "threshold": float(cfg.get("threshold", 0.1)), "seed": int(cfg.get("seed", 0)),
-            "sampling": sampling, "search": search}
+    res = {"downsample_num": int(cfg.get("pcd_downsample_num", -1)), "threshold": float(cfg.get("threshold", 0.1)), "seed": int(cfg.get("seed", 0)),
+           "sampling": sampling, "search": search}
+    for key, limit in (("fscore_thresholds", PCD_MAX_THRESHOLDS), ("voxel_sizes", PCD_MAX_VOXEL_SIZES)):      # absent: the dict is what it was
+        if key in cfg:
+            res[key] = pcd_score_names(cfg[key], f"eval_pcd.{key}", limit)[0]
+    return res
 
 
 CAMERA_EVAL_KEYS = ("metric_names", "reproj_px", "focal")
@@ -299,6 +306,7 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
         if pcd_cfg is not None:
             kw = {"threshold": pcd_cfg["threshold"], "downsample_num": pcd_cfg["downsample_num"], "seed": pcd_cfg["seed"] + data_idx,
                   "sampling": pcd_cfg["sampling"], "search": pcd_cfg["search"]}
+            kw.update({k: pcd_cfg[k] for k in ("fscore_thresholds", "voxel_sizes") if k in pcd_cfg})
             pts = output.get("pred_world_pts")
             if hasattr(pts, "detach"):
                 pts = pts.detach().cpu().numpy()
@@ -313,6 +321,7 @@ def evaluate(config, dataset=None, model=None, save_dir="./debug_output", rank=0
             else:
                 res = pcd_evaluation(pts, gt["gt_world_pts"], gt["gt_masks"], gt["gt_rgbs"], **kw)
             metric.update({k: res[k] for k in PCD_KEYS})
+            metric.update({k: v for k, v in res.items() if "@" in k})      # prec@t, recall@t, fscore@t, iou@v
             if config.get("vis_pcd"):
                 pcd_dir = os.path.join(save_dir, f"pcd_{seq}")
                 os.makedirs(pcd_dir, exist_ok=True)

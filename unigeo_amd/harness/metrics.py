@@ -531,27 +531,142 @@ def icp_point_to_point(src, dst, threshold, max_iteration=30, nn=_nn):
     return T, it, fit, rmse, hist
 
 
-def pcd_scores(gt_pts, pred_pts, gt_normals, pred_normals, nn=_nn):
-    """``accuracy`` and ``completion`` of ``metrics/utils.py:14-42`` -> the eight reference keys."""
+# ---- precision / recall / F-score at distance thresholds and the voxel IoU
+PCD_MAX_THRESHOLDS, PCD_MAX_VOXEL_SIZES = 8, 4      # the arrays of ug_pcd_score_opts
+VOXEL_HALF = 1 << 20                                # a cell index lies in (-2^20, 2^20): kernels/voxkey.h
+
+
+def pcd_score_names(values, what, limit):
+    """The configured thresholds or voxel sizes -> ``(float values, their names)``; a name is ``format(x, "g")``.  At most ``limit``
+    real numbers, each positive and finite, no two with the same name: anything else is a ``ValueError``."""
+    if isinstance(values, (str, bytes)) or not hasattr(values, "__iter__"):
+        raise ValueError(f"{what} must be a list of positive finite numbers, not {values!r}")
+    vals = []
+    for v in values:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{what}: {v!r} is not a number")
+        v = float(v)
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError(f"{what}: {v!r} is not positive and finite")
+        vals.append(v)
+    if len(vals) > limit:
+        raise ValueError(f"{what}: at most {limit} values, not {len(vals)}")
+    names = [format(v, "g") for v in vals]
+    if len(set(names)) != len(names):
+        raise ValueError(f"{what}: two values are written the same way: {names}")
+    return vals, names
+
+
+def pcd_threshold_values(names, counts, n):
+    """``prec@t = n_prec / n``, ``recall@t = n_rec / n`` and ``fscore@t = 2 P R / (P + R)`` (0 when ``P + R == 0``) in float64 from the integer
+    counts ``[len(names), 2]``; NaN for ``n == 0``.  The device path forms its values here too."""
+    res = {}
+    for name, (n_prec, n_rec) in zip(names, np.asarray(counts, np.int64).reshape(-1, 2).tolist()):
+        if n == 0:
+            P = R = F = math.nan
+        else:
+            P, R = float(n_prec) / float(n), float(n_rec) / float(n)
+            F = 0.0 if P + R == 0.0 else 2.0 * P * R / (P + R)
+        res.update({f"prec@{name}": P, f"recall@{name}": R, f"fscore@{name}": F})
+    return res
+
+
+def pcd_threshold_scores(d_acc, d_comp, thresholds):
+    """Precision, recall and F-score at distance thresholds (Tanks and Temples) -> ``prec@t``, ``recall@t``, ``fscore@t`` per threshold and
+    ``score_counts`` int64 ``[len(thresholds), 2]``.  ``d_acc[i]`` is the distance of prediction ``i`` to its nearest ground-truth point,
+    ``d_comp[j]`` that of ground-truth point ``j`` to its nearest prediction: the arrays ``acc`` and ``comp`` are the means of.
+    ``n_prec = #{d_acc < t}``, ``n_rec = #{d_comp < t}``, both strict; a NaN distance is not below.
+
+    ``np.float32(recall@0.05)`` is the reference's ``completion_ratio(gt, rec)`` with its default ``dist_th=0.05``
+    (``metrics/utils.py:7-11``, called nowhere there): the float32 mean of a 0 / 1 array is that quotient rounded once, as long as the
+    count stays below 2^24."""
+    taus, names = pcd_score_names(thresholds, "fscore_thresholds", PCD_MAX_THRESHOLDS)
+    d1, d2 = np.asarray(d_acc, np.float64).reshape(-1), np.asarray(d_comp, np.float64).reshape(-1)
+    counts = np.zeros((len(taus), 2), np.int64)
+    with np.errstate(invalid="ignore"):
+        for k, t in enumerate(taus):
+            counts[k] = int(np.count_nonzero(d1 < t)), int(np.count_nonzero(d2 < t))
+    res = pcd_threshold_values(names, counts, len(d1))
+    res["score_counts"] = counts
+    return res
+
+
+def voxel_keys(pts, voxel_size):
+    """The sorted distinct packed cells of a cloud ``[n,3]`` and how many points were skipped.  The cell is ``floor(x / v)`` per axis, each
+    step one float64 operation, from the world origin; a point with a non-finite coordinate or a cell outside ``(-2^20, 2^20)`` is
+    skipped.  Packed as ``kernels/voxkey.h`` packs it: ``((ix + 2^20) << 42) | ((iy + 2^20) << 21) | (iz + 2^20)``."""
+    p = np.asarray(pts, np.float64).reshape(-1, 3)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        f = np.floor(p / np.float64(voxel_size))
+        keep = ((f > -float(VOXEL_HALF)) & (f < float(VOXEL_HALF))).all(1)      # a NaN fails both
+    i = (f[keep].astype(np.int64) + VOXEL_HALF).astype(np.uint64)
+    keys = (i[:, 0] << np.uint64(42)) | (i[:, 1] << np.uint64(21)) | i[:, 2]
+    return np.unique(keys), int(len(p) - np.count_nonzero(keep))
+
+
+def voxel_iou(pred, gt, voxel_size):
+    """Occupancy IoU of two clouds on one voxel grid of edge ``voxel_size`` anchored at the world origin -> ``(iou, counts)``:
+    ``counts`` int64 ``[6]`` = cells of the prediction, of the ground truth, of both, of either, skipped predictions, skipped ground-truth
+    points; ``iou = both / either`` in float64, NaN when neither cloud has a cell.
+
+    UNPINNED: the reference's ``compute_iou`` (``metrics/utils.py:45-60``) is called nowhere and takes Open3D voxel grids, each with its own
+    origin (the cloud's minimum bound), so their index sets are not comparable; open3d is not installed.  One common origin is a
+    deliberate difference."""
+    v = float(voxel_size)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"voxel_iou: voxel_size must be positive and finite, not {voxel_size!r}")
+    kp, sp = voxel_keys(pred, v)
+    kg, sg = voxel_keys(gt, v)
+    both = int(len(np.intersect1d(kp, kg, assume_unique=True)))
+    either = len(kp) + len(kg) - both
+    counts = np.array([len(kp), len(kg), both, either, sp, sg], np.int64)
+    return (float(both) / float(either) if either else math.nan), counts
+
+
+def pcd_voxel_values(names, counts):
+    """``iou@v = both / either`` in float64 from the integer counts ``[len(names), 6]``, NaN for an empty union."""
+    return {f"iou@{name}": (float(c[2]) / float(c[3]) if c[3] else math.nan)
+            for name, c in zip(names, np.asarray(counts, np.int64).reshape(-1, 6).tolist())}
+
+
+def _pcd_extra_scores(d_acc, d_comp, pred_pts, gt_pts, fscore_thresholds, voxel_sizes):
+    res = {}
+    if len(fscore_thresholds):
+        res.update(pcd_threshold_scores(d_acc, d_comp, fscore_thresholds))
+    if len(voxel_sizes):
+        vs, names = pcd_score_names(voxel_sizes, "voxel_sizes", PCD_MAX_VOXEL_SIZES)
+        counts = np.stack([voxel_iou(pred_pts, gt_pts, v)[1] for v in vs], 0)
+        res.update(pcd_voxel_values(names, counts))
+        res["voxel_counts"] = counts
+    return res
+
+
+def pcd_scores(gt_pts, pred_pts, gt_normals, pred_normals, nn=_nn, fscore_thresholds=(), voxel_sizes=()):
+    """``accuracy`` and ``completion`` of ``metrics/utils.py:14-42`` -> the eight reference keys; with ``fscore_thresholds`` / ``voxel_sizes``
+    also the keys of ``pcd_threshold_scores`` over the same two distance arrays and ``iou@v`` / ``voxel_counts``."""
     d1, i1 = nn(pred_pts, gt_pts)
     d2, i2 = nn(gt_pts, pred_pts)
     n1 = np.abs(np.sum(gt_normals[i1] * pred_normals, axis=-1))
     n2 = np.abs(np.sum(gt_normals * pred_normals[i2], axis=-1))
-    return {"acc": float(np.mean(d1)), "comp": float(np.mean(d2)), "nc1": float(np.mean(n1)), "nc2": float(np.mean(n2)),
-            "acc_med": float(np.median(d1)), "comp_med": float(np.median(d2)), "nc1_med": float(np.median(n1)), "nc2_med": float(np.median(n2))}
+    res = {"acc": float(np.mean(d1)), "comp": float(np.mean(d2)), "nc1": float(np.mean(n1)), "nc2": float(np.mean(n2)),
+           "acc_med": float(np.median(d1)), "comp_med": float(np.median(d2)), "nc1_med": float(np.median(n1)), "nc2_med": float(np.median(n2))}
+    res.update(_pcd_extra_scores(d1, d2, pred_pts, gt_pts, fscore_thresholds, voxel_sizes))
+    return res
 
 
-def pcd_metrics_from_clouds(p, g, threshold=0.1, knn=30, max_iteration=30, nn=_nn, knn_fn=None):
+def pcd_metrics_from_clouds(p, g, threshold=0.1, knn=30, max_iteration=30, nn=_nn, knn_fn=None, fscore_thresholds=(), voxel_sizes=()):
     """ICP, normals and scores of two aligned float32 clouds ``[n,3]`` -> the eight keys plus the ICP record; NaN scores for no point.
-    ``nn`` / ``knn_fn`` do the searches (defaults: the k-d tree or ``nn_brute``, and ``knn_brute``)."""
+    ``nn`` / ``knn_fn`` do the searches (defaults: the k-d tree or ``nn_brute``, and ``knn_brute``).  ``fscore_thresholds`` / ``voxel_sizes``
+    as in ``pcd_scores``: scored on the moved prediction against the ground truth."""
     p64, g64 = np.asarray(p, np.float32).astype(np.float64), np.asarray(g, np.float32).astype(np.float64)
     if len(p64) == 0:
         res = {k: math.nan for k in PCD_KEYS}
+        res.update(_pcd_extra_scores(p64[:, 0], p64[:, 0], p64, g64, fscore_thresholds, voxel_sizes))
         res.update(icp_iterations=0, icp_fitness=0.0, icp_rmse=0.0, transformation=np.eye(4))
         return res
     T, it, fit, rmse, hist = icp_point_to_point(p64, g64, threshold, max_iteration, nn)
     moved = _move(T, p64)
-    res = pcd_scores(g64, moved, knn_normals(g64, knn, knn_fn), knn_normals(moved, knn, knn_fn), nn)
+    res = pcd_scores(g64, moved, knn_normals(g64, knn, knn_fn), knn_normals(moved, knn, knn_fn), nn, fscore_thresholds, voxel_sizes)
     res.update(icp_iterations=it, icp_fitness=fit, icp_rmse=rmse, transformation=T, icp_history=hist)
     return res
 
@@ -601,7 +716,7 @@ def pcd_sample_indices_fps(p, g, downsample_num):
 
 
 def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample_num=-1, seed=0, knn=30, max_iteration=30, sampling="random",
-                   search="brute"):
+                   search="brute", fscore_thresholds=(), voxel_sizes=()):
     """``pcd_evaluation`` of the reference (``metrics/eval_pcd.py:10-168``) -> dict: masked selection in pixel order,
     ``pcd_align``, seeded downsampling (the reference draws from the unseeded global generator and raises when ``downsample_num`` exceeds the
     point count; here that uses every point), point-to-point ICP from the identity, KNN normals, ``accuracy`` / ``completion``.
@@ -609,12 +724,18 @@ def pcd_evaluation(pred_pts, gt_pts, masks, rgbs=None, threshold=0.1, downsample
     ``sampling="fps"`` ignores ``seed``, samples each aligned cloud with ``pcd_fps_indices`` and adds ``pred_idx`` /
     ``gt_idx``, the picked positions among the masked points; each cloud then carries the colours of its own points.
     ``search="grid"`` does every search with ``nn_grid`` / ``knn_grid``, which return what ``nn_brute`` / ``knn_brute``
-    return; ``search="brute"`` keeps the default searches."""
+    return; ``search="brute"`` keeps the default searches.
+    ``fscore_thresholds`` (at most 8) and ``voxel_sizes`` (at most 4), both empty by default, add ``prec@t`` / ``recall@t`` / ``fscore@t`` with
+    ``score_counts`` and ``iou@v`` with ``voxel_counts`` (the number in a key is ``format(x, "g")``); without them the
+    dict is what it was."""
+    pcd_score_names(fscore_thresholds, "fscore_thresholds", PCD_MAX_THRESHOLDS)
+    pcd_score_names(voxel_sizes, "voxel_sizes", PCD_MAX_VOXEL_SIZES)
     if sampling not in ("random", "fps"):
         raise ValueError(f"pcd_evaluation: sampling must be 'random' or 'fps', not {sampling!r}")
     if search not in ("brute", "grid"):
         raise ValueError(f"pcd_evaluation: search must be 'brute' or 'grid', not {search!r}")
     how = {"nn": nn_grid, "knn_fn": knn_grid} if search == "grid" else {}
+    how.update(fscore_thresholds=fscore_thresholds, voxel_sizes=voxel_sizes)
     m = _np(masks).reshape(-1) > 0
     p = _np(pred_pts).astype(np.float32).reshape(-1, 3)[m]
     g = _np(gt_pts).astype(np.float32).reshape(-1, 3)[m]
